@@ -220,7 +220,15 @@ def parse_args(argv=None):
                         '(learner.py:67-78: its rows no longer sum to 1); 0 = all columns')
     p.add_argument('--tol', type=float, default=0.0,
                    help='stop-rule tolerance of nmf.py:207,215 (relative; x n x f inside).  0 = MultimodalLearner.train')
-    return p.parse_args(argv)
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed segments, write what the last one computed as DIR/<name>.npy (float32, float64 in '
+                        'the f64 mode; at most 64 MB): fit -- W (a fixed seeded sample of its rows, W_rows), H, errors; '
+                        'transform -- W (sampled likewise), errors.  Same arguments, same inputs: two builds compare output '
+                        'for output')
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 def make_H0(seed, f, k):
@@ -309,6 +317,55 @@ def measured_clock(args, n_local):
                     if 'k_rowpass' in kname and 'column-split' not in kname and v.get('sclk_mhz_from_grbm_gui_active'):
                         return v['sclk_mhz_from_grbm_gui_active']
     return None
+
+
+# --dump-outputs stays within 64 MB: 40 for W's row sample and its row indices, 16 for H (its columns sampled beyond that, with
+# their indices), the rest for the loss record
+DUMP_W_BYTES = 40 << 20
+DUMP_H_BYTES = 16 << 20
+
+
+def dump_sample(count, item_bytes, budget, seed):
+    """Sorted indices of at most budget // item_bytes of `count` rows (or columns), drawn from a fixed stream: all of them
+    when they fit.  The draw depends on the shape and the seed only, so runs with the same arguments sample the same rows."""
+    m = max(1, budget // item_bytes)
+    if count <= m:
+        return np.arange(count)
+    return np.sort(np.random.RandomState(seed).choice(count, m, replace=False))
+
+
+def collect_outputs(args, model, dist, world, rank, r0, r1, errors, with_H):
+    """What the caller of the timed path receives after its last step: W (a seeded sample of the GLOBAL rows, so that runs on
+    any number of ranks sample the same rows; every rank contributes its own), H when `with_H`, and the loss record.
+    A collective when world > 1: every rank calls it.  Returns {name: array} on rank 0, None elsewhere."""
+    dtype = np.float64 if args.precision == 'f64' else np.float32
+    item = np.dtype(dtype).itemsize
+    rows = dump_sample(model.n_total, model.k * item + 8, DUMP_W_BYTES, args.seed + 17)        # (+ 8: the row's index)
+    mine = rows[(rows >= r0) & (rows < r1)]
+    part = model.get_W_local(dtype=dtype)[mine - r0]
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, part)
+        part = np.concatenate(parts, axis=0)          # (ranks hold ascending row ranges: the sample's order)
+    if rank != 0:
+        return None
+    out = {'W': part, 'W_rows': rows.astype(np.float64), 'errors': np.asarray(errors, dtype=np.float64)}
+    if with_H:
+        H = model.get_H(dtype=dtype)
+        cols = dump_sample(H.shape[1], H.shape[0] * item + 8, DUMP_H_BYTES, args.seed + 18)
+        if cols.size < H.shape[1]:
+            H = H[:, cols]
+            out['H_cols'] = cols.astype(np.float64)
+        out['H'] = np.ascontiguousarray(H)
+    return out
+
+
+def write_outputs(path, outputs):
+    """DIR/<name>.npy for every output; returns the directory and the arrays' shapes for the result line."""
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(path, name + '.npy'), arr)
+    return {'dir': path, 'arrays': {name: list(arr.shape) for name, arr in outputs.items()}}
 
 
 def host_info():
@@ -473,6 +530,11 @@ def run_transform(args, torch, dist, model, H0, world, rank, n_local, r0, r1, fe
             segments.append(float(t.item()))
         for key in prof_tot:
             prof_tot[key] += prof[key]
+    dumped = None
+    if args.dump_outputs:
+        outputs = collect_outputs(args, tmodel, dist, world, rank, r0, r1, last[0], with_H=False)
+        if outputs is not None:
+            dumped = write_outputs(args.dump_outputs, outputs)
     if rank != 0:
         if tmodel is not model:
             tmodel.close()
@@ -545,6 +607,8 @@ def run_transform(args, torch, dist, model, H0, world, rank, n_local, r0, r1, fe
         'kernels': {'iteration_algorithmic_tflops': 4.0 * n * fs * k / (1e3 * elapsed / args.steps * 1e-3) / 1e12,
                     'rest_of_the_iteration_ms': 1e3 * elapsed / args.steps - row_ms},
     }
+    if dumped is not None:
+        out['dump_outputs'] = dumped
     if n_gpus == 1 and not args.no_cpu_baseline:
         out.update(transform_cpu_baseline_and_parity(args, H, fs))
     if tmodel is not model:
@@ -728,6 +792,12 @@ def main():
     else:
         segments, fits, prof_tot, tail_rows, fp8 = run_segments(args.repeats)
         power_clock = None
+    # (before the 16-bit segment below: it runs the same model again)
+    dumped = None
+    if args.dump_outputs:
+        outputs = collect_outputs(args, model, dist, world, rank, r0, r1, fits[-1][0], with_H=True)
+        if outputs is not None:
+            dumped = write_outputs(args.dump_outputs, outputs)
     # The same workload with 16-bit ratio tiles and the f16-operand column pass (KLNMF_QTILE=16 is read at every loop's
     # entry): the number the north star's "bf16/16-bit MFMA contractions" wording describes, beside the headline one.
     value_16bit = None
@@ -949,6 +1019,8 @@ def main():
                                                       if MEASURED_ITERATION['bytes'] else None,
             },
         }
+        if dumped is not None:
+            out['dump_outputs'] = dumped
         if n_gpus == 1 and not args.no_cpu_baseline:
             base, sample = cpu_baseline(args)
             out['cpu_baseline'] = base

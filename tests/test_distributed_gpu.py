@@ -265,17 +265,21 @@ def test_collective_branch_refuses_together(monkeypatch):
 
 
 @pytest.mark.gpu
-def test_bench_two_rank_rehearsal():
+def test_bench_two_rank_rehearsal(tmp_path):
     """bench.py's N > 1 code path end to end on one GPU (KLNMF_BENCH_REHEARSAL: both ranks on device 0, gloo): shard
-    generation from the seeded blocks, the common storage factor, the sharded loop, max-over-ranks timing, one JSON line."""
+    generation from the seeded blocks, the common storage factor, the sharded loop, max-over-ranks timing, one JSON line.
+    --dump-outputs: the ranks' sampled rows of W, H and the loss record equal a one-process run's on the same arguments (the
+    same seeded sample of the global rows; the numerator summed in another order)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, KLNMF_BENCH_REHEARSAL='1')
+    common = ['--steps', '4', '--warmup', '2', '--repeats', '2', '--rows', '20000', '--features', '512', '--components', '40',
+              '--no-cpu-baseline']
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-           '--master-port', str(_free_port()), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2',
-           '--repeats', '2', '--rows', '20000', '--features', '512', '--components', '40', '--no-cpu-baseline']
+           '--master-port', str(_free_port()), os.path.join(root, 'bench.py'), '--gpus', '2'] + common \
+        + ['--dump-outputs', str(tmp_path / 'two')]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1]
@@ -289,6 +293,17 @@ def test_bench_two_rank_rehearsal():
     assert cfg['collective_path'] == 'torch' and 'rccl_ranks' in cfg and cfg['rccl_ranks'] is None
     assert cfg['fp8']['source'] == 'klnmf_query' and cfg['fp8']['timed_iterations_with_fp8_ratio_tiles'] == 0      # 10 016 rows per rank
     assert d['dtype'] == 'f16' and d['value_16bit'] is None
+    assert d['dump_outputs']['arrays'] == {'W': [20000, 40], 'W_rows': [20000], 'errors': [6], 'H': [40, 512]}
+    r1 = subprocess.run([sys.executable, os.path.join(root, 'bench.py')] + common + ['--dump-outputs', str(tmp_path / 'one')],
+                        capture_output=True, text=True, timeout=300, cwd=root)
+    assert r1.returncode == 0, r1.stderr[-2000:]
+    two, one = ({name: np.load(str(tmp_path / run / (name + '.npy'))) for name in ('W', 'W_rows', 'errors', 'H')}
+                for run in ('two', 'one'))
+    assert one['W'].dtype == np.float32 and np.array_equal(one['W_rows'], two['W_rows'])
+    assert d['loss_last'] == two['errors'][-1]
+    np.testing.assert_allclose(two['errors'], one['errors'], rtol=2e-4)
+    for name in ('W', 'H'):
+        assert np.abs(two[name] - one[name]).max() <= 1e-2 * np.abs(one[name]).max(), name
 
 
 @pytest.mark.gpu

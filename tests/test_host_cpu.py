@@ -218,6 +218,60 @@ def test_bench_defaults_follow_the_measurement_contract():
     # the CPU sample is SURVEY 8d's n = 100 000 (more than 65 536: the parity leg on it runs fp8 tiles and the fp8 x fp8 column
     # pass), 1 + 5 iterations: about 25 s of fp64 work on the GPU box's host, 4 of the 6 GPU iterations on fp8
     assert a.cpu_rows == 100000 and a.cpu_iters == 5 and a.segment_timeout > 0
+    assert a.dump_outputs is None
+    with pytest.raises(SystemExit):
+        bench.parse_args(['--steps', '0'])
+
+
+def test_bench_dump_outputs_are_a_fixed_sample_within_64_mb(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: W's rows (and H's columns, where H alone would exceed its share) are a seeded sample that
+    depends on the arguments only; at the default shape every mode stays within 64 MB; a shard contributes exactly the
+    sampled rows it holds, and the files load back as written."""
+    import bench
+
+    class Shard(object):             # what collect_outputs reads of a ShardedKLNMF
+        def __init__(self, n_total, r0, r1, f, k):
+            self.n_total, self.k, self.r0, self.r1, self.f = n_total, k, r0, r1, f
+
+        def get_W_local(self, dtype=np.float64):
+            return np.repeat(np.arange(self.r0, self.r1, dtype=dtype)[:, None], self.k, axis=1)      # each row holds its index
+
+        def get_H(self, dtype=np.float64):
+            return np.arange(self.k * self.f, dtype=dtype).reshape(self.k, self.f)
+
+    for precision, item in (('f16', 4), ('f32', 4), ('f64', 8)):
+        for n, f, k in ((1000000, 4096, 200), (4000000, 2000000, 1)):          # (the default shape; one where indices weigh most)
+            a = bench.parse_args(['--precision', precision, '--rows', str(n), '--features', str(f), '--components', str(k)])
+            rows = bench.dump_sample(n, k * item + 8, bench.DUMP_W_BYTES, a.seed + 17)
+            cols = bench.dump_sample(f, k * item + 8, bench.DUMP_H_BYTES, a.seed + 18)
+            total = rows.size * (k * item + 8) + k * cols.size * item + (cols.size * 8 if cols.size < f else 0) \
+                + (a.warmup + a.steps) * 8
+            assert total <= 64 << 20 and 0 < rows.size < n and (cols.size == f) == (k > 1)
+            assert np.array_equal(rows, bench.dump_sample(n, k * item + 8, bench.DUMP_W_BYTES, a.seed + 17))
+            assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < n
+
+    a = bench.parse_args(['--rows', '5000', '--features', '300', '--components', '7', '--dump-outputs', str(tmp_path)])
+    full = bench.collect_outputs(a, Shard(5000, 0, 5000, 300, 7), None, 1, 0, 0, 5000, [3.0, 2.0], with_H=True)
+    assert full['W'].dtype == np.float32 and full['W'].shape == (5000, 7) and 'H_cols' not in full
+    assert np.array_equal(full['W_rows'], np.arange(5000.0)) and full['H'].shape == (7, 300)
+    # a sampled W (the budget shrunk to sample at a small shape): every rank contributes the sampled rows of its own range, in order
+    monkeypatch.setattr(bench, 'DUMP_W_BYTES', 1 << 16)
+    a = bench.parse_args(['--rows', '3000', '--features', '64', '--components', '5'])
+    one = bench.collect_outputs(a, Shard(3000, 0, 3000, 64, 5), None, 1, 0, 0, 3000, [1.0], with_H=False)
+    assert 'H' not in one and one['W'].shape[0] == one['W_rows'].size < 3000
+    assert np.array_equal(one['W'][:, 0], one['W_rows']) and np.array_equal(one['W'][:, -1], one['W_rows'])
+    halves = [bench.collect_outputs(a, Shard(3000, r0, r1, 64, 5), None, 1, 0, r0, r1, [1.0], with_H=False)['W']
+              for r0, r1 in ((0, 1504), (1504, 3000))]
+    assert np.array_equal(np.concatenate(halves), one['W'])
+    monkeypatch.setattr(bench, 'DUMP_H_BYTES', 1 << 10)
+    sampled = bench.collect_outputs(a, Shard(3000, 0, 3000, 64, 5), None, 1, 0, 0, 3000, [1.0], with_H=True)
+    cols = sampled['H_cols'].astype(np.int64)
+    assert 0 < cols.size < 64 and np.array_equal(sampled['H'], Shard(3000, 0, 3000, 64, 5).get_H(np.float32)[:, cols])
+    written = bench.write_outputs(str(tmp_path), full)
+    assert written['arrays']['W'] == [5000, 7]
+    for name, arr in full.items():
+        back = np.load(os.path.join(str(tmp_path), name + '.npy'))
+        assert back.dtype in (np.float32, np.float64) and np.array_equal(back, arr)
 
 
 def test_scale_inverse_scales_W_columns_and_H_rows():
