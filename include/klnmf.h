@@ -46,6 +46,11 @@ extern "C" {
 #define KLNMF_PREC_BF16     KLNMF_PREC_F16      /* round-1 name of the mode (its operands were bf16 then) */
 /* (3 was KLNMF_PREC_F16_V32 -- the same kernels on fp32-stored V -- until round 5: retired, it missed the 1e-4 bar on a
  *  BASELINE shape and kept the generation-1 kernels in the library for no measured benefit) */
+#define KLNMF_PREC_BF16X3   4        /* the fp32 mode (fp32 storage, loop, loss partials in fp64, every shape, any k, CSR on the
+                                      * fp32 sparse kernels, any eps) with its three dense contractions on the bf16 matrix
+                                      * cores: each fp32 operand x split into hi = bf16(x) and lo = bf16(x - hi), products
+                                      * hi.hi + hi.lo + lo.hi accumulated in fp32 -- each product within ~2^-16 of a.b
+                                      * (relative), no scaling (bf16 has fp32's exponent range; operands below 3.39e38) */
 
 /* host element types for uploads / downloads */
 #define KLNMF_DT_F32        0

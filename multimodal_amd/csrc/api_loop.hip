@@ -254,8 +254,18 @@ void sparse_Q(klnmf_ctx *c, int write_q, double eps, const DecideArgs &dec) {
     HIPCHK(hipGetLastError());
 }
 
-// k_gemm: 64 x 64 tiles, the inner product on the fp64 / fp32 MFMA (exact.hip.h)
-#define KL_GEMM_TT(tt, T, EPI, grid, stream, ...) hipLaunchKernelGGL((k_gemm<T, EPI, 4, true>), grid, dim3(256), 0, stream, __VA_ARGS__)
+// k_gemm: 64 x 64 tiles, the inner product on the fp64 / fp32 MFMA (exact.hip.h); KLNMF_PREC_BF16X3 (fp32 storage): the same
+// launch on the split-operand bf16 MFMA (split3.hip.h, same arguments and epilogues)
+#define KL_GEMM_TT(tt, T, EPI, grid, stream, ...)                                                                     \
+    do {                                                                                                            \
+        if constexpr (std::is_same<T, float>::value) {                                                              \
+            if (c->prec == KLNMF_PREC_BF16X3) {                                                                     \
+                hipLaunchKernelGGL((k_gemm_x3<EPI>), grid, dim3(256), 0, stream, __VA_ARGS__);                      \
+                break;                                                                                              \
+            }                                                                                                       \
+        }                                                                                                           \
+        hipLaunchKernelGGL((k_gemm<T, EPI, 4, true>), grid, dim3(256), 0, stream, __VA_ARGS__);                     \
+    } while (0)
 
 // dec.on: the stop rule rides in the one-block loss reduction (single-context loops: no k_decide launch)
 template <typename T>
@@ -1168,7 +1178,7 @@ int klnmf_step_Q(klnmf_ctx *c) {
 int klnmf_step_W(klnmf_ctx *c) {
     return guarded([&] {
         need_problem(c);
-        if (!c->is_exact()) fail(KLNMF_ERR_UNSUPP, "step API needs KLNMF_PREC_F64/F32");
+        if (!c->is_exact()) fail(KLNMF_ERR_UNSUPP, "step API needs KLNMF_PREC_F64/F32/BF16X3");
         reset_state(c);
         EXACT_CALL(c, exact_W, c->sparse ? c->sp_q : c->Q, 1);
         c->cur ^= 1;
@@ -1179,7 +1189,7 @@ int klnmf_step_W(klnmf_ctx *c) {
 int klnmf_step_H(klnmf_ctx *c) {
     return guarded([&] {
         need_problem(c);
-        if (!c->is_exact()) fail(KLNMF_ERR_UNSUPP, "step API needs KLNMF_PREC_F64/F32");
+        if (!c->is_exact()) fail(KLNMF_ERR_UNSUPP, "step API needs KLNMF_PREC_F64/F32/BF16X3");
         reset_state(c);
         EXACT_CALL(c, exact_N, c->cur);
         EXACT_CALL(c, exact_H);

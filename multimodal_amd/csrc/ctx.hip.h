@@ -20,11 +20,13 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/klnmf.h"
 #include "common.hip.h"
 #include "exact.hip.h"
+#include "split3.hip.h"
 #include "sparseb.hip.h"
 #include "mfma.hip.h"
 #include "mfma4.hip.h"
@@ -377,7 +379,9 @@ struct klnmf_ctx {
     int comm_rank = 0, comm_size = 1;
     double *comm_scratch = nullptr;       // 8 doubles on the device, owned by the communicator (not by a problem)
 
-    bool is_exact() const { return prec == KLNMF_PREC_F64 || prec == KLNMF_PREC_F32; }
+    // the exact modes' storage, loop and kernels; KLNMF_PREC_BF16X3 is the fp32 side of them with the dense contractions on
+    // the split-operand bf16 kernel (split3.hip.h)
+    bool is_exact() const { return prec == KLNMF_PREC_F64 || prec == KLNMF_PREC_F32 || prec == KLNMF_PREC_BF16X3; }
     // fp8 ratio tiles from how many rows per context?  Their e4m3 rounding only enters the H numerator, a sum over all rows
     // (relative error ~ 0.036 sqrt(2 / n)); measured against the fp64 oracle (scripts/fp8_rows_survey.py,
     // profiles/r03_fp8_rows_survey.txt): final-KL deviation 1.7e-5 .. 3.5e-5 from 4096 to 50 000 rows at k = 50, 6.7e-6 .. 1.5e-5

@@ -22,8 +22,9 @@ the loss is recorded before each update and the breaking iteration's loss is not
 appended (q5, nmf.py:214-220).
 
 Extra (non-reference) constructor arguments: `precision` ('f64' default =
-the reference's float64 arithmetic; 'f32'; 'f16' (= 'bf16') = MFMA fast path with V
-stored as power-of-two-scaled fp16; 'auto'), `device`.  Environment: KLNMF_PRECISION, KLNMF_DEVICE.
+the reference's float64 arithmetic; 'f32'; 'bf16x3' = the f32 mode with its contractions on the bf16 matrix cores, every
+fp32 operand split into two bf16 parts (hi.hi + hi.lo + lo.hi, fp32 accumulation: each product within ~2^-16 of a.b; any
+shape, any k, any eps); 'f16' (= 'bf16') = MFMA fast path with V stored as power-of-two-scaled fp16; 'auto'), `device`.  Environment: KLNMF_PRECISION, KLNMF_DEVICE.
 """
 import os
 import sys
@@ -76,7 +77,8 @@ def _note_once(key, text):
 def resolve_precision(precision, n, f, k):
     """The arithmetic one problem runs in.  'auto' by size (above); the 16-bit modes hand k > 512 to the fp32 kernels of the
     same library (LDS-tiled VALU GEMMs: any k, at least the 16-bit mode's accuracy) instead of refusing the problem -- and
-    say so once on stderr (the fp32 kernels are an order of magnitude slower than the MFMA path)."""
+    say so once on stderr (the fp32 kernels are an order of magnitude slower than the MFMA path).  An explicit 'f64', 'f32' or
+    'bf16x3' runs as asked on every shape (the exact modes' kernels have no k bound and no accuracy envelope)."""
     if precision == 'auto':
         if float(n) * float(f) * float(k) < AUTO_F16_WORK:
             precision = 'f64'
@@ -116,6 +118,10 @@ def sparse_precision(precision):
     if precision in ('auto', 'f64'):
         return 'f64'
     if _native.PRECISIONS[precision] == _native.PREC_F32:
+        return 'f32'
+    if _native.PRECISIONS[precision] == _native.PREC_BF16X3:
+        _note_once(('csr', precision), "KLdivNMF: CSR input with precision=%r runs the reference's sparse branch on the fp32 "
+                   "sparse kernels (precision='f32'); pass a dense array for the split-operand bf16 contractions\n" % (precision,))
         return 'f32'
     _note_once(('csr', precision), "KLdivNMF: CSR input with precision=%r runs the reference's sparse branch on the fp32 "
                "sparse kernels (precision='f32'); pass a dense array for the 16-bit MFMA path\n" % (precision,))
@@ -219,7 +225,7 @@ class KLdivNMF(object):
             prec = 'f64'
         elif shape is not None:                   # decided per problem (shape = (n, f, k)): 'auto' by size, k > 512 -> fp32 kernels
             prec = resolve_precision(prec, *shape)
-        if exact and _native.PRECISIONS[prec] not in (_native.PREC_F64, _native.PREC_F32):
+        if exact and _native.PRECISIONS[prec] not in (_native.PREC_F64, _native.PREC_F32, _native.PREC_BF16X3):
             prec = 'f64'
         return _native.Context(precision=prec, device=self.device, pooled=True)
 
@@ -353,7 +359,7 @@ class KLdivNMF(object):
             # dead from every caller in the reference (nmf.py:246-250), kept
             W = _scale(normalize_sum(W, axis=1), np.asarray(X.sum(axis=1)).ravel(), axis=1)
         if (eps != 1.e-8 and not sparse and self.precision != 'auto'
-                and _native.PRECISIONS[self.precision] >= _native.PREC_BF16):
+                and _native.PRECISIONS[self.precision] == _native.PREC_BF16):
             raise ValueError("the bf16 kernels use the reference's fixed eps = 1e-8")
         H = self.components_
         with self._context(sparse=sparse) as ctx:
