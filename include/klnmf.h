@@ -329,6 +329,12 @@ int klnmf_all_distances_device(int device, int dtype, int metric, int64_t na, in
  *                            klnmf_iter_colpass and before klnmf_iter_advance; loss[0] alone may be exchanged earlier, while the
  *                            column pass computes.  The loop state behind the answer is the same on every rank. */
 #define KLNMF_Q_FP8_POLL_DUE      13
+/* The CSR kernels a problem given by klnmf_set_problem_sparse runs on (csrc/sparseb.hip.h):
+ *   KLNMF_Q_SP_COL_BLOCKS    column blocks of the fused ratio / W-rule pass;  KLNMF_Q_SP_ROW_BLOCKS  row blocks of the
+ *                            H-numerator pass.  0 (both): the unblocked kernels (k > 512, or no stored entries), or the
+ *                            problem is dense */
+#define KLNMF_Q_SP_COL_BLOCKS     14
+#define KLNMF_Q_SP_ROW_BLOCKS     15
 int klnmf_query(klnmf_ctx *ctx, int what, int64_t *value);
 /*   KLNMF_QF_SUM_V  the sum of the uploaded V as stored (16-bit modes; 0 in the exact modes), in the data's own units */
 #define KLNMF_QF_SUM_V            0

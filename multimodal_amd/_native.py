@@ -240,6 +240,7 @@ Q_W8_SATURATED, Q_W8_FALLBACKS, Q_RATIO_SATURATED, Q_RATIO_UNFIXED = 5, 6, 7, 8
 Q_NO_NUM_EPS = 9
 Q_MON_CHECKS, Q_MON_TRIPS, Q_MON_GAVE_UP = 10, 11, 12
 Q_FP8_POLL_DUE = 13
+Q_SP_COL_BLOCKS, Q_SP_ROW_BLOCKS = 14, 15
 QF_SUM_V, QF_NNZ_V, QF_MON_STAT, QF_MON_THRESHOLD = 0, 1, 2, 3
 QF_KL_OVER_SUM_V = 9
 
@@ -668,6 +669,11 @@ class Context(object):
     def fp8_poll_due(self):
         """Loops in pieces on row shards: the next `iter_advance` reads the all-reduced count in loss[1] (KLNMF_Q_FP8_POLL_DUE)."""
         return bool(self.query(Q_FP8_POLL_DUE))
+
+    def sparse_blocks(self):
+        """(column blocks, row blocks) of the CSR kernels this problem runs on; (0, 0): the unblocked kernels, or a dense
+        problem (KLNMF_Q_SP_COL_BLOCKS / KLNMF_Q_SP_ROW_BLOCKS)."""
+        return self.query(Q_SP_COL_BLOCKS), self.query(Q_SP_ROW_BLOCKS)
 
     def query_f64(self, what):
         v = _c.c_double(0.0)

@@ -189,6 +189,8 @@ int klnmf_query(klnmf_ctx *c, int what, int64_t *value) {
             case KLNMF_Q_MON_TRIPS: *value = c->stat_mon_trips; break;
             case KLNMF_Q_MON_GAVE_UP: *value = c->stat_mon_gave_up ? 1 : 0; break;
             case KLNMF_Q_FP8_POLL_DUE: *value = (c->have_problem && fp8_poll_due(c)) ? 1 : 0; break;
+            case KLNMF_Q_SP_COL_BLOCKS: *value = (c->have_problem && c->sparse && c->sp_blocked) ? c->sp_cb : 0; break;
+            case KLNMF_Q_SP_ROW_BLOCKS: *value = (c->have_problem && c->sparse && c->sp_blocked) ? c->sp_rb : 0; break;
             case KLNMF_Q_COMM_RANKS: {
                 int cnt = 1;
                 if (c->comm) RCCLCHK(rccl().CommCount(c->comm, &cnt));

@@ -17,7 +17,9 @@
 //     per row block in TRANSPOSED layout [rb][column][k] (one coalesced k-vector per wave), summed and transposed by
 //     k_spb_numer.
 // Block pointers are built on the device at upload from the sorted CSR / CSC arrays (binary search per row and block);
-// indices are kept as int32 (half the index bytes).  Results equal the unblocked kernels' to summation order (G6 / G9 at 1e-9).
+// indices are kept as int32 (half the index bytes).  Results equal the unblocked kernels' to summation order: tests/test_sparse_gpu.py
+// checks every component chunk, 1 to 7 column and row blocks (forced and by the size rule) and the unblocked kernels against
+// the fp64 reference, and a blocked run against the same problem in one block of each kind (1e-12 in fp64).
 #pragma once
 #include "sparse.hip.h"
 

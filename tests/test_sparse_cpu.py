@@ -1,0 +1,69 @@
+"""CPU side of the CSR kernel tests (tests/test_sparse_gpu.py): the regime query's constants, the chunked fp64 reference
+and the structure builder.  No GPU needed."""
+import os
+import re
+
+import numpy as np
+from numpy.testing import assert_allclose
+
+from multimodal_amd import _native
+from oracle import klnmf_oracle as orc
+from tests import sparse_cases as sc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_sparse_block_query_constants_match_the_header():
+    with open(os.path.join(ROOT, 'include', 'klnmf.h')) as fh:
+        header = fh.read()
+    defined = dict((m.group(1), int(m.group(2))) for m in re.finditer(r'#define KLNMF_(Q_SP_\w+)\s+(\d+)', header))
+    assert defined == {'Q_SP_COL_BLOCKS': _native.Q_SP_COL_BLOCKS, 'Q_SP_ROW_BLOCKS': _native.Q_SP_ROW_BLOCKS}
+    # and they extend the item list without reusing a number
+    others = [int(m.group(1)) for m in re.finditer(r'#define KLNMF_Q_(?!SP_)\w+\s+(\d+)', header)]
+    assert not set(defined.values()) & set(others)
+
+
+def test_chunked_reference_equals_the_oracle():
+    X = sc.designed_csr(141, 150, 1, 1, seed=5)
+    X.data[5] = 0.0                  # an explicit zero: dropped by both (nmf.py:66)
+    k = 7
+    W, H = sc.factors(141, 150, k, seed=6)
+    for eps in (orc.EPS_RATIO, 1e-5):
+        got = sc.ref_step(X, W, H, eps=eps, chunked=True)
+        want = sc.ref_step(X, W, H, eps=eps, chunked=False)
+        for g, w in zip(got, want):
+            assert_allclose(g, w, rtol=1e-13, atol=0)
+    # the oracle's own update and fit, with a chunk far smaller than the matrix
+    loss, q = sc.chunked_terms(X, W, H, chunk=50)
+    assert_allclose(loss, orc.sparse_kl_error(X, W, H), rtol=1e-13)
+    assert_allclose(q, orc.sparse_ratio_q(X, W, H)[3], rtol=1e-13)
+    Wn, Hn = orc.sparse_update_step(X, W, H)
+    _, _, Wc, Hc = sc.ref_step(X, W, H, chunked=True)
+    assert_allclose(Wc, Wn, rtol=1e-13, atol=0)
+    assert_allclose(Hc, Hn, rtol=1e-13, atol=0)
+    for fit in (True, False):
+        Wo, Ho, eo = orc.sparse_fit_transform(X, k, H, max_iter=6, tol=0, fit=fit, components=H)
+        Wc, Hc, ec = sc.ref_fit(X, H, 6, fit=fit, components=H, chunked=True)
+        assert len(ec) == len(eo) == 6
+        assert_allclose(ec, eo, rtol=1e-13)
+        assert_allclose(Wc, Wo, rtol=1e-13, atol=0)
+        assert_allclose(Hc, Ho, rtol=1e-13, atol=0)
+
+
+def test_structure_builder_produces_the_cells_it_promises():
+    for (n, f, cb, rb) in [(301, 263, 1, 1), (1001, 1000, 2, 3), (1001, 1000, 7, 7), (1001, 1000, 3, 2)]:
+        X = sc.designed_csr(n, f, cb, rb, seed=1)
+        assert X.has_sorted_indices and X.nnz == X.count_nonzero() and np.all(X.data > 0)
+        rows, cols = sc.cell_counts(X, cb, rb)
+        assert set(sc.ROW_CELLS) <= rows, sorted(set(sc.ROW_CELLS) - rows)
+        assert set(sc.COL_CELLS) <= cols, sorted(set(sc.COL_CELLS) - cols)
+        lengths = sc.row_lengths(X)
+        assert (lengths == 0).any() and (lengths == 1).any()
+    # the counts themselves, on a matrix small enough to count by hand
+    import scipy.sparse as sp
+    X = sp.csr_matrix(([1., 1., 1., 1.], ([0, 0, 2, 2], [0, 3, 1, 2])), shape=(3, 4))
+    rows, cols = sc.cell_counts(X, 2, 2)          # column blocks {0, 1} {2, 3}; row blocks {0, 1} {2}
+    assert rows == {0, 1}
+    assert cols == {0, 1}
+    rows, cols = sc.cell_counts(X, 1, 1)
+    assert rows == {0, 2} and cols == {1}
