@@ -51,6 +51,11 @@ extern "C" {
                                       * cores: each fp32 operand x split into hi = bf16(x) and lo = bf16(x - hi), products
                                       * hi.hi + hi.lo + lo.hi accumulated in fp32 -- each product within ~2^-16 of a.b
                                       * (relative), no scaling (bf16 has fp32's exponent range; operands below 3.39e38) */
+#define KLNMF_PREC_F16X3    5        /* fp32 storage (V, Q, W, H), loss partials in fp64, any eps, with every operand of the three
+                                      * dense contractions split into two fp16 parts under a power-of-two scale: hi = f16(x s),
+                                      * lo = f16(x s - hi), products hi.hi + hi.lo + lo.hi accumulated in fp32.  k <= 256: the
+                                      * loop's row pass (loss + ratio + W rule) and column pass are fused split-fp16 kernels;
+                                      * k > 256, the single steps and CSR input: the KLNMF_PREC_BF16X3 / fp32 kernels */
 
 /* host element types for uploads / downloads */
 #define KLNMF_DT_F32        0

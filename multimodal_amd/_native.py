@@ -15,13 +15,17 @@ LIB_PATH = os.environ.get('KLNMF_LIB') or os.path.join(_HERE, 'csrc', 'libklnmf.
 PREC_F64, PREC_F32, PREC_BF16 = 0, 1, 2
 # fp32 storage and loop, the dense contractions as hi.hi + hi.lo + lo.hi of bf16 operand parts (csrc/split3.hip.h)
 PREC_BF16X3 = 4
+# fp32 storage, the dense contractions as hi.hi + hi.lo + lo.hi of power-of-two-scaled fp16 operand parts; k <= 256: the loop's
+# row and column passes are fused split-fp16 kernels (csrc/f16x3.hip.h), k > 256: bf16x3's kernels
+PREC_F16X3 = 5
 PRECISIONS = {'f64': PREC_F64, 'fp64': PREC_F64, 'float64': PREC_F64,
               'f32': PREC_F32, 'fp32': PREC_F32, 'float32': PREC_F32,
               'f16': PREC_BF16, 'fp16': PREC_BF16, 'float16': PREC_BF16,
               # the 16-bit mode's historical name (its MFMA operands were bf16 in round 1; fp16 with power-of-two
               # scaling since: same matrix rate, 8x smaller operand rounding -- csrc/mfma.hip.h)
               'bf16': PREC_BF16,
-              'bf16x3': PREC_BF16X3}
+              'bf16x3': PREC_BF16X3,
+              'f16x3': PREC_F16X3}
 DT_F32, DT_F64 = 0, 1
 STREAM_DEFAULT = (1 << 64) - 1        # KLNMF_STREAM_DEFAULT: (void *)(intptr_t)-1
 
@@ -270,7 +274,8 @@ class Context(object):
             precision = PRECISIONS[precision]
         self.precision = precision
         # the mode's canonical name (what device_data picks the fp32 / fp64 source copies by)
-        self.precision_name = {PREC_F64: 'f64', PREC_F32: 'f32', PREC_BF16: 'f16', PREC_BF16X3: 'bf16x3'}[precision]
+        self.precision_name = {PREC_F64: 'f64', PREC_F32: 'f32', PREC_BF16: 'f16', PREC_BF16X3: 'bf16x3',
+                               PREC_F16X3: 'f16x3'}[precision]
         self.n = self.f = self.k = 0
         self.cap = 0
         self._pool_key = (precision, int(device)) if (pooled and stream is None and os.environ.get('KLNMF_NO_POOL') != '1') else None
@@ -315,7 +320,7 @@ class Context(object):
 
     @property
     def exact(self):
-        return self.precision in (PREC_F64, PREC_F32, PREC_BF16X3)
+        return self.precision in (PREC_F64, PREC_F32, PREC_BF16X3, PREC_F16X3)
 
     # -- data in --
     def set_problem(self, n, f, k, max_iter_capacity):

@@ -62,6 +62,7 @@ void place_block(klnmf_ctx *c, const S *dsrc, int64_t rows, int64_t cols, int64_
             break;
         case KLNMF_PREC_F32:
         case KLNMF_PREC_BF16X3:
+        case KLNMF_PREC_F16X3:
             hipLaunchKernelGGL((k_place_V<float, S>), dim3(grid), dim3(256), 0, c->stream,
                                (float *)c->V, c->f, dsrc, rows, cols, ld, row0, col0, scale, row_idx);
             break;
@@ -231,7 +232,8 @@ extern "C" {
 int klnmf_create(klnmf_ctx **out, int device, int precision, void *stream) {
     return guarded([&] {
         if (!out) fail(KLNMF_ERR_ARG, "null out pointer");
-        if (precision != KLNMF_PREC_F64 && precision != KLNMF_PREC_F32 && precision != KLNMF_PREC_F16 && precision != KLNMF_PREC_BF16X3)
+        if (precision != KLNMF_PREC_F64 && precision != KLNMF_PREC_F32 && precision != KLNMF_PREC_F16 && precision != KLNMF_PREC_BF16X3 &&
+            precision != KLNMF_PREC_F16X3)
             fail(KLNMF_ERR_ARG, "unknown precision mode");
         int ndev = 0;
         HIPCHK(hipGetDeviceCount(&ndev));
@@ -284,7 +286,7 @@ int klnmf_set_problem(klnmf_ctx *c, int64_t n, int64_t f, int64_t k, int64_t cap
         if (n > (1LL << 30) || f > (1LL << 30) || k > (1LL << 20))
             fail(KLNMF_ERR_UNSUPP, "dimension too large");
         if (c->is_exact() && n > (int64_t)65535 * GT)
-            fail(KLNMF_ERR_UNSUPP, "KLNMF_PREC_F64 / F32 / BF16X3: more than 65535 x 64 rows per context (row tiles ride on gridDim.y); "
+            fail(KLNMF_ERR_UNSUPP, "KLNMF_PREC_F64 / F32 / BF16X3 / F16X3: more than 65535 x 64 rows per context (row tiles ride on gridDim.y); "
                                    "shard the rows or use the 16-bit mode");
         HIPCHK(hipStreamSynchronize(c->stream));
         c->free_all();
@@ -357,11 +359,19 @@ int klnmf_set_problem(klnmf_ctx *c, int64_t n, int64_t f, int64_t k, int64_t cap
             }
             c->loss_part_count = ((f + GT - 1) / GT) * ((n + GT - 1) / GT);
             c->loss_part = (double *)c->dalloc(sizeof(double) * c->loss_part_count);
+            c->x3_ready = false;
+            c->x3_hs = c->x3_qr = nullptr; c->x3_xmax = nullptr; c->x3_loss = nullptr;
+            if (c->x3_fused()) {
+                c->x3_hs = (float *)c->dalloc(sizeof(float) * F3_KMAX);
+                c->x3_xmax = (unsigned *)c->dalloc(sizeof(unsigned) * F3_KMAX);
+                c->x3_qr = (float *)c->dalloc(sizeof(float) * n);
+                c->x3_loss = (double *)c->dalloc(sizeof(double) * ((n + F3_TR - 1) / F3_TR));
+            }
         } else {
             c->KT = (int)((k + 31) / 32);
             c->ks = (int)((k + 15) / 16);
             c->big = false;
-            if (k > 512) fail(KLNMF_ERR_UNSUPP, "k > 512 runs in KLNMF_PREC_F32 / F64 / BF16X3 (the 16-bit MFMA kernels cover k <= 512)");
+            if (k > 512) fail(KLNMF_ERR_UNSUPP, "k > 512 runs in KLNMF_PREC_F32 / F64 / BF16X3 / F16X3 (the 16-bit MFMA kernels cover k <= 512)");
             if (c->KT >= 8) {
                 // 224 < k <= 512: 4-wave workgroups of the row pass (whole register file per wave, FUSED order) and the
                 // component-split column passes; component tiles in pairs, the W.H contraction over all of them
@@ -545,7 +555,7 @@ int klnmf_release_problem(klnmf_ctx *c) {
 int klnmf_set_problem_sparse(klnmf_ctx *c, int64_t n, int64_t f, int64_t k, int64_t cap, int64_t nnz) {
     return guarded([&] {
         use(c);
-        if (!c->is_exact()) fail(KLNMF_ERR_UNSUPP, "CSR input runs in the exact modes (KLNMF_PREC_F64 / F32 / BF16X3); densify for the bf16 kernels");
+        if (!c->is_exact()) fail(KLNMF_ERR_UNSUPP, "CSR input runs in the exact modes (KLNMF_PREC_F64 / F32 / BF16X3 / F16X3); densify for the bf16 kernels");
         if (n <= 0 || f <= 0 || k <= 0 || cap < 0 || nnz < 0) fail(KLNMF_ERR_ARG, "n, f, k must be positive, nnz >= 0");
         if (n > (1LL << 30) || f > (1LL << 30) || k > (1LL << 20)) fail(KLNMF_ERR_UNSUPP, "dimension too large");
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -799,7 +809,7 @@ int klnmf_set_H_device(klnmf_ctx *c, const void *dsrc, int dtype, int64_t ld, in
         if (c->prec == KLNMF_PREC_F64) {
             if (f64) copy_2d(c, (double *)c->H + col0, c->f, (const double *)dsrc, ld, c->k, ncols);
             else copy_2d(c, (double *)c->H + col0, c->f, (const float *)dsrc, ld, c->k, ncols);
-        } else if (c->prec == KLNMF_PREC_F32 || c->prec == KLNMF_PREC_BF16X3) {
+        } else if (c->is_f32()) {
             if (f64) copy_2d(c, (float *)c->H + col0, c->f, (const double *)dsrc, ld, c->k, ncols);
             else copy_2d(c, (float *)c->H + col0, c->f, (const float *)dsrc, ld, c->k, ncols);
         } else {
@@ -826,7 +836,7 @@ int klnmf_get_W_device(klnmf_ctx *c, void *ddst, int dtype, int64_t ld) {
         if (c->prec == KLNMF_PREC_F64) {
             if (f64) copy_2d(c, (double *)ddst, ld, (const double *)c->W[c->cur], c->k, c->n, c->k);
             else copy_2d(c, (float *)ddst, ld, (const double *)c->W[c->cur], c->k, c->n, c->k);
-        } else if (c->prec == KLNMF_PREC_F32 || c->prec == KLNMF_PREC_BF16X3) {
+        } else if (c->is_f32()) {
             if (f64) copy_2d(c, (double *)ddst, ld, (const float *)c->W[c->cur], c->k, c->n, c->k);
             else copy_2d(c, (float *)ddst, ld, (const float *)c->W[c->cur], c->k, c->n, c->k);
         } else {

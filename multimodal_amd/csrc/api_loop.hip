@@ -255,11 +255,13 @@ void sparse_Q(klnmf_ctx *c, int write_q, double eps, const DecideArgs &dec) {
 }
 
 // k_gemm: 64 x 64 tiles, the inner product on the fp64 / fp32 MFMA (exact.hip.h); KLNMF_PREC_BF16X3 (fp32 storage): the same
-// launch on the split-operand bf16 MFMA (split3.hip.h, same arguments and epilogues)
+// launch on the split-operand bf16 MFMA (split3.hip.h, same arguments and epilogues).  KLNMF_PREC_F16X3 with k > 256 runs
+// bf16x3's kernels throughout; with k <= 256 what its fused loop kernels do not cover (single steps, W0, the loss alone) runs
+// on the fp32 kernel, which keeps a step within 2^-18 of sum |a.b| (f16x3.hip.h)
 #define KL_GEMM_TT(tt, T, EPI, grid, stream, ...)                                                                     \
     do {                                                                                                            \
         if constexpr (std::is_same<T, float>::value) {                                                              \
-            if (c->prec == KLNMF_PREC_BF16X3) {                                                                     \
+            if (c->prec == KLNMF_PREC_BF16X3 || (c->prec == KLNMF_PREC_F16X3 && c->k > F3_KMAX)) {                  \
                 hipLaunchKernelGGL((k_gemm_x3<EPI>), grid, dim3(256), 0, stream, __VA_ARGS__);                      \
                 break;                                                                                              \
             }                                                                                                       \
@@ -271,6 +273,7 @@ void sparse_Q(klnmf_ctx *c, int write_q, double eps, const DecideArgs &dec) {
 template <typename T>
 void exact_Q(klnmf_ctx *c, int write_q, double eps = kEpsRatio, DecideArgs dec = DecideArgs{0, nullptr, 0.0, nullptr, 0}) {
     if (c->sparse) { sparse_Q<T>(c, write_q, eps, dec); return; }
+    if (write_q) c->x3_ready = false;
     EpiQ<T> epi{(const T *)c->V, (T *)c->Q, c->f, c->loss_part, write_q, 0.0, (T)eps};
     const int TL = 16 * c->q_tt;
     dim3 grid((unsigned)((c->f + TL - 1) / TL), (unsigned)((c->n + TL - 1) / TL), 1);
@@ -286,6 +289,41 @@ void exact_Q(klnmf_ctx *c, int write_q, double eps = kEpsRatio, DecideArgs dec =
                        (const double *)c->loss_part, (int64_t)grid.x * grid.y, c->loss_xchg,
                        (const DevState *)c->st, dec);
     HIPCHK(hipGetLastError());
+}
+
+// KLNMF_PREC_F16X3, k <= 256, dense: the H scales, then loss + ratio + W rule in one pass over V (f16x3.hip.h); store_q (a fit):
+// the ratios, their row scales and the component maxima are kept for x3_colpass
+void x3_rowpass(klnmf_ctx *c, int store_q, double eps, const DecideArgs &dec) {
+    hipLaunchKernelGGL(k_x3_hscale, dim3((unsigned)F3_KMAX), dim3(256), 0, c->stream, (const float *)c->H, c->f, (int)c->k,
+                       c->x3_hs, c->x3_xmax, (const DevState *)c->st);
+    HIPCHK(hipGetLastError());
+    const unsigned blocks = (unsigned)((c->n + F3_TR - 1) / F3_TR);
+    EventPair ev{};
+    if (c->prof_now) ev = begin_event(c, c->ev_row);
+#define KL_RP_X3(NBV)                                                                                                              \
+    hipLaunchKernelGGL((k_rowpass_x3<NBV>), dim3(blocks), dim3(256), 0, c->stream, c->n, c->f, (int)c->k, (const float *)c->V,    \
+                       (const float *)c->W[c->cur], (float *)c->W[c->cur ^ 1], (const float *)c->H, (const float *)c->x3_hs,      \
+                       store_q ? (float *)c->Q : (float *)nullptr, store_q ? c->x3_qr : (float *)nullptr,                          \
+                       store_q ? c->x3_xmax : (unsigned *)nullptr, c->x3_loss, (float)eps, (const DevState *)c->st)
+    const int nb = (int)((c->k + 63) / 64);
+    if (nb <= 1) KL_RP_X3(1); else if (nb == 2) KL_RP_X3(2); else if (nb == 3) KL_RP_X3(3); else KL_RP_X3(4);
+#undef KL_RP_X3
+    HIPCHK(hipGetLastError());
+    if (c->prof_now) HIPCHK(hipEventRecord(ev.b, c->stream));
+    hipLaunchKernelGGL(k_sum_doubles, dim3(1), dim3(1024), 0, c->stream, (const double *)c->x3_loss, (int64_t)blocks, c->loss_xchg,
+                       (const DevState *)c->st, dec);
+    HIPCHK(hipGetLastError());
+    c->x3_ready = store_q != 0;
+}
+
+// the H numerator's slabs of the fused loop: W_new^T . Q per row chunk on split fp16 operands (Npart, EpiN's layout)
+void x3_colpass(klnmf_ctx *c) {
+    dim3 grid((unsigned)((c->f + 63) / 64), (unsigned)((c->k + 63) / 64), (unsigned)c->nsplit);
+    hipLaunchKernelGGL(k_colpass_x3, grid, dim3(256), 0, c->stream, c->n, c->f, (int)c->k, (const float *)c->W[c->cur ^ 1],
+                       (const float *)c->Q, (const float *)c->x3_qr, (const unsigned *)c->x3_xmax, (float *)c->Npart, c->kchunk,
+                       (const DevState *)c->st);
+    HIPCHK(hipGetLastError());
+    c->x3_ready = false;
 }
 
 // W_new = W * (Qsrc . H^T)   (multiply=0: W_new = Qsrc . H^T, i.e. W0 with Qsrc = V)
@@ -374,7 +412,8 @@ void exact_N(klnmf_ctx *c, int widx, bool sum_slabs = true) {
     dim3 grid((unsigned)((c->f + TLn - 1) / TLn), (unsigned)((c->k + TLn - 1) / TLn), (unsigned)c->nsplit);
     EventPair ev{};
     if (c->prof_now) ev = begin_event(c, c->ev_col);
-    KL_GEMM_TT(c->n_tt, T, EpiN<T>, grid, c->stream, (int)c->k, (int)c->f,
+    if (c->x3_fused() && c->x3_ready && widx == (c->cur ^ 1)) x3_colpass(c);
+    else KL_GEMM_TT(c->n_tt, T, EpiN<T>, grid, c->stream, (int)c->k, (int)c->f,
                (int)c->n, (const T *)c->W[widx], (int64_t)1, (int64_t)c->k,
                (const T *)c->Q, (int64_t)c->f, (int64_t)1, c->kchunk,
                (const DevState *)c->st, epi);
@@ -657,6 +696,10 @@ void piece_rowpass(klnmf_ctx *c, int fit, const double *fused_tol, bool defer_to
         // fused_tol (single-context loops): the stop rule in the loss reduction's launch, no k_decide
         DecideArgs dec{0, nullptr, 0.0, nullptr, 0};
         if (fused_tol) dec = DecideArgs{1, c->st, *fused_tol, c->errors, c->cap};
+        if (c->x3_fused()) {
+            x3_rowpass(c, fit, kEpsRatio, dec);
+            return;
+        }
         EXACT_CALL(c, exact_Q, 1, kEpsRatio, dec);
         EXACT_CALL(c, exact_W, c->sparse ? c->sp_q : c->Q, 1);
         return;
@@ -1178,7 +1221,7 @@ int klnmf_step_Q(klnmf_ctx *c) {
 int klnmf_step_W(klnmf_ctx *c) {
     return guarded([&] {
         need_problem(c);
-        if (!c->is_exact()) fail(KLNMF_ERR_UNSUPP, "step API needs KLNMF_PREC_F64/F32/BF16X3");
+        if (!c->is_exact()) fail(KLNMF_ERR_UNSUPP, "step API needs KLNMF_PREC_F64/F32/BF16X3/F16X3");
         reset_state(c);
         EXACT_CALL(c, exact_W, c->sparse ? c->sp_q : c->Q, 1);
         c->cur ^= 1;
@@ -1189,7 +1232,7 @@ int klnmf_step_W(klnmf_ctx *c) {
 int klnmf_step_H(klnmf_ctx *c) {
     return guarded([&] {
         need_problem(c);
-        if (!c->is_exact()) fail(KLNMF_ERR_UNSUPP, "step API needs KLNMF_PREC_F64/F32/BF16X3");
+        if (!c->is_exact()) fail(KLNMF_ERR_UNSUPP, "step API needs KLNMF_PREC_F64/F32/BF16X3/F16X3");
         reset_state(c);
         EXACT_CALL(c, exact_N, c->cur);
         EXACT_CALL(c, exact_H);

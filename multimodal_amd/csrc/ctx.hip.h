@@ -27,6 +27,7 @@
 #include "common.hip.h"
 #include "exact.hip.h"
 #include "split3.hip.h"
+#include "f16x3.hip.h"
 #include "sparseb.hip.h"
 #include "mfma.hip.h"
 #include "mfma4.hip.h"
@@ -380,8 +381,20 @@ struct klnmf_ctx {
     double *comm_scratch = nullptr;       // 8 doubles on the device, owned by the communicator (not by a problem)
 
     // the exact modes' storage, loop and kernels; KLNMF_PREC_BF16X3 is the fp32 side of them with the dense contractions on
-    // the split-operand bf16 kernel (split3.hip.h)
-    bool is_exact() const { return prec == KLNMF_PREC_F64 || prec == KLNMF_PREC_F32 || prec == KLNMF_PREC_BF16X3; }
+    // the split-operand bf16 kernel (split3.hip.h); KLNMF_PREC_F16X3 the same storage and step kernels, its fit and transform
+    // loop on the fused split-fp16 kernels where x3_fused() (f16x3.hip.h)
+    bool is_exact() const {
+        return prec == KLNMF_PREC_F64 || prec == KLNMF_PREC_F32 || prec == KLNMF_PREC_BF16X3 || prec == KLNMF_PREC_F16X3;
+    }
+    // fp32 storage (the exact modes other than f64)
+    bool is_f32() const { return prec == KLNMF_PREC_F32 || prec == KLNMF_PREC_BF16X3 || prec == KLNMF_PREC_F16X3; }
+    // KLNMF_PREC_F16X3 on dense input with k <= 256: the loop's row pass is k_rowpass_x3 and its column pass k_colpass_x3
+    // (k > 256 and CSR input: the bf16x3 kernels / the fp32 sparse kernels)
+    bool x3_fused() const { return prec == KLNMF_PREC_F16X3 && !sparse && k <= F3_KMAX; }
+    float *x3_hs = nullptr, *x3_qr = nullptr;     // per-component H scales; per-row ratio scales of the column pass
+    unsigned *x3_xmax = nullptr;                  // per-component maxima of W_new qr (bit patterns of non-negative floats)
+    double *x3_loss = nullptr;                    // one loss partial per 64 rows
+    bool x3_ready = false;                        // Q, x3_qr and x3_xmax are the last fused row pass's (its column pass may run)
     // fp8 ratio tiles from how many rows per context?  Their e4m3 rounding only enters the H numerator, a sum over all rows
     // (relative error ~ 0.036 sqrt(2 / n)); measured against the fp64 oracle (scripts/fp8_rows_survey.py,
     // profiles/r03_fp8_rows_survey.txt): final-KL deviation 1.7e-5 .. 3.5e-5 from 4096 to 50 000 rows at k = 50, 6.7e-6 .. 1.5e-5

@@ -51,7 +51,7 @@ class ShardedKLNMF(object):
     Parameters
     ----------
     n_total, f, k : global problem shape (this rank holds `n_local` rows).
-    precision     : 'f16' (= 'bf16') | 'bf16x3' | 'f32' | 'f64'  ('bf16x3': the f32 mode's loop and exchange, its
+    precision     : 'f16' (= 'bf16') | 'bf16x3' | 'f16x3' | 'f32' | 'f64'  ('bf16x3' / 'f16x3': the f32 mode's loop and exchange, its
                     contractions on split bf16 operands -- _native.PRECISIONS)
     group         : torch.distributed process group or None (single process).
     backend       : context object; default = a HIP `_native.Context` on the

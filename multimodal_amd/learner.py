@@ -8,7 +8,7 @@ unchanged.  What differs is where the work happens: the per-modality blocks and
 their balancing coefficients go straight to the NMF upload, where scale, cast
 and column placement are one kernel per block, instead of first materialising
 `safe_hstack([c * m ...])` on the host (reference learner.py:53-56).
-The arithmetic is KLdivNMF's: KLNMF_PRECISION = f64 (default) | f32 | bf16x3 | f16 | auto (lib/nmf.py).
+The arithmetic is KLdivNMF's: KLNMF_PRECISION = f64 (default) | f32 | bf16x3 | f16x3 | f16 | auto (lib/nmf.py).
 """
 from .lib.nmf import KLdivNMF as NMF
 from .lib.nmf import check_non_negative

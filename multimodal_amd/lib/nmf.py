@@ -24,7 +24,8 @@ appended (q5, nmf.py:214-220).
 Extra (non-reference) constructor arguments: `precision` ('f64' default =
 the reference's float64 arithmetic; 'f32'; 'bf16x3' = the f32 mode with its contractions on the bf16 matrix cores, every
 fp32 operand split into two bf16 parts (hi.hi + hi.lo + lo.hi, fp32 accumulation: each product within ~2^-16 of a.b; any
-shape, any k, any eps); 'f16' (= 'bf16') = MFMA fast path with V stored as power-of-two-scaled fp16; 'auto'), `device`.  Environment: KLNMF_PRECISION, KLNMF_DEVICE.
+shape, any k, any eps); 'f16x3' = the same with fp16 operand parts under power-of-two scales and, for k <= 256, the
+loop's passes fused (k > 256: 'bf16x3'); 'f16' (= 'bf16') = MFMA fast path with V stored as power-of-two-scaled fp16; 'auto'), `device`.  Environment: KLNMF_PRECISION, KLNMF_DEVICE.
 """
 import os
 import sys
@@ -61,6 +62,7 @@ AUTO_F16_MIN_K = 16
 # KLNMF_QF_KL_OVER_SUM_V); `KLdivNMF.last_fp8_report['outside_f16_envelope']` and one stderr line say when a fit ended below it.
 F16_MIN_KL_OVER_SUM_V = 3e-3
 
+MAX_K_F16X3 = 256         # the fused split-fp16 loop of 'f16x3' holds a workgroup's Q.H^T of all components in registers
 MAX_K_MFMA = 512          # the 16-bit MFMA kernels hold a wave's accumulators of all components in registers: k <= 512
 MAX_ROWS_EXACT = 65535 * 64   # the exact modes' row tiles ride on gridDim.y (csrc/api_context.hip: KLNMF_ERR_UNSUPP beyond)
 
@@ -78,7 +80,8 @@ def resolve_precision(precision, n, f, k):
     """The arithmetic one problem runs in.  'auto' by size (above); the 16-bit modes hand k > 512 to the fp32 kernels of the
     same library (LDS-tiled VALU GEMMs: any k, at least the 16-bit mode's accuracy) instead of refusing the problem -- and
     say so once on stderr (the fp32 kernels are an order of magnitude slower than the MFMA path).  An explicit 'f64', 'f32' or
-    'bf16x3' runs as asked on every shape (the exact modes' kernels have no k bound and no accuracy envelope)."""
+    'bf16x3' runs as asked on every shape (the exact modes' kernels have no k bound and no accuracy envelope).  'f16x3' is
+    explicit only ('auto' never picks it); k > 256 runs on bf16x3's kernels, said once on stderr."""
     if precision == 'auto':
         if float(n) * float(f) * float(k) < AUTO_F16_WORK:
             precision = 'f64'
@@ -103,6 +106,10 @@ def resolve_precision(precision, n, f, k):
                    "the final KL within 1e-4 of the reference's; measured up to 5e-4 below) -- precision='auto' or 'f32' keeps 1e-6\n"
                    % (precision, f, k, AUTO_F16_MIN_F, AUTO_F16_MIN_K))
     code = _native.PRECISIONS[precision]
+    if code == _native.PREC_F16X3 and k > MAX_K_F16X3:
+        _note_once(('k', precision), "KLdivNMF: precision=%r fuses k <= %d; k = %d runs on the split bf16 kernels (precision='bf16x3')\n"
+                   % (precision, MAX_K_F16X3, k))
+        return 'bf16x3'
     if code == _native.PREC_BF16 and k > MAX_K_MFMA:
         _note_once(('k', precision), "KLdivNMF: precision=%r holds k <= %d; k = %d runs on the fp32 kernels (precision='f32')\n"
                    % (precision, MAX_K_MFMA, k))
@@ -119,9 +126,9 @@ def sparse_precision(precision):
         return 'f64'
     if _native.PRECISIONS[precision] == _native.PREC_F32:
         return 'f32'
-    if _native.PRECISIONS[precision] == _native.PREC_BF16X3:
+    if _native.PRECISIONS[precision] in (_native.PREC_BF16X3, _native.PREC_F16X3):
         _note_once(('csr', precision), "KLdivNMF: CSR input with precision=%r runs the reference's sparse branch on the fp32 "
-                   "sparse kernels (precision='f32'); pass a dense array for the split-operand bf16 contractions\n" % (precision,))
+                   "sparse kernels (precision='f32'); pass a dense array for the split-operand contractions\n" % (precision,))
         return 'f32'
     _note_once(('csr', precision), "KLdivNMF: CSR input with precision=%r runs the reference's sparse branch on the fp32 "
                "sparse kernels (precision='f32'); pass a dense array for the 16-bit MFMA path\n" % (precision,))
@@ -225,7 +232,7 @@ class KLdivNMF(object):
             prec = 'f64'
         elif shape is not None:                   # decided per problem (shape = (n, f, k)): 'auto' by size, k > 512 -> fp32 kernels
             prec = resolve_precision(prec, *shape)
-        if exact and _native.PRECISIONS[prec] not in (_native.PREC_F64, _native.PREC_F32, _native.PREC_BF16X3):
+        if exact and _native.PRECISIONS[prec] not in (_native.PREC_F64, _native.PREC_F32, _native.PREC_BF16X3, _native.PREC_F16X3):
             prec = 'f64'
         return _native.Context(precision=prec, device=self.device, pooled=True)
 
