@@ -13,6 +13,11 @@ timed region.  Protocol: `--repeats` (5) independent fits from th
 warm-up iterations, then EXACTLY K iterations timed between barrier + synchronize fences, the maximum over ranks
 taken per segment; `value` = K / median segment time.  Rank 0 prints one JSON line.
 
+A plain run does only what that line's headline needs: set-up, the segments, `--dump-outputs`, the line.  `--full` adds what
+takes time of its own: the fp64 CPU baseline and the HIP path's parity on its row sample (one process), the extra all-16-bit
+segment (`value_16bit`) and the power / clock sampler (`power_clock`); `--no-cpu-baseline` and `--no-16bit-segment` leave a
+piece out of it.  The roofline and per-kernel figures come from the timed segments' own events and are in every line.
+
 Data: the seeded block-wise synthetic V of SURVEY.md 8d (multimodal_amd/synthetic.py: per-row-block RandomState
 streams), the same bytes the CPU baseline sees.  Strong scaling: the problem (n rows) is fixed, rank r holds n/N rows.
 
@@ -187,7 +192,10 @@ def parse_args(argv=None):
     p.add_argument('--k', '--components', dest='k', type=int, default=200)
     p.add_argument('--precision', default='f16', choices=['f16', 'bf16', 'f32', 'f64'],
                    help="f16: fp16 MFMA operands (scaled images), fp32 accumulate; 'bf16' is the round-1 name of the same mode")
-    p.add_argument('--no-cpu-baseline', action='store_true')
+    p.add_argument('--full', action='store_true',
+                   help='also measure what the headline does not need: CPU baseline + parity on its sample, value_16bit, '
+                        'power_clock')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline and its parity leg')
     p.add_argument('--cpu-rows', type=int, default=100000,
                    help='rows of the same V the CPU baseline is timed on (SURVEY 8d: n = 100 000 at the same f, k, scaled '
                         'linearly in n); more than 65 536, so the parity leg on the same sample runs fp8 ratio tiles and the '
@@ -196,7 +204,7 @@ def parse_args(argv=None):
                    help='timed CPU iterations after one warm-up (about 25 s of fp64 work at the default sample); the parity leg '
                         'runs the same 1 + N iterations on the GPU (6 by default: 4 of them on fp8 ratio tiles)')
     p.add_argument('--no-16bit-segment', action='store_true',
-                   help='skip the extra segment that measures value_16bit (16-bit ratio tiles, f16 column pass)')
+                   help='--full without the extra segment that measures value_16bit (16-bit ratio tiles, f16 column pass)')
     p.add_argument('--segment-timeout', type=float, default=float(os.environ.get('KLNMF_BENCH_SEGMENT_TIMEOUT', '300')),
                    help='watchdog: seconds one warm-up + timed segment may take before the rank exits with status 3')
     p.add_argument('--seed', type=int, default=1234)
@@ -609,7 +617,7 @@ def run_transform(args, torch, dist, model, H0, world, rank, n_local, r0, r1, fe
     }
     if dumped is not None:
         out['dump_outputs'] = dumped
-    if n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and n_gpus == 1 and not args.no_cpu_baseline:
         out.update(transform_cpu_baseline_and_parity(args, H, fs))
     if tmodel is not model:
         tmodel.close()
@@ -665,7 +673,8 @@ def main():
     real_stdout = os.dup(1)
     os.dup2(2, 1)
     # (the power / clock helper is a child process: it must exist before anything here initialises the GPU)
-    sampler0 = PowerClockSampler(int(os.environ.get('LOCAL_RANK', '0'))) if int(os.environ.get('RANK', '0')) == 0 else None
+    sampler0 = (PowerClockSampler(int(os.environ.get('LOCAL_RANK', '0')))
+                if args.full and int(os.environ.get('RANK', '0')) == 0 else None)
     import torch
     import torch.distributed as dist
     from multimodal_amd.distributed import ShardedKLNMF, row_partition
@@ -802,7 +811,7 @@ def main():
     # entry): the number the north star's "bf16/16-bit MFMA contractions" wording describes, beside the headline one.
     value_16bit = None
     fast16 = args.precision in ('f16', 'bf16')
-    if fast16 and not args.no_16bit_segment and fp8 is not None and fp8['tile_iterations'] > 0:
+    if args.full and fast16 and not args.no_16bit_segment and fp8 is not None and fp8['tile_iterations'] > 0:
         saved = os.environ.get('KLNMF_QTILE')
         os.environ['KLNMF_QTILE'] = '16'
         try:
@@ -1021,7 +1030,7 @@ def main():
         }
         if dumped is not None:
             out['dump_outputs'] = dumped
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             base, sample = cpu_baseline(args)
             out['cpu_baseline'] = base
             try:

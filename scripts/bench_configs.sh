@@ -6,7 +6,7 @@ TAG=${1:-configs}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
-run() { name=$1; shift; python3 $R/bench.py --no-cpu-baseline --data device --repeats 3 "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name rc=$?"; python3 - $OUT/$name.json <<'PY'
+run() { name=$1; shift; python3 $R/bench.py --full --no-cpu-baseline --data device --repeats 3 "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name rc=$?"; python3 - $OUT/$name.json <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -17,7 +17,7 @@ cd $R
 case $PART in
 1)
   timeout -k 10 900 python3 -m pytest tests -m gpu -q -p no:cacheprovider > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -2 $O/pytest.log
-  timeout -k 10 400 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+  timeout -k 10 400 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
   scripts/bench_configs.sh $TAG/configs > $O/configs.txt 2>&1; cat $O/configs.txt
   ;;
 2)
@@ -32,7 +32,7 @@ case $PART in
   for f in $(find $O -name "*kernel_stats.csv"); do echo $f; grep klnmf $f | cut -c1-160 | head -8; done
   ;;
 3)
-  timeout -k 10 300 python3 bench.py --workload transform > $O/bench_transform.json 2> $O/bench_transform.err; echo "transform rc=$?"
+  timeout -k 10 300 python3 bench.py --workload transform --full > $O/bench_transform.json 2> $O/bench_transform.err; echo "transform rc=$?"
   timeout -k 10 300 python3 bench.py --workload transform --n 90000 --f 6144 --k 200 --slice 4096 --steps 40 --warmup 3 --no-cpu-baseline > $O/bench_transform_sliced_c3.json 2> $O/bench_transform_sliced_c3.err; echo "sliced rc=$?"
   bash scripts/pmc_traffic.sh $TAG/pmc_transform python3 $R/bench.py --workload transform --train-iters 0 --steps 3 --warmup 1 --repeats 1 --data device --no-cpu-baseline > $O/pmc_transform.txt 2>&1
   cd $R
@@ -63,8 +63,8 @@ import json,sys; d=json.loads(open('$O/ab_mon.json').read().strip().splitlines()
   cut -c1-200 $O/calibration.txt | tail -80; cut -c1-200 $O/calibration_150_iterations.txt
   ;;
 5)
-  timeout -k 10 400 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
-  timeout -k 10 300 python3 bench.py --workload transform > $O/bench_transform.json 2> $O/bench_transform.err; echo "transform rc=$?"
+  timeout -k 10 400 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+  timeout -k 10 300 python3 bench.py --workload transform --full > $O/bench_transform.json 2> $O/bench_transform.err; echo "transform rc=$?"
   timeout -k 10 300 python3 scripts/bench_sparse.py --precision f64 > $O/sparse_f64.json 2> $O/sparse_f64.err; echo "sparse f64 rc=$?"
   ;;
 esac

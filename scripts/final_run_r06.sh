@@ -17,7 +17,7 @@ B="--steps 8 --warmup 2 --repeats 1 --data device --no-cpu-baseline --no-16bit-s
 case $PART in
 1)
   timeout -k 10 900 python3 -m pytest tests -m gpu -q -p no:cacheprovider > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -2 $O/pytest.log
-  timeout -k 10 400 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+  timeout -k 10 400 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
   bash scripts/bench_configs.sh $TAG/configs > $O/configs.txt 2>&1; cat $O/configs.txt
   ;;
 2)
@@ -53,15 +53,15 @@ case $PART in
   done
   cd $R
   rm -rf $O/tl_shard $O/tl_c2 $O/tl_c3 $O/tl_c5shard
-  timeout -k 10 300 python3 bench.py --workload transform > $O/bench_transform.json 2> $O/bench_transform.err; echo "transform rc=$?"
+  timeout -k 10 300 python3 bench.py --workload transform --full > $O/bench_transform.json 2> $O/bench_transform.err; echo "transform rc=$?"
   ;;
 5)
   # the instruction-mix / busy counter groups of configuration 2's row pass (profiles/r06_pmc_summary_c2.txt)
   bash scripts/pmc_profile.sh $TAG/pmc_mix_c2 --rows 50000 --components 50 $B > /dev/null 2>&1; echo "pmc mix c2 rc=$?"
   ;;
 4)
-  timeout -k 10 400 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
-  timeout -k 10 300 python3 bench.py --workload transform > $O/bench_transform.json 2> $O/bench_transform.err; echo "transform rc=$?"
+  timeout -k 10 400 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+  timeout -k 10 300 python3 bench.py --workload transform --full > $O/bench_transform.json 2> $O/bench_transform.err; echo "transform rc=$?"
   bash scripts/bench_configs.sh $TAG/configs > $O/configs.txt 2>&1; cat $O/configs.txt
   ;;
 esac

@@ -6,7 +6,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for grp in "LdsLatency" "VmemLatency" "InstrFetchLatency SmemLatency"; do
   tag=$(echo $grp | tr " " "_")
-  timeout 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/$tag -o p -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/$tag.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/$tag -o p -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $OUT/$tag.log 2>&1
 done
 cd $R
 python3 - <<'PY'

@@ -276,7 +276,7 @@ def test_bench_two_rank_rehearsal(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, KLNMF_BENCH_REHEARSAL='1')
     common = ['--steps', '4', '--warmup', '2', '--repeats', '2', '--rows', '20000', '--features', '512', '--components', '40',
-              '--no-cpu-baseline']
+              '--full', '--no-cpu-baseline']
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(root, 'bench.py'), '--gpus', '2'] + common \
         + ['--dump-outputs', str(tmp_path / 'two')]

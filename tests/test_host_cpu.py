@@ -219,6 +219,8 @@ def test_bench_defaults_follow_the_measurement_contract():
     # pass), 1 + 5 iterations: about 25 s of fp64 work on the GPU box's host, 4 of the 6 GPU iterations on fp8
     assert a.cpu_rows == 100000 and a.cpu_iters == 5 and a.segment_timeout > 0
     assert a.dump_outputs is None
+    # a plain run measures the headline alone: the CPU baseline, value_16bit and power_clock are --full's
+    assert not a.full and bench.parse_args(['--full']).full
     with pytest.raises(SystemExit):
         bench.parse_args(['--steps', '0'])
 
