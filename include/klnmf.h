@@ -37,6 +37,7 @@ extern "C" {
 #define KLNMF_ERR_HIP      -3        /* HIP runtime error                 */
 #define KLNMF_ERR_UNSUPP   -4        /* shape not supported by this mode  */
 #define KLNMF_ERR_RCCL     -5        /* an RCCL call failed, or librccl could not be opened */
+#define KLNMF_ERR_REPLICA  -6        /* the dictionaries of a group's contexts differ after a loop (klnmf_group_run) */
 
 /* arithmetic modes */
 #define KLNMF_PREC_F64      0        /* fp64 everywhere (reference arithmetic)      */
@@ -62,6 +63,7 @@ extern "C" {
 #define KLNMF_DT_F64        1
 
 typedef struct klnmf_ctx klnmf_ctx;
+typedef struct klnmf_group klnmf_group;
 
 /* ---- library / device -------------------------------------------------- */
 int         klnmf_version(void);
@@ -237,6 +239,45 @@ int klnmf_iter_colpass_part(klnmf_ctx *ctx, int part);
  * tensors handed to torch.distributed.all_reduce): loss_ptr >= 2 doubles,
  * numer_ptr >= numer_count elements.  NULL keeps the current buffer. */
 int klnmf_bind_exchange(klnmf_ctx *ctx, void *loss_ptr, void *numer_ptr);
+
+/* ---- Row shards driven from ONE host thread: a group of contexts (SURVEY.md 8e's ctx_create(device_ids[], n_dev)) ---------
+ * One ordinary context per row shard, each on one device; a device may repeat (several shards on one GPU).  What travels per fit
+ * iteration is what the RCCL path exchanges -- the numerator of the H rule (nmf.py:349) and the two loss doubles (nmf.py:214) --
+ * summed by two launches per context that read the peers' buffers directly (peer access; fine-grained device memory where the
+ * members are on distinct devices), ordered by HIP events only: no flags, no spinning, no graphs.
+ * Every element is summed in shard order, so every replica of H holds the same bits.
+ *   each shard:  klnmf_create(device_i) -> klnmf_set_problem(n_i, f, k, cap) -> klnmf_set_v_max(max over ALL shards) -> uploads ->
+ *                klnmf_set_H (the same H) -> klnmf_init_W
+ *   klnmf_group_create(&g, ctxs, n) -> klnmf_group_run(g, n_total, ...) (as often as wanted) -> klnmf_group_destroy(g)
+ *
+ * klnmf_group_create  contexts whose problems are set, in row order; they must share f, k, precision and capacity (CSR problems:
+ *                     KLNMF_ERR_UNSUPP).  Enables peer access between every pair of distinct devices (KLNMF_ERR_UNSUPP naming
+ *                     the pair where hipDeviceCanAccessPeer says no), allocates the exchange buffers and binds them to the
+ *                     contexts (klnmf_bind_exchange).  A context belongs to one group at a time. */
+int klnmf_group_create(klnmf_group **out, klnmf_ctx *const *ctxs, int n);
+/* klnmf_group_run  the whole loop of nmf.py:212-222 over the group's shards, fit (H rule) or transform (fit = 0: the loss
+ *                  alone is exchanged); tol is the RELATIVE tolerance of nmf.py:207 (x n_total x f inside).  The loop's entry is
+ *                  agreed on the host: if any shard is refused (V beyond the announced maximum, factors beyond the fp16 operand
+ *                  range) every shard fails together before anything is enqueued, and the fp8 decision is taken from the sums
+ *                  over all shards (klnmf_loop_begin_agreed on each).  Per iteration: row pass, column pass, exchange, stop rule,
+ *                  H rule; the stop rule is polled every 16 iterations.  errors_out / n_done / stopped: shard 0's (identical on
+ *                  every shard).  After a fit the dictionaries of all shards are compared bit for bit: KLNMF_ERR_REPLICA if
+ *                  they differ.  Synchronous. */
+int klnmf_group_run(klnmf_group *g, int64_t n_total, int64_t max_iter, int fit, double tol,
+                    double *errors_out, int64_t *n_done, int *stopped);
+/* klnmf_group_destroy  frees the exchange buffers and gives every context its own back (destroy the group before the
+ *                      contexts' problems are released or re-set). */
+int klnmf_group_destroy(klnmf_group *g);
+/* klnmf_group_enqueue_time  the host's time to enqueue one iteration of the last klnmf_group_run on this thread (every member's
+ *                           pieces, waits and exchange launches; the stop rule's polls every 16 iterations excluded): the
+ *                           iterations timed, the median and the largest, in milliseconds.  The median of a loop that keeps the
+ *                           GPU busy is what one host thread costs per iteration (scripts/group_timing.py). */
+int klnmf_group_enqueue_time(klnmf_group *g, int64_t *iterations, double *median_ms, double *max_ms);
+/* klnmf_group_selftest  the exchange alone on buffers of its own: n buffers of `count` elements (dtype KLNMF_DT_F32 /
+ *                       KLNMF_DT_F64) on devices[0 .. n) filled with values whose sum depends on the order of summation,
+ *                       both phases run, every buffer and loss pair compared bit for bit with the host's sum in shard order;
+ *                       *failed = mismatching elements (0 = pass). */
+int klnmf_group_selftest(const int *devices, int n, int64_t count, int dtype, int *failed);
 
 /* Step-granular entry points (unit parity with the reference's private
  * methods).  Synchronous. */

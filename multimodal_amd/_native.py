@@ -29,7 +29,7 @@ PRECISIONS = {'f64': PREC_F64, 'fp64': PREC_F64, 'float64': PREC_F64,
 DT_F32, DT_F64 = 0, 1
 STREAM_DEFAULT = (1 << 64) - 1        # KLNMF_STREAM_DEFAULT: (void *)(intptr_t)-1
 
-ERR_ARG, ERR_ALLOC, ERR_HIP, ERR_UNSUPP, ERR_RCCL = -1, -2, -3, -4, -5
+ERR_ARG, ERR_ALLOC, ERR_HIP, ERR_UNSUPP, ERR_RCCL, ERR_REPLICA = -1, -2, -3, -4, -5, -6
 COMM_ID_BYTES = 128
 
 _c = ctypes
@@ -87,6 +87,12 @@ SIGNATURES = {
                                           _c.POINTER(_c.c_int)]),
     'klnmf_exchange_layout': (_c.c_int, [_ctx_p, _c.POINTER(_i64), _c.POINTER(_i64)]),
     'klnmf_bind_exchange': (_c.c_int, [_ctx_p, _c.c_void_p, _c.c_void_p]),
+    'klnmf_group_create': (_c.c_int, [_c.POINTER(_c.c_void_p), _c.POINTER(_ctx_p), _c.c_int]),
+    'klnmf_group_run': (_c.c_int, [_c.c_void_p, _i64, _i64, _c.c_int, _c.c_double,
+                                   _c.POINTER(_c.c_double), _c.POINTER(_i64), _c.POINTER(_c.c_int)]),
+    'klnmf_group_destroy': (_c.c_int, [_c.c_void_p]),
+    'klnmf_group_enqueue_time': (_c.c_int, [_c.c_void_p, _c.POINTER(_i64), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    'klnmf_group_selftest': (_c.c_int, [_c.POINTER(_c.c_int), _c.c_int, _i64, _c.c_int, _c.POINTER(_c.c_int)]),
     'klnmf_error': (_c.c_int, [_ctx_p, _c.POINTER(_c.c_double)]),
     'klnmf_loss_terms': (_c.c_int, [_ctx_p, _c.POINTER(_c.c_double)]),
     'klnmf_update': (_c.c_int, [_ctx_p, _c.c_int]),
@@ -684,3 +690,62 @@ class Context(object):
         v = _c.c_double(0.0)
         _check(self._lib.klnmf_query_f64(self._h, int(what), ctypes.byref(v)))
         return float(v.value)
+
+
+def group_selftest(devices, count, f64=False):
+    """klnmf_group_selftest: the group exchange alone on `len(devices)` buffers of `count` elements (float64 or float32) filled
+    with values whose sum depends on the order of summation; returns the number of elements (and loss pairs) that differ
+    bit for bit from the host's sum in shard order (0 = pass)."""
+    lib = load()
+    devs = (_c.c_int * len(devices))(*[int(d) for d in devices])
+    failed = _c.c_int(-1)
+    _check(lib.klnmf_group_selftest(devs, len(devices), int(count), DT_F64 if f64 else DT_F32, ctypes.byref(failed)))
+    return failed.value
+
+
+class Group(object):
+    """klnmf_group_*: the row shards of one problem, one `Context` each (a device may repeat), driven from this thread.  The
+    contexts' problems must be set (same f, k, precision, capacity); the group binds its own exchange buffers to them until
+    `close()`.  The contexts stay owned by the caller and must outlive the group."""
+
+    def __init__(self, contexts):
+        self._lib = load()
+        self._h = _c.c_void_p()
+        self.contexts = list(contexts)
+        arr = (_ctx_p * len(self.contexts))(*[c._h.value for c in self.contexts])
+        _check(self._lib.klnmf_group_create(ctypes.byref(self._h), arr, len(self.contexts)))
+
+    def run(self, n_total, max_iter, fit, tol):
+        """The whole loop over the shards (tol relative, nmf.py:207); returns (errors list, n_done, stopped) -- shard 0's,
+        identical on every shard.  NativeError with code ERR_REPLICA if the shards' dictionaries differ after a fit."""
+        max_iter = int(max_iter)
+        errs = np.zeros(max(1, max_iter), dtype=np.float64)
+        nd = _i64(0)
+        stopped = _c.c_int(0)
+        _check(self._lib.klnmf_group_run(self._h, int(n_total), max_iter, 1 if fit else 0, float(tol),
+                                         errs.ctypes.data_as(_c.POINTER(_c.c_double)), ctypes.byref(nd),
+                                         ctypes.byref(stopped)))
+        return [float(e) for e in errs[:nd.value]], nd.value, bool(stopped.value)
+
+    def enqueue_time(self):
+        """(iterations timed, median ms, largest ms) of the host's per-iteration enqueue in the last `run`."""
+        it, med, mx = _i64(0), _c.c_double(0), _c.c_double(0)
+        _check(self._lib.klnmf_group_enqueue_time(self._h, ctypes.byref(it), ctypes.byref(med), ctypes.byref(mx)))
+        return it.value, med.value, mx.value
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h.value:
+            self._lib.klnmf_group_destroy(self._h)
+            self._h = _c.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()

@@ -4,6 +4,8 @@
 //   api_loop.hip     the loop of nmf.py:212-222 and its pieces: launch sequencing, stop rule, fp8 regime and its monitor
 //   api_comm.hip     row shards over the GPUs of a node: the RCCL communicator, the agreed loop entry, the exchange (nmf.py:349)
 //   api_eval.hip     evaluation and introspection: reconstruction products (learner.py:80-84), distances, queries, profiling
+//   api_group.hip    a group of contexts (row shards, one device each, a device may repeat) driven from one host thread: the
+//                    exchange of group.hip.h between their streams, the loop of klnmf_group_run
 // This header: error handling, the device block cache, the development switches and the context itself.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -198,11 +198,12 @@ def _sweep_worker(job):
      precision) = job
     import os
     import torch
-    saved = {name: os.environ.get(name) for name in ('KLNMF_PRECISION', 'KLNMF_DEVICE')}
+    saved = {name: os.environ.get(name) for name in ('KLNMF_PRECISION', 'KLNMF_DEVICE', 'KLNMF_DEVICES')}
     try:       # (the learner's NMF objects read their mode and device from the environment, as experiment.py's would)
         if precision is not None:
             os.environ['KLNMF_PRECISION'] = precision
         os.environ['KLNMF_DEVICE'] = str(device)
+        os.environ.pop('KLNMF_DEVICES', None)      # (a sweep is replica-parallel: every learner of this worker on its one device)
         torch.cuda.set_device(device)
         from .device_data import DeviceDataset
         ds = DeviceDataset(data, device=device)

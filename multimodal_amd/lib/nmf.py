@@ -25,7 +25,9 @@ Extra (non-reference) constructor arguments: `precision` ('f64' default =
 the reference's float64 arithmetic; 'f32'; 'bf16x3' = the f32 mode with its contractions on the bf16 matrix cores, every
 fp32 operand split into two bf16 parts (hi.hi + hi.lo + lo.hi, fp32 accumulation: each product within ~2^-16 of a.b; any
 shape, any k, any eps); 'f16x3' = the same with fp16 operand parts under power-of-two scales and, for k <= 256, the
-loop's passes fused (k > 256: 'bf16x3'); 'f16' (= 'bf16') = MFMA fast path with V stored as power-of-two-scaled fp16; 'auto'), `device`.  Environment: KLNMF_PRECISION, KLNMF_DEVICE.
+loop's passes fused (k > 256: 'bf16x3'); 'f16' (= 'bf16') = MFMA fast path with V stored as power-of-two-scaled fp16; 'auto'), `device` (a GPU index, or a
+list of them: the dense loop then runs over row shards, one context per entry -- `_fit_group`).  Environment: KLNMF_PRECISION,
+KLNMF_DEVICES (a comma-separated list, the default `device`), KLNMF_DEVICE.
 """
 import os
 import sys
@@ -135,8 +137,43 @@ def sparse_precision(precision):
     return 'f32'
 
 
+def _devices_of(device):
+    """`device` as a tuple of GPU indices: an int is a one-entry list; a sequence of ints is a list (entries may repeat)."""
+    if isinstance(device, (int, np.integer)) and not isinstance(device, bool):
+        return (int(device),)
+    try:
+        devices = tuple(device)
+    except TypeError:
+        raise ValueError("device must be a GPU index or a sequence of them, not %r" % (device,))
+    if not devices or any(isinstance(d, bool) or not isinstance(d, (int, np.integer)) or d < 0 for d in devices):
+        raise ValueError("device must be a GPU index or a non-empty sequence of them, not %r" % (device,))
+    return tuple(int(d) for d in devices)
+
+
+def _default_devices():
+    """KLNMF_DEVICES (comma-separated GPU indices) if set, else KLNMF_DEVICE (one index, default 0)."""
+    env = os.environ.get('KLNMF_DEVICES', '').strip()
+    if env:
+        try:
+            return _devices_of([int(x) for x in env.split(',') if x.strip()])
+        except ValueError:
+            raise ValueError("KLNMF_DEVICES=%r: expected comma-separated GPU indices, e.g. 0,1,2,3" % env)
+    return (int(os.environ.get('KLNMF_DEVICE', '0')),)
+
+
 def _default_device():
-    return int(os.environ.get('KLNMF_DEVICE', '0'))
+    """The one device of the paths that do not shard (single steps, evaluation, reconstruction): the first default device."""
+    return _default_devices()[0]
+
+
+def shard_plan(n, devices):
+    """[(device, (row0, row1)), ...] of a dense loop on `devices`: `distributed.row_partition` over min(len(devices),
+    ceil(n / 32)) of them (every shard holds at least one 32-row tile).  One entry: the plain single-context path."""
+    from ..distributed import row_partition
+    m = min(len(devices), (int(n) + 31) // 32)
+    if m <= 1:
+        return [(devices[0], (0, int(n)))]
+    return list(zip(devices[:m], row_partition(int(n), m)))
 
 
 def check_non_negative(X, whom):
@@ -215,7 +252,10 @@ class KLdivNMF(object):
         self.eps = eps
         self.subit = subit
         self.precision = precision if precision is not None else _default_precision()
-        self.device = device if device is not None else _default_device()
+        # device: an int, or a list (KLNMF_DEVICES by default): the dense loop of two or more runs over row shards (`_fit_group`);
+        # `device` is the first entry -- where everything that does not shard runs
+        self.devices = _devices_of(device) if device is not None else _default_devices()
+        self.device = self.devices[0]
         self.last_fp8_report = None         # set by every loop: what it ran on e4m3 operands (klnmf_query)
 
     # ------------------------------------------------------------ helpers ---
@@ -274,18 +314,29 @@ class KLdivNMF(object):
         n_features = sum(b.shape[1] for b in blocks)
         return self._fit_uploaded(n_samples, n_features, lambda ctx: ctx.upload_blocks(blocks, coefs),
                                   lambda H_init: _out_dtype(H_init, *blocks), _fit=_fit,
-                                  return_errors=return_errors)
+                                  return_errors=return_errors, host_blocks=(blocks, coefs))
 
     def _fit_uploaded(self, n_samples, n_features, upload, out_dtype_of, _fit=True, return_errors=False,
-                      sparse_X=None):
+                      sparse_X=None, host_blocks=None):
         """The loop of nmf.py:159-230 on a matrix that `upload(ctx)` places in the context: host blocks
-        (`_fit_blocks`) or rows gathered from device-resident data (`device_data.DeviceDataset`)."""
+        (`_fit_blocks`, which also passes them as `host_blocks` = (blocks, coefs): with two or more devices the loop runs over
+        row shards, `_fit_group`) or rows gathered from device-resident data (`device_data.DeviceDataset`: first device)."""
         if not self.n_components:
             self.n_components = n_features
         H_init = self._init_H(n_features)
         k = self.n_components
         max_iter = int(self.max_iter)
         out_dtype = out_dtype_of(H_init)
+
+        if len(self.devices) > 1:
+            if sparse_X is not None:
+                _note_once(('csr-group',), "KLdivNMF: CSR input runs on one device (%d), not over the row shards of devices %s "
+                           "(groups hold dense problems only)\n" % (self.device, list(self.devices)))
+            elif host_blocks is not None:
+                plan = shard_plan(n_samples, self.devices)
+                if len(plan) > 1:
+                    return self._fit_group(plan, host_blocks[0], host_blocks[1], n_samples, n_features, H_init, out_dtype, _fit,
+                                           return_errors)
 
         with self._context(shape=None if sparse_X is not None else (n_samples, n_features, k),
                            sparse=sparse_X is not None) as ctx:
@@ -310,6 +361,57 @@ class KLdivNMF(object):
             if _fit and n_done > 0:
                 self.components_ = ctx.get_H(dtype=out_dtype)
 
+        n_iter = n_done + 1 if stopped else max_iter
+        if max_iter > 0 and n_iter == max_iter and tol_abs > 0:   # nmf.py:224-225
+            sys.stderr.write("Warning: Iteration limit reached during fit\n")
+        if return_errors:
+            return W, errors
+        return W
+
+    def _fit_group(self, plan, blocks, coefs, n_samples, n_features, H_init, out_dtype, _fit, return_errors):
+        """`_fit_uploaded` over row shards: one context per entry of `plan` (`shard_plan`), driven as one group
+        (klnmf_group_run: the numerator of the H rule and the loss exchanged between the contexts every iteration).  The
+        arithmetic is the one the global shape picks; V is stored with one factor from the global maximum; W comes back in
+        row order, `components_`, the loss record and `last_fp8_report` from shard 0 (identical on every shard)."""
+        k = self.n_components
+        max_iter = int(self.max_iter)
+        prec = resolve_precision(self.precision, n_samples, n_features, k)
+        vmax = 0.0
+        for b, c in zip(blocks, coefs):
+            if b.size:
+                vmax = max(vmax, float(c) * float(np.max(b)))
+        H_loop = H_init if (_fit or self.components_ is H_init) else self.components_
+        ctxs, group = [], None
+        try:
+            for dev, (r0, r1) in plan:
+                ctx = _native.Context(precision=prec, device=dev, pooled=True)
+                ctxs.append(ctx)
+                ctx.set_problem(r1 - r0, n_features, k, max_iter)
+                ctx.set_v_max(vmax)
+                col = 0
+                for b, c in zip(blocks, coefs):
+                    ctx.upload_V(b[r0:r1], row0=0, col0=col, scale=c)
+                    col += b.shape[1]
+                ctx.set_H(H_init)
+                ctx.init_W()                       # W0 = X . H_init^T (nmf.py:156), this shard's rows
+                if H_loop is not H_init:
+                    ctx.set_H(H_loop)              # loop runs on components_ (nmf.py:214)
+            if _fit:
+                self.components_ = H_init          # nmf.py:203-204
+            group = _native.Group(ctxs)
+            errors, n_done, stopped = group.run(n_samples, max_iter, _fit, self.tol)
+            self.last_fp8_report = ctxs[0].fp8_report()
+            self.last_fp8_report['shards'] = len(ctxs)
+            self._check_f16_envelope(ctxs[0], n_samples, n_features, k)
+            W = np.vstack([ctx.get_W(dtype=out_dtype) for ctx in ctxs])
+            if _fit and n_done > 0:
+                self.components_ = ctxs[0].get_H(dtype=out_dtype)
+        finally:
+            if group is not None:
+                group.close()
+            for ctx in ctxs:
+                ctx.close()
+        tol_abs = self.tol * n_samples * n_features
         n_iter = n_done + 1 if stopped else max_iter
         if max_iter > 0 and n_iter == max_iter and tol_abs > 0:   # nmf.py:224-225
             sys.stderr.write("Warning: Iteration limit reached during fit\n")
