@@ -248,10 +248,12 @@ int klnmf_bind_exchange(klnmf_ctx *ctx, void *loss_ptr, void *numer_ptr);
  * Every element is summed in shard order, so every replica of H holds the same bits.
  *   each shard:  klnmf_create(device_i) -> klnmf_set_problem(n_i, f, k, cap) -> klnmf_set_v_max(max over ALL shards) -> uploads ->
  *                klnmf_set_H (the same H) -> klnmf_init_W
+ *                (CSR: klnmf_set_problem_sparse(n_i, f, k, cap, nnz_i) -> klnmf_upload_csr_rows of the shard's rows -> klnmf_set_H ->
+ *                klnmf_init_W; a shard may hold no stored entry)
  *   klnmf_group_create(&g, ctxs, n) -> klnmf_group_run(g, n_total, ...) (as often as wanted) -> klnmf_group_destroy(g)
  *
- * klnmf_group_create  contexts whose problems are set, in row order; they must share f, k, precision and capacity (CSR problems:
- *                     KLNMF_ERR_UNSUPP).  Enables peer access between every pair of distinct devices (KLNMF_ERR_UNSUPP naming
+ * klnmf_group_create  contexts whose problems are set, in row order; they must share f, k, precision and capacity, and be all
+ *                     dense or all CSR (KLNMF_ERR_ARG otherwise: the contexts stay as they were).  Enables peer access between every pair of distinct devices (KLNMF_ERR_UNSUPP naming
  *                     the pair where hipDeviceCanAccessPeer says no), allocates the exchange buffers and binds them to the
  *                     contexts (klnmf_bind_exchange).  A context belongs to one group at a time. */
 int klnmf_group_create(klnmf_group **out, klnmf_ctx *const *ctxs, int n);
@@ -428,6 +430,13 @@ int klnmf_synchronize(klnmf_ctx *ctx);
 int klnmf_set_problem_sparse(klnmf_ctx *ctx, int64_t n, int64_t f, int64_t k, int64_t max_iter_capacity, int64_t nnz);
 int klnmf_upload_csr(klnmf_ctx *ctx, int dtype, const int64_t *indptr, const int64_t *indices, const void *data,
                      const int64_t *csc_indptr, const int64_t *csc_rows, const int64_t *csc_perm);
+/* klnmf_upload_csr_rows  X in CSR only (indptr[n+1], indices[nnz], data[nnz]); the library builds the CSC order on the device
+ * (csrc/csc.hip.h: a stable radix sort of the entries by column), bit for bit what klnmf_upload_csr is given by a caller that
+ * sorts on the host (np.argsort(indices, kind='stable')).  It replaces the host side of nmf.py:52-70 and 331-351 -- the
+ * transposed access to X's structure that `_special_sparse_dot` and the H rule's W^T.Q need.  The structure is checked on the
+ * device first: row pointers that decrease, a column index outside [0, f) or indices of a row that are not sorted are refused
+ * (KLNMF_ERR_ARG) before anything is reordered, and leave the problem with no stored entry until the next upload. */
+int klnmf_upload_csr_rows(klnmf_ctx *ctx, int dtype, const int64_t *indptr, const int64_t *indices, const void *data);
 int klnmf_get_Q_values(klnmf_ctx *ctx, void *dst, int dtype);
 
 /* ---- reconstruction (next-row K7) ---------------------------------------- */

@@ -123,6 +123,7 @@ SIGNATURES = {
     'klnmf_set_problem_sparse': (_c.c_int, [_ctx_p, _i64, _i64, _i64, _i64, _i64]),
     'klnmf_upload_csr': (_c.c_int, [_ctx_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                     _c.c_void_p, _c.c_void_p]),
+    'klnmf_upload_csr_rows': (_c.c_int, [_ctx_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     'klnmf_get_Q_values': (_c.c_int, [_ctx_p, _c.c_void_p, _c.c_int]),
     'klnmf_matmul': (_c.c_int, [_c.c_int, _c.c_int, _i64, _i64, _i64, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     'klnmf_all_distances': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _i64, _i64, _i64, _c.c_void_p, _c.c_void_p,
@@ -379,7 +380,7 @@ class Context(object):
     # ---- CSR input (exact modes) ----
     def set_problem_sparse(self, X, k, max_iter_capacity):
         """X: scipy CSR (explicit zeros are dropped, indices sorted -- nmf.py:66 does the same).  Uploads the
-        structure in CSR and CSC order and the values."""
+        structure in CSR order and the values; the library builds the CSC order on the device (klnmf_upload_csr_rows)."""
         import scipy.sparse as sp
         X = sp.csr_matrix(X, copy=True)
         X.eliminate_zeros()
@@ -393,15 +394,8 @@ class Context(object):
         indptr = np.ascontiguousarray(X.indptr, dtype=np.int64)
         indices = np.ascontiguousarray(X.indices, dtype=np.int64)
         data = np.ascontiguousarray(X.data, dtype=dt)
-        # CSC order of the same entries: a stable sort of the CSR entries by column
-        perm = np.argsort(indices, kind='stable').astype(np.int64)
-        rows_of = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
-        csc_rows = np.ascontiguousarray(rows_of[perm])
-        csc_indptr = np.zeros(f + 1, dtype=np.int64)
-        np.cumsum(np.bincount(indices, minlength=f), out=csc_indptr[1:])
         p = lambda a: a.ctypes.data_as(_c.c_void_p)
-        _check(self._lib.klnmf_upload_csr(self._h, DT_F32 if dt == np.float32 else DT_F64, p(indptr), p(indices),
-                                          p(data), p(csc_indptr), p(csc_rows), p(perm)))
+        _check(self._lib.klnmf_upload_csr_rows(self._h, DT_F32 if dt == np.float32 else DT_F64, p(indptr), p(indices), p(data)))
         self._csr = (indptr, indices)
         return X
 

@@ -37,7 +37,6 @@ bool comm_multi(const klnmf_ctx *c) { return c->comm != nullptr && (c->comm_size
 // (a rank-local overflow, a rank-local operand range) are all-reduced (max) and every rank fails TOGETHER; the fp8 decision
 // is taken from the all-reduced sums, so that all ranks run the same kernels and N = 1 / N = 8 differ by summation order only.
 void comm_loop_entry(klnmf_ctx *c) {
-    if (c->sparse) fail(KLNMF_ERR_UNSUPP, "loops on a communicator: dense problems only");
     c->refusals_dirty = true;
     const Refusals mine = read_refusals(c);
     DevState ds{};
@@ -196,7 +195,6 @@ int klnmf_run_sharded(klnmf_ctx *c, int64_t n_total, int64_t max_iter, int fit, 
         need_problem(c);
         if (max_iter < 0 || max_iter > c->cap) fail(KLNMF_ERR_ARG, "max_iter out of range");
         if (n_total < c->n) fail(KLNMF_ERR_ARG, "n_total smaller than this rank's rows");
-        if (c->sparse) fail(KLNMF_ERR_UNSUPP, "klnmf_run_sharded: dense problems only");
         const bool multi = comm_multi(c);
         if (multi) {
             comm_loop_entry(c);

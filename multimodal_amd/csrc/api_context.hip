@@ -1,5 +1,6 @@
 // libklnmf.so, unit 1 of 4: contexts, problems, uploads and downloads (ctx.hip.h lists the units).
 #include "ctx.hip.h"
+#include "csc.hip.h"
 
 DevBlockCache g_block_cache;
 
@@ -552,6 +553,83 @@ int klnmf_release_problem(klnmf_ctx *c) {
     });
 }
 
+}  // extern "C"
+
+namespace {
+
+// The blocked regime's structures of an uploaded CSR problem (sparseb.hip.h): block pointers by binary search in the sorted rows /
+// columns, int32 copies of the indices.  Refuses (`msg`) unsorted rows or columns.
+static void csr_blocked_setup(klnmf_ctx *c, const char *msg) {
+    if (!c->sp_blocked) return;
+    HIPCHK(hipMemsetAsync(c->sp_bad, 0, sizeof(int), c->stream));
+    hipLaunchKernelGGL(k_spb_blkptr, dim3(grid_for(c->n * (c->sp_cb + 1), 256, 1 << 20)), dim3(256), 0, c->stream,
+                       (const int64_t *)c->sp_indptr, (const int64_t *)c->sp_indices, c->n, c->sp_cb, c->sp_cb_cols, c->sp_blkptr, c->sp_bad);
+    hipLaunchKernelGGL(k_spb_blkptr, dim3(grid_for(c->f * (c->sp_rb + 1), 256, 1 << 20)), dim3(256), 0, c->stream,
+                       (const int64_t *)c->csc_indptr, (const int64_t *)c->csc_rows, c->f, c->sp_rb, c->sp_rb_rows, c->csc_blkptr, c->sp_bad);
+    hipLaunchKernelGGL(k_spb_narrow, dim3(grid_for(c->nnz, 256, 8192)), dim3(256), 0, c->stream, (const int64_t *)c->sp_indices, c->sp_idx32, c->nnz);
+    hipLaunchKernelGGL(k_spb_narrow, dim3(grid_for(c->nnz, 256, 8192)), dim3(256), 0, c->stream, (const int64_t *)c->csc_rows, c->csc_rows32, c->nnz);
+    hipLaunchKernelGGL(k_spb_narrow, dim3(grid_for(c->nnz, 256, 8192)), dim3(256), 0, c->stream, (const int64_t *)c->csc_perm, c->csc_perm32, c->nnz);
+    HIPCHK(hipGetLastError());
+    int bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, c->sp_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (bad) fail(KLNMF_ERR_ARG, msg);
+}
+
+// csc_indptr / csc_rows / csc_perm from the CSR structure already on the device (csc.hip.h), after checking it there.  Bad input is
+// refused before any pass runs, and leaves every row and column of the problem empty (no kernel reads the refused indices).
+static void csc_build(klnmf_ctx *c) {
+    const CscWork wk(c->nnz);
+    int64_t *counts = c->csc_work, *parts = c->csc_work + wk.m, *flag = c->csc_work + wk.flag_at();
+    HIPCHK(hipMemsetAsync(flag, 0, sizeof(int64_t), c->stream));
+    hipLaunchKernelGGL(k_csc_check, dim3(grid_for(std::max(c->n, c->nnz), 256, 8192)), dim3(256), 0, c->stream,
+                       (const int64_t *)c->sp_indptr, (const int64_t *)c->sp_indices, c->n, c->f, c->nnz, flag);
+    HIPCHK(hipGetLastError());
+    int64_t bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, flag, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (bad) {
+        HIPCHK(hipMemsetAsync(c->sp_indptr, 0, sizeof(int64_t) * (c->n + 1), c->stream));
+        HIPCHK(hipMemsetAsync(c->csc_indptr, 0, sizeof(int64_t) * (c->f + 1), c->stream));
+        if (c->sp_blocked) {
+            HIPCHK(hipMemsetAsync(c->sp_blkptr, 0, sizeof(int64_t) * c->n * (c->sp_cb + 1), c->stream));
+            HIPCHK(hipMemsetAsync(c->csc_blkptr, 0, sizeof(int64_t) * c->f * (c->sp_rb + 1), c->stream));
+        }
+        HIPCHK(hipStreamSynchronize(c->stream));
+        fail(KLNMF_ERR_ARG, "klnmf_upload_csr_rows: the row pointers must not decrease, and the column indices of every row must be "
+                            "sorted and lie in [0, f)");
+    }
+    if (c->nnz > 0) {
+        int bits = 0;
+        while (bits < 62 && ((c->f - 1) >> bits) != 0) ++bits;
+        const int passes = std::max(1, (bits + kCscBits - 1) / kCscBits);
+        const int64_t *src = nullptr;
+        for (int p = 0; p < passes; ++p) {
+            // the last pass writes csc_perm; csc_rows is the other buffer until k_csc_rows fills it
+            int64_t *dst = ((passes - 1 - p) & 1) == 0 ? c->csc_perm : c->csc_rows;
+            const int shift = p * kCscBits;
+            hipLaunchKernelGGL(k_csc_hist, dim3((unsigned)wk.tiles), dim3(kCscThreads), 0, c->stream, src,
+                               (const int64_t *)c->sp_indices, c->nnz, shift, wk.tiles, counts);
+            hipLaunchKernelGGL(k_csc_scan_tiles, dim3((unsigned)wk.nparts), dim3(kCscThreads), 0, c->stream, counts, wk.m, parts);
+            hipLaunchKernelGGL(k_csc_scan_part, dim3(1), dim3(kCscThreads), 0, c->stream, parts, wk.nparts);
+            hipLaunchKernelGGL(k_csc_scan_add, dim3(grid_for(wk.m, 256, 8192)), dim3(256), 0, c->stream, counts, wk.m, (const int64_t *)parts);
+            hipLaunchKernelGGL(k_csc_scatter, dim3((unsigned)wk.tiles), dim3(kCscThreads), 0, c->stream, src,
+                               (const int64_t *)c->sp_indices, c->nnz, shift, wk.tiles, (const int64_t *)counts, dst);
+            HIPCHK(hipGetLastError());
+            src = dst;
+        }
+        hipLaunchKernelGGL(k_csc_rows, dim3(grid_for(c->nnz, 256, 8192)), dim3(256), 0, c->stream, (const int64_t *)c->csc_perm,
+                           (const int64_t *)c->sp_indptr, c->n, c->nnz, c->csc_rows);
+    }
+    hipLaunchKernelGGL(k_csc_indptr, dim3(grid_for(c->f + 1, 256, 8192)), dim3(256), 0, c->stream, (const int64_t *)c->csc_perm,
+                       (const int64_t *)c->sp_indices, c->nnz, c->f, c->csc_indptr);
+    HIPCHK(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" {
+
 int klnmf_set_problem_sparse(klnmf_ctx *c, int64_t n, int64_t f, int64_t k, int64_t cap, int64_t nnz) {
     return guarded([&] {
         use(c);
@@ -584,6 +662,7 @@ int klnmf_set_problem_sparse(klnmf_ctx *c, int64_t n, int64_t f, int64_t k, int6
         c->csc_indptr = (int64_t *)c->dalloc(sizeof(int64_t) * (f + 1));
         c->csc_rows = (int64_t *)c->dalloc(sizeof(int64_t) * (nnz > 0 ? nnz : 1));
         c->csc_perm = (int64_t *)c->dalloc(sizeof(int64_t) * (nnz > 0 ? nnz : 1));
+        c->csc_work = (int64_t *)c->dalloc(sizeof(int64_t) * CscWork(nnz).elems);
         c->sp_data = c->dalloc((size_t)(nnz > 0 ? nnz : 1) * es);
         c->sp_q = c->dalloc((size_t)(nnz > 0 ? nnz : 1) * es);
         c->sp_row_loss = (double *)c->dalloc(sizeof(double) * n);
@@ -655,22 +734,27 @@ int klnmf_upload_csr(klnmf_ctx *c, int dtype, const int64_t *indptr, const int64
             // values: through the dense setter (dtype conversion) as a 1 x nnz matrix
             set_matrix(c, data, dtype, 1, c->nnz, c->sp_data, nullptr, 0);
         }
-        if (c->sp_blocked) {
-            // block pointers by binary search in the sorted rows / columns, int32 copies of the indices (sparseb.hip.h)
-            HIPCHK(hipMemsetAsync(c->sp_bad, 0, sizeof(int), c->stream));
-            hipLaunchKernelGGL(k_spb_blkptr, dim3(grid_for(c->n * (c->sp_cb + 1), 256, 1 << 20)), dim3(256), 0, c->stream,
-                               (const int64_t *)c->sp_indptr, (const int64_t *)c->sp_indices, c->n, c->sp_cb, c->sp_cb_cols, c->sp_blkptr, c->sp_bad);
-            hipLaunchKernelGGL(k_spb_blkptr, dim3(grid_for(c->f * (c->sp_rb + 1), 256, 1 << 20)), dim3(256), 0, c->stream,
-                               (const int64_t *)c->csc_indptr, (const int64_t *)c->csc_rows, c->f, c->sp_rb, c->sp_rb_rows, c->csc_blkptr, c->sp_bad);
-            hipLaunchKernelGGL(k_spb_narrow, dim3(grid_for(c->nnz, 256, 8192)), dim3(256), 0, c->stream, (const int64_t *)c->sp_indices, c->sp_idx32, c->nnz);
-            hipLaunchKernelGGL(k_spb_narrow, dim3(grid_for(c->nnz, 256, 8192)), dim3(256), 0, c->stream, (const int64_t *)c->csc_rows, c->csc_rows32, c->nnz);
-            hipLaunchKernelGGL(k_spb_narrow, dim3(grid_for(c->nnz, 256, 8192)), dim3(256), 0, c->stream, (const int64_t *)c->csc_perm, c->csc_perm32, c->nnz);
-            HIPCHK(hipGetLastError());
-            int bad = 0;
-            HIPCHK(hipMemcpyAsync(&bad, c->sp_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            if (bad) fail(KLNMF_ERR_ARG, "klnmf_upload_csr: the column indices of every row (and the rows of every column in the CSC arrays) must be sorted");
-        }
+        csr_blocked_setup(c, "klnmf_upload_csr: the column indices of every row (and the rows of every column in the CSC arrays) must be sorted");
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->v_uploaded = true;
+        c->refusals_dirty = true;
+    });
+}
+
+int klnmf_upload_csr_rows(klnmf_ctx *c, int dtype, const int64_t *indptr, const int64_t *indices, const void *data) {
+    return guarded([&] {
+        need_problem(c);
+        if (!c->sparse) fail(KLNMF_ERR_ARG, "klnmf_upload_csr_rows needs klnmf_set_problem_sparse");
+        if (!indptr || (c->nnz > 0 && (!indices || !data))) fail(KLNMF_ERR_ARG, "null pointer");
+        if (dtype != KLNMF_DT_F32 && dtype != KLNMF_DT_F64) fail(KLNMF_ERR_ARG, "dtype must be KLNMF_DT_F32 or KLNMF_DT_F64");
+        if (indptr[0] != 0 || indptr[c->n] != c->nnz) fail(KLNMF_ERR_ARG, "the row pointers do not match n, nnz");
+        c->v_uploaded = false;
+        HIPCHK(hipMemcpyAsync(c->sp_indptr, indptr, sizeof(int64_t) * (c->n + 1), hipMemcpyHostToDevice, c->stream));
+        if (c->nnz > 0)
+            HIPCHK(hipMemcpyAsync(c->sp_indices, indices, sizeof(int64_t) * c->nnz, hipMemcpyHostToDevice, c->stream));
+        csc_build(c);
+        if (c->nnz > 0) set_matrix(c, data, dtype, 1, c->nnz, c->sp_data, nullptr, 0);
+        csr_blocked_setup(c, "klnmf_upload_csr_rows: the column indices of every row must be sorted");
         HIPCHK(hipStreamSynchronize(c->stream));
         c->v_uploaded = true;
         c->refusals_dirty = true;

@@ -204,7 +204,9 @@ int klnmf_group_create(klnmf_group **out, klnmf_ctx *const *ctxs, int n) {
         const klnmf_ctx *c0 = ctxs[0];
         for (int r = 0; r < n; ++r) {
             const klnmf_ctx *c = ctxs[r];
-            if (c->sparse) fail(KLNMF_ERR_UNSUPP, "klnmf_group_create: CSR problems do not run on a group (shard " + std::to_string(r) + ")");
+            if (c->sparse != c0->sparse)
+                fail(KLNMF_ERR_ARG, "klnmf_group_create: shard " + std::to_string(r) + " holds a " + (c->sparse ? "CSR" : "dense") +
+                                        " problem, shard 0 a " + (c0->sparse ? "CSR" : "dense") + " one: the members must be all dense or all CSR");
             if (c->f != c0->f || c->k != c0->k || c->prec != c0->prec || c->cap != c0->cap)
                 fail(KLNMF_ERR_ARG, "klnmf_group_create: shard " + std::to_string(r) + " differs from shard 0 in f, k, precision or capacity");
             if (c->comm != nullptr) fail(KLNMF_ERR_ARG, "klnmf_group_create: shard " + std::to_string(r) + " holds an RCCL communicator");

@@ -260,6 +260,7 @@ struct klnmf_ctx {
     double *sp_loss_part = nullptr;           // [cb][n]
     void *sp_G = nullptr, *sp_NT = nullptr;   // [cb][n][k], [rb][f][k]
     int *sp_bad = nullptr;
+    int64_t *csc_work = nullptr;      // workspace of the device-side CSC build (csc.hip.h, CscWork: klnmf_upload_csr_rows)
     double *hpart = nullptr;          // exact modes, long rows: [k][hseg_n] partial row sums of the H rule / of the CSR loss term
     int hseg_n = 1; int64_t hseg = 0; // segments per dictionary row and their length (1: the one-block-per-row kernels)
 

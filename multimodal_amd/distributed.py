@@ -45,6 +45,27 @@ def row_partition(n, world_size):
     return [(bounds[r], bounds[r + 1]) for r in range(world_size)]
 
 
+def csr_row_partition(indptr, parts):
+    """Contiguous row ranges [start, stop) of a CSR matrix (row pointers `indptr`) for `parts` shards that balance the STORED
+    ENTRIES, not the rows: boundary r is the first row at which r / parts of the entries have gone by.  No part holds more than
+    nnz / parts plus the entries of one row; every part holds at least one row (it may hold no entry).  Deterministic.
+
+    With fewer rows than parts this raises ValueError, before any collective (as `row_partition`)."""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    n = len(indptr) - 1
+    if parts < 1 or n < parts:
+        raise ValueError("cannot shard %d rows over %d parts: use at most %d" % (n, parts, max(1, n)))
+    nnz = int(indptr[-1])
+    bounds = [0]
+    for r in range(1, parts):
+        # first row i with indptr[i] >= r x nnz / parts (integer arithmetic), then at least one row behind the last boundary
+        # and one row left for every later part
+        b = int(np.searchsorted(indptr * parts, r * nnz, side='left'))
+        bounds.append(min(max(b, bounds[-1] + 1), n - (parts - r)))
+    bounds.append(n)
+    return [(bounds[r], bounds[r + 1]) for r in range(parts)]
+
+
 class ShardedKLNMF(object):
     """The loop of nmf.py:212-222 over row shards.
 
@@ -56,12 +77,23 @@ class ShardedKLNMF(object):
     group         : torch.distributed process group or None (single process).
     backend       : context object; default = a HIP `_native.Context` on the
                     current torch device / stream.
+    csr           : this rank's row block of a CSR matrix (scipy sparse; `csr_row_partition` balances the blocks): the shard is
+                    a CSR problem (klnmf_set_problem_sparse, the reference's sparse branch) in the arithmetic
+                    `nmf.sparse_precision` names for `precision`; n_local and f must match its shape.  Its data is uploaded
+                    here: `upload_V*` and `set_v_max` raise.
     """
 
     def __init__(self, n_total, n_local, f, k, max_iter, precision='f16',
-                 group=None, backend=None, device=None, collective='torch'):
+                 group=None, backend=None, device=None, collective='torch', csr=None):
         import torch
         self.torch = torch
+        self.csr = None
+        if csr is not None:
+            from .lib.nmf import sparse_precision
+            if tuple(csr.shape) != (n_local, f):
+                raise ValueError("csr block of shape %s, expected (n_local, f) = %s" % (tuple(csr.shape), (n_local, f)))
+            precision = sparse_precision(precision)
+            self.csr = csr
         self.n_total, self.n_local, self.f, self.k = n_total, n_local, f, k
         self.max_iter = int(max_iter)
         self.group = group
@@ -80,7 +112,10 @@ class ShardedKLNMF(object):
         else:
             self.tensor_device = torch.device('cpu')
         self.ctx = backend
-        self.ctx.set_problem(n_local, f, k, self.max_iter)
+        if self.csr is not None:
+            self.ctx.set_problem_sparse(self.csr, k, self.max_iter)
+        else:
+            self.ctx.set_problem(n_local, f, k, self.max_iter)
         _, _, count, is64 = self.ctx.exchange_buffers()
         # exchange buffers owned by torch so they can be handed to all_reduce
         self.numer_t = torch.zeros(count, dtype=torch.float64 if is64 else torch.float32,
@@ -125,9 +160,14 @@ class ShardedKLNMF(object):
         self.iterations_enqueued = 0
 
     # ---- data ----
+    def _dense_only(self, what):
+        if self.csr is not None:
+            raise ValueError("ShardedKLNMF.%s: this shard is a CSR problem, uploaded by the constructor" % what)
+
     def set_v_max(self, local_max):
         """Fix the 16-bit storage factor of V from the GLOBAL maximum (all ranks
         must use the same factor because they share H); call before uploading."""
+        self._dense_only('set_v_max')
         if self.collective == 'native':
             self.ctx.set_v_max(self.ctx.comm_max(float(local_max)))
             return
@@ -138,10 +178,12 @@ class ShardedKLNMF(object):
         self.ctx.set_v_max(float(t.item()))
 
     def upload_V(self, block, row0=0, col0=0, scale=1.0):
+        self._dense_only('upload_V')
         self.ctx.upload_V(block, row0=row0, col0=col0, scale=scale)
 
     def upload_V_device(self, tensor, row0=0, col0=0, scale=1.0):
         """fp32 CUDA tensor [rows, cols] (row-major) already on this rank's GPU."""
+        self._dense_only('upload_V_device')
         assert tensor.dtype == self.torch.float32 and tensor.is_contiguous()
         self.ctx.upload_V_device(tensor.data_ptr(), tensor.shape[0], tensor.shape[1],
                                  tensor.stride(0), row0, col0, scale)
@@ -307,7 +349,14 @@ class ShardedKLNMF(object):
             return W
         # one all-gather of equally sized (padded) blocks instead of pickled objects
         torch = self.torch
-        sizes = [b - a for a, b in row_partition(self.n_total, self.world_size)]
+        if self.csr is not None:
+            # CSR shards: blocks of any size (csr_row_partition), gathered first
+            mine_n = torch.tensor([W.shape[0]], dtype=torch.int64, device=self.tensor_device)
+            all_n = [torch.zeros_like(mine_n) for _ in range(self.world_size)]
+            self.dist.all_gather(all_n, mine_n, group=self.group)
+            sizes = [int(t.item()) for t in all_n]
+        else:
+            sizes = [b - a for a, b in row_partition(self.n_total, self.world_size)]
         pad = max(sizes)
         mine = torch.zeros((pad, W.shape[1]), dtype=torch.float64 if np.dtype(dtype) == np.float64 else torch.float32,
                            device=self.tensor_device)

@@ -26,7 +26,8 @@ the reference's float64 arithmetic; 'f32'; 'bf16x3' = the f32 mode with its cont
 fp32 operand split into two bf16 parts (hi.hi + hi.lo + lo.hi, fp32 accumulation: each product within ~2^-16 of a.b; any
 shape, any k, any eps); 'f16x3' = the same with fp16 operand parts under power-of-two scales and, for k <= 256, the
 loop's passes fused (k > 256: 'bf16x3'); 'f16' (= 'bf16') = MFMA fast path with V stored as power-of-two-scaled fp16; 'auto'), `device` (a GPU index, or a
-list of them: the dense loop then runs over row shards, one context per entry -- `_fit_group`).  Environment: KLNMF_PRECISION,
+list of them: the dense loop then runs over row shards, one context per entry -- `_fit_group`; CSR input too, above
+`CSR_SHARD_MIN_NNZ` stored entries per shard -- `_fit_group_csr`).  Environment: KLNMF_PRECISION,
 KLNMF_DEVICES (a comma-separated list, the default `device`), KLNMF_DEVICE.
 """
 import os
@@ -67,6 +68,13 @@ F16_MIN_KL_OVER_SUM_V = 3e-3
 MAX_K_F16X3 = 256         # the fused split-fp16 loop of 'f16x3' holds a workgroup's Q.H^T of all components in registers
 MAX_K_MFMA = 512          # the 16-bit MFMA kernels hold a wave's accumulators of all components in registers: k <= 512
 MAX_ROWS_EXACT = 65535 * 64   # the exact modes' row tiles ride on gridDim.y (csrc/api_context.hip: KLNMF_ERR_UNSUPP beyond)
+
+# CSR input on a device list runs over row shards (`_fit_group_csr`) when every shard holds at least this many stored entries;
+# below, on the list's first device.  At the measured fp64 rate of the sparse loop (about 8.5 G entries/s: README) 2^20 entries
+# are about 0.12 ms of a shard's work per iteration; the group's own cost, measured on one GPU at the bench shape, is 0.02 - 0.04 ms
+# per shard and iteration (N = 2, 4: profiles/csr_shards_group.json), so a shard at the threshold does 3x
+# more work than it costs.  An estimate on one chip: the exchange between distinct devices has not been measured.
+CSR_SHARD_MIN_NNZ = 1 << 20
 
 _NOTED = set()
 
@@ -176,6 +184,21 @@ def shard_plan(n, devices):
     return list(zip(devices[:m], row_partition(int(n), m)))
 
 
+def csr_shard_plan(indptr, devices):
+    """[(device, (row0, row1)), ...] of a CSR loop on `devices`: `distributed.csr_row_partition` (stored entries balanced) over as
+    many of them as keep every shard at `CSR_SHARD_MIN_NNZ` stored entries or more.  One entry: the plain single-context path."""
+    from ..distributed import csr_row_partition
+    indptr = np.asarray(indptr, dtype=np.int64)
+    n, nnz = len(indptr) - 1, int(indptr[-1])
+    m = min(len(devices), n, nnz // max(1, int(CSR_SHARD_MIN_NNZ)))
+    while m > 1:
+        parts = csr_row_partition(indptr, m)
+        if all(int(indptr[b] - indptr[a]) >= CSR_SHARD_MIN_NNZ for a, b in parts):
+            return list(zip(devices[:m], parts))
+        m -= 1
+    return [(devices[0], (0, n))]
+
+
 def check_non_negative(X, whom):
     """ValueError on negative entries (reference nmf.py:23-26)."""
     X = X.data if sp.issparse(X) else X
@@ -252,7 +275,8 @@ class KLdivNMF(object):
         self.eps = eps
         self.subit = subit
         self.precision = precision if precision is not None else _default_precision()
-        # device: an int, or a list (KLNMF_DEVICES by default): the dense loop of two or more runs over row shards (`_fit_group`);
+        # device: an int, or a list (KLNMF_DEVICES by default): the loop on two or more runs over row shards (`_fit_group`, CSR:
+        # `_fit_group_csr`);
         # `device` is the first entry -- where everything that does not shard runs
         self.devices = _devices_of(device) if device is not None else _default_devices()
         self.device = self.devices[0]
@@ -330,8 +354,15 @@ class KLdivNMF(object):
 
         if len(self.devices) > 1:
             if sparse_X is not None:
+                X = sp.csr_matrix(sparse_X, copy=True)      # (what set_problem_sparse uploads: no explicit zeros, sorted rows)
+                X.eliminate_zeros()
+                X.sort_indices()
+                plan = csr_shard_plan(X.indptr, self.devices)
+                if len(plan) > 1:
+                    return self._fit_group_csr(plan, X, n_samples, n_features, H_init, out_dtype, _fit, return_errors)
                 _note_once(('csr-group',), "KLdivNMF: CSR input runs on one device (%d), not over the row shards of devices %s "
-                           "(groups hold dense problems only)\n" % (self.device, list(self.devices)))
+                           "(fewer than CSR_SHARD_MIN_NNZ = %d stored entries per shard)\n"
+                           % (self.device, list(self.devices), CSR_SHARD_MIN_NNZ))
             elif host_blocks is not None:
                 plan = shard_plan(n_samples, self.devices)
                 if len(plan) > 1:
@@ -374,24 +405,42 @@ class KLdivNMF(object):
         arithmetic is the one the global shape picks; V is stored with one factor from the global maximum; W comes back in
         row order, `components_`, the loss record and `last_fp8_report` from shard 0 (identical on every shard)."""
         k = self.n_components
-        max_iter = int(self.max_iter)
         prec = resolve_precision(self.precision, n_samples, n_features, k)
         vmax = 0.0
         for b, c in zip(blocks, coefs):
             if b.size:
                 vmax = max(vmax, float(c) * float(np.max(b)))
+
+        def load(ctx, r0, r1):
+            ctx.set_problem(r1 - r0, n_features, k, int(self.max_iter))
+            ctx.set_v_max(vmax)
+            col = 0
+            for b, c in zip(blocks, coefs):
+                ctx.upload_V(b[r0:r1], row0=0, col0=col, scale=c)
+                col += b.shape[1]
+        return self._run_group(plan, prec, load, n_samples, n_features, H_init, out_dtype, _fit, return_errors)
+
+    def _fit_group_csr(self, plan, X, n_samples, n_features, H_init, out_dtype, _fit, return_errors):
+        """`_fit_group` for CSR input (`csr_shard_plan`): each context holds the CSR rows of its shard (klnmf_set_problem_sparse,
+        the CSC order built on its device), in the arithmetic `sparse_precision` names -- the same as one context's."""
+        k = self.n_components
+        prec = sparse_precision(self.precision)
+
+        def load(ctx, r0, r1):
+            ctx.set_problem_sparse(X[r0:r1], k, int(self.max_iter))
+        return self._run_group(plan, prec, load, n_samples, n_features, H_init, out_dtype, _fit, return_errors)
+
+    def _run_group(self, plan, prec, load, n_samples, n_features, H_init, out_dtype, _fit, return_errors):
+        """The group loop of `_fit_group` / `_fit_group_csr`: `load(ctx, row0, row1)` sets a shard's problem and data."""
+        k = self.n_components
+        max_iter = int(self.max_iter)
         H_loop = H_init if (_fit or self.components_ is H_init) else self.components_
         ctxs, group = [], None
         try:
             for dev, (r0, r1) in plan:
                 ctx = _native.Context(precision=prec, device=dev, pooled=True)
                 ctxs.append(ctx)
-                ctx.set_problem(r1 - r0, n_features, k, max_iter)
-                ctx.set_v_max(vmax)
-                col = 0
-                for b, c in zip(blocks, coefs):
-                    ctx.upload_V(b[r0:r1], row0=0, col0=col, scale=c)
-                    col += b.shape[1]
+                load(ctx, r0, r1)
                 ctx.set_H(H_init)
                 ctx.init_W()                       # W0 = X . H_init^T (nmf.py:156), this shard's rows
                 if H_loop is not H_init:
