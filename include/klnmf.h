@@ -383,6 +383,16 @@ int klnmf_all_distances_device(int device, int dtype, int metric, int64_t na, in
  *                            problem is dense */
 #define KLNMF_Q_SP_COL_BLOCKS     14
 #define KLNMF_Q_SP_ROW_BLOCKS     15
+/* The dense kernel routes a problem given by klnmf_set_problem runs on in KLNMF_PREC_F64 / F32 / BF16X3 / F16X3 (csrc/exact.hip.h;
+ * 0 for a 16-bit-mode problem, a CSR problem or no problem):
+ *   KLNMF_Q_EX_ROW_CHUNKS    row chunks of the H numerator W^T.Q (its slabs);  KLNMF_Q_EX_W_CHUNKS  feature chunks of the W rule's
+ *                            Q.H^T (1: one piece);  KLNMF_Q_EX_H_SEGMENTS  segments per dictionary row of the H rule (1: one block
+ *                            per row);  KLNMF_Q_EX_H_FROM_SLABS  1: a single-context klnmf_run applies the H rule straight from the
+ *                            row chunks' slabs (k_update_H_slabs), 0: from their sum (the step API and the loop in pieces always) */
+#define KLNMF_Q_EX_ROW_CHUNKS     16
+#define KLNMF_Q_EX_W_CHUNKS       17
+#define KLNMF_Q_EX_H_SEGMENTS     18
+#define KLNMF_Q_EX_H_FROM_SLABS   19
 int klnmf_query(klnmf_ctx *ctx, int what, int64_t *value);
 /*   KLNMF_QF_SUM_V  the sum of the uploaded V as stored (16-bit modes; 0 in the exact modes), in the data's own units */
 #define KLNMF_QF_SUM_V            0

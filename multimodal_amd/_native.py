@@ -252,6 +252,7 @@ Q_NO_NUM_EPS = 9
 Q_MON_CHECKS, Q_MON_TRIPS, Q_MON_GAVE_UP = 10, 11, 12
 Q_FP8_POLL_DUE = 13
 Q_SP_COL_BLOCKS, Q_SP_ROW_BLOCKS = 14, 15
+Q_EX_ROW_CHUNKS, Q_EX_W_CHUNKS, Q_EX_H_SEGMENTS, Q_EX_H_FROM_SLABS = 16, 17, 18, 19
 QF_SUM_V, QF_NNZ_V, QF_MON_STAT, QF_MON_THRESHOLD = 0, 1, 2, 3
 QF_KL_OVER_SUM_V = 9
 
@@ -679,6 +680,12 @@ class Context(object):
         """(column blocks, row blocks) of the CSR kernels this problem runs on; (0, 0): the unblocked kernels, or a dense
         problem (KLNMF_Q_SP_COL_BLOCKS / KLNMF_Q_SP_ROW_BLOCKS)."""
         return self.query(Q_SP_COL_BLOCKS), self.query(Q_SP_ROW_BLOCKS)
+
+    def exact_regime(self):
+        """(row chunks, W chunks, H segments, from slabs) of the dense exact-mode kernels this problem runs on; all 0: a CSR
+        problem, a 16-bit-mode problem or none (KLNMF_Q_EX_ROW_CHUNKS / _W_CHUNKS / _H_SEGMENTS / _H_FROM_SLABS)."""
+        return (self.query(Q_EX_ROW_CHUNKS), self.query(Q_EX_W_CHUNKS), self.query(Q_EX_H_SEGMENTS),
+                self.query(Q_EX_H_FROM_SLABS))
 
     def query_f64(self, what):
         v = _c.c_double(0.0)

@@ -328,7 +328,7 @@ int klnmf_set_problem(klnmf_ctx *c, int64_t n, int64_t f, int64_t k, int64_t cap
                 return s;
             };
             c->n_tt = 4;
-            int64_t s = n_split(c->n_tt);
+            int64_t s = c->sw.ex_rc > 0 ? (int64_t)c->sw.ex_rc : n_split(c->n_tt);      // (KLNMF_EX_ROW_CHUNKS: ctx.hip.h)
             int64_t chunk = (n + s - 1) / s;
             chunk = (chunk + GK - 1) / GK * GK;
             s = (n + chunk - 1) / chunk;
@@ -337,6 +337,10 @@ int klnmf_set_problem(klnmf_ctx *c, int64_t n, int64_t f, int64_t k, int64_t cap
             c->Npart = c->dalloc((size_t)s * k * f * es);
             c->hseg = 4096;          // dictionary rows of 16 384 columns and more: the H rule in segments (exact_H)
             c->hseg_n = f >= 16384 ? (int)((f + c->hseg - 1) / c->hseg) : 1;
+            if (c->sw.ex_hseg > 0) {                    // (KLNMF_EX_H_SEG)
+                c->hseg = c->sw.ex_hseg;
+                c->hseg_n = f > c->hseg ? (int)((f + c->hseg - 1) / c->hseg) : 1;
+            }
             c->hpart = c->hseg_n > 1 ? (double *)c->dalloc(sizeof(double) * (size_t)k * c->hseg_n) : nullptr;
             c->numer = c->dalloc((size_t)k * f * es);
             // W rule: n*k/4096 output tiles, each contracting over all of f.  With fewer tiles than CUs split f so that
@@ -350,6 +354,7 @@ int klnmf_set_problem(klnmf_ctx *c, int64_t n, int64_t f, int64_t k, int64_t cap
                 c->w_tt = 4;
                 int64_t ws = w_split(c->w_tt);
                 ws = std::min<int64_t>(ws, (f + 4 * GK - 1) / (4 * GK));
+                if (c->sw.ex_wc > 0) ws = c->sw.ex_wc;      // (KLNMF_EX_W_CHUNKS)
                 while (ws > 1 && ws * n * k * (int64_t)es > ((int64_t)256 << 20)) --ws;
                 int64_t wch = (f + ws - 1) / ws;
                 wch = (wch + GK - 1) / GK * GK;

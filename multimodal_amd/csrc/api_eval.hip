@@ -191,6 +191,10 @@ int klnmf_query(klnmf_ctx *c, int what, int64_t *value) {
             case KLNMF_Q_FP8_POLL_DUE: *value = (c->have_problem && fp8_poll_due(c)) ? 1 : 0; break;
             case KLNMF_Q_SP_COL_BLOCKS: *value = (c->have_problem && c->sparse && c->sp_blocked) ? c->sp_cb : 0; break;
             case KLNMF_Q_SP_ROW_BLOCKS: *value = (c->have_problem && c->sparse && c->sp_blocked) ? c->sp_rb : 0; break;
+            case KLNMF_Q_EX_ROW_CHUNKS: *value = (c->have_problem && c->is_exact() && !c->sparse) ? c->nsplit : 0; break;
+            case KLNMF_Q_EX_W_CHUNKS: *value = (c->have_problem && c->is_exact() && !c->sparse) ? c->wsplit : 0; break;
+            case KLNMF_Q_EX_H_SEGMENTS: *value = (c->have_problem && c->is_exact() && !c->sparse) ? c->hseg_n : 0; break;
+            case KLNMF_Q_EX_H_FROM_SLABS: *value = (c->have_problem && c->is_exact() && h_from_slabs(c)) ? 1 : 0; break;
             case KLNMF_Q_COMM_RANKS: {
                 int cnt = 1;
                 if (c->comm) RCCLCHK(rccl().CommCount(c->comm, &cnt));

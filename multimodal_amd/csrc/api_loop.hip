@@ -780,7 +780,7 @@ void piece_fit_tail(klnmf_ctx *c) {
         // the H rule sums the row chunks' slabs itself where that is a few thousand loads per row (the reference's own data
         // scale: one launch less of 7); beyond, one block per row walking the slabs is slower than the wide sum kernel
         // (1000 x 2000, k = 50, 16 slabs: 97 vs 73 us per iteration)
-        const bool slabs = !c->sparse && c->hseg_n == 1 && (int64_t)c->nsplit * c->f <= 8192;
+        const bool slabs = h_from_slabs(c);
         EXACT_CALL(c, exact_N, c->cur ^ 1, !slabs);
         EXACT_CALL(c, exact_H, slabs);
         return;

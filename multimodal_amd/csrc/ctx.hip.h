@@ -185,6 +185,12 @@ struct DevSwitches {
     bool comm_overlap = true;   // KLNMF_COMM_OVERLAP=0: the parts' all-reduces on the loop's own stream
     bool comm_single = false;   // KLNMF_COMM_SINGLE=1: a one-rank communicator takes the collective path (tests)
     int sp_cb = 0, sp_rb = 0;   // KLNMF_SP_CB / KLNMF_SP_RB: column / row blocks of the CSR kernels (sparseb.hip.h; 0: by the L2's size)
+    // dense problems of the exact modes (klnmf_set_problem; 0: the size rules).  KLNMF_EX_ROW_CHUNKS / KLNMF_EX_W_CHUNKS = N: the H
+    // numerator's row chunks / the W rule's feature chunks computed from N instead of the CU count (each chunk still rounded up to
+    // GK, so the count may come out below N; 1: the one-piece W rule); KLNMF_EX_H_SEG = L: the H rule in segments of L columns
+    // at any f > L.  Buffers are sized for what these force; klnmf_query (KLNMF_Q_EX_*) reports the effective values.
+    int ex_rc = 0, ex_wc = 0;
+    int64_t ex_hseg = 0;
     int graph = 0;              // KLNMF_GRAPH=1: two iterations captured into a hipGraph and replayed (measured: no gain)
     static DevSwitches read() {
         DevSwitches d;
@@ -208,6 +214,9 @@ struct DevSwitches {
         d.graph = num("KLNMF_GRAPH", 0);
         d.sp_cb = num("KLNMF_SP_CB", 0);
         d.sp_rb = num("KLNMF_SP_RB", 0);
+        d.ex_rc = std::max(0, num("KLNMF_EX_ROW_CHUNKS", 0));
+        d.ex_wc = std::max(0, num("KLNMF_EX_W_CHUNKS", 0));
+        d.ex_hseg = std::max(0, num("KLNMF_EX_H_SEG", 0));
         return d;
     }
 };
@@ -460,6 +469,12 @@ inline void comm_release(klnmf_ctx *c) {
 inline void need_problem(klnmf_ctx *c) {
     use(c);
     if (!c->have_problem) fail(KLNMF_ERR_ARG, "klnmf_set_problem has not been called");
+}
+
+// A single-context fit loop (piece_fit_tail) applies the H rule straight from the row chunks' slabs (k_update_H_slabs) where that
+// is a few thousand loads per row; beyond, and in segments, the slabs are summed first (k_sum_partials).  KLNMF_Q_EX_H_FROM_SLABS.
+inline bool h_from_slabs(const klnmf_ctx *c) {
+    return !c->sparse && c->hseg_n == 1 && (int64_t)c->nsplit * c->f <= 8192;
 }
 
 inline EventPair begin_event(klnmf_ctx *c, std::vector<EventPair> &v) {
