@@ -1,4 +1,4 @@
-// libklnmf.so, unit 3 of 4: row shards over the GPUs of a node -- the RCCL entry points (opened at run time), the loop entry every
+// libklnmf.so, unit 3 of 5: row shards over the GPUs of a node -- the RCCL entry points (opened at run time), the loop entry every
 // rank agrees on, the iteration with its ONE grouped all-reduce, and the exchange buffers of the torch path (ctx.hip.h lists the units).
 #include "ctx.hip.h"
 
@@ -113,9 +113,7 @@ void comm_iteration(klnmf_ctx *c, int fit, double tol_abs) {
         LossArgs lt = kNoLoss;
         lt.tol_abs = tol_abs;
         launch_post(c, POST_RULE, parts, P, lt, true, false, false);
-        c->cur ^= 1;
-        c->iter_in_loop += 1;
-        poll_fp8_overflow(c, true);
+        loop_advance(c, true, true);
         return;
     }
     const size_t ncount = c->is_exact() ? (size_t)(c->k * c->f) : (size_t)c->k * (size_t)c->f_pad;
@@ -130,9 +128,7 @@ void comm_iteration(klnmf_ctx *c, int fit, double tol_abs) {
     RCCLCHK(ra); RCCLCHK(rb); RCCLCHK(rc);
     piece_decide(c, tol_abs);                  // identical inputs on every rank -> identical decisions
     if (fit) piece_update_H(c);
-    c->cur ^= 1;
-    c->iter_in_loop += 1;
-    if (fit) poll_fp8_overflow(c, !c->is_exact());
+    loop_advance(c, fit != 0, true);          // (here a fit is in an exact mode: nothing to poll, whatever `agreed`)
 }
 
 }  // namespace klnmf_host
@@ -202,27 +198,12 @@ int klnmf_run_sharded(klnmf_ctx *c, int64_t n_total, int64_t max_iter, int fit, 
             check_v_overflow(c);
             begin_fp8_loop(c);
         }
-        reset_state(c);
-        c->loop_start_cur = c->cur;
-        c->loop_hswaps = 0; c->loop_h0 = c->H32; c->loop_h1 = c->H32alt;
+        loop_open(c);
         const double tol_abs = tol * (double)n_total * (double)c->f;          // nmf.py:207 on the GLOBAL shape
         for (int64_t it = 0; it < max_iter; ++it) {
-            if (multi) {
-                comm_iteration(c, fit, tol_abs);
-            } else {
-                // one rank: the stop decision rides in the loss kernel, as in klnmf_run (one launch less per iteration)
-                piece_rowpass(c, fit, &tol_abs);
-                if (fit) piece_fit_tail(c);
-                c->cur ^= 1;
-                c->iter_in_loop += 1;
-                if (fit) poll_fp8_overflow(c);
-            }
-            if (tol_abs > 0 && (it & 15) == 15) {
-                DevState hs{};
-                HIPCHK(hipMemcpyAsync(&hs, c->st, sizeof(DevState), hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipStreamSynchronize(c->stream));
-                if (hs.stop) break;
-            }
+            if (multi) comm_iteration(c, fit, tol_abs);
+            else local_iteration(c, fit, tol_abs);      // one rank: klnmf_run's loop with the global tolerance
+            if (tol_abs > 0 && (it & 15) == 15 && stop_fired(c)) break;
         }
         fetch_results(c, errors_out, n_done, stopped);
     });

@@ -1,4 +1,4 @@
-// libklnmf.so, unit 1 of 4: contexts, problems, uploads and downloads (ctx.hip.h lists the units).
+// libklnmf.so, unit 1 of 5: contexts, problems, uploads and downloads (ctx.hip.h lists the units).
 #include "ctx.hip.h"
 #include "csc.hip.h"
 
@@ -505,6 +505,8 @@ int klnmf_set_problem(klnmf_ctx *c, int64_t n, int64_t f, int64_t k, int64_t cap
             // Column-split update pass: with fewer than half as many 8-wave workgroups as CUs (n < ~32 000 rows; the
             // reference's own data sets have 10^2..10^3) split every row block's columns over blockIdx.y so that the grid
             // fills the chip once.  KLNMF_ROW_SPLIT = 0 / N (development switch) forces it off / to N chunks.
+            // (row_chunks and tail_wg below: only under !big -- the column-split kernels exist for the 8-wave workgroups alone,
+            // and fast_rowpass refuses a big problem that carries either)
             c->row_chunks = 1;
             c->row_ct_chunk = c->nct;
             if (!c->big && !c->q8_ok) {

@@ -302,19 +302,12 @@ int klnmf_group_run(klnmf_group *g, int64_t n_total, int64_t max_iter, int fit, 
                 klnmf_ctx *c = g->ctxs[r];
                 piece_decide(c, tol_abs);              // identical inputs on every member -> identical decisions
                 if (fit) piece_update_H(c);
-                c->cur ^= 1;                           // klnmf_iter_advance
-                c->loop_iters += 1;
-                c->iter_in_loop += 1;
-                if (!c->is_exact()) poll_fp8_overflow(c, true);
+                loop_advance(c, true, true);           // (as klnmf_iter_advance)
             });
             g->enqueue_ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
             if (tol_abs > 0 && (it & 15) == 15) {
-                klnmf_ctx *c = g->ctxs[0];
-                DevState hs{};
-                HIPCHK(hipSetDevice(c->device));
-                HIPCHK(hipMemcpyAsync(&hs, c->st, sizeof(DevState), hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipStreamSynchronize(c->stream));
-                if (hs.stop) break;
+                HIPCHK(hipSetDevice(g->ctxs[0]->device));
+                if (stop_fired(g->ctxs[0])) break;
             }
         }
         // results: every member's; shard 0's are reported, and every replica must agree with them bit for bit

@@ -1,102 +1,35 @@
-// libklnmf.so, unit 2 of 4: the loop of nmf.py:212-222 -- kernel dispatch, the pieces of an iteration, the stop rule's bookkeeping,
-// the fp8 regime with its monitor, and the entry points that run loops and single steps (ctx.hip.h lists the units).
+// libklnmf.so, unit 2 of 5: the loop of nmf.py:212-222 -- kernel dispatch, the pieces of an iteration, the stop rule's bookkeeping,
+// the fp8 regime with its monitor, the loop driver, and the entry points that run loops and single steps (ctx.hip.h lists the units).
 #include "ctx.hip.h"
 
 namespace klnmf_host {
 namespace {
 
 // ---------------------------------------------------------------- dispatch ---
-template <int MODE>
-void launch_rowpass4_kt(klnmf_ctx *c, const RowPass4Args &a, int grid_x, int grid_y = 1) {
-    const dim3 grid(grid_x, grid_y);
-    const int odd = 2 * c->KT - c->ks;
-    const bool ep = c->kc >= 0;
-    const bool ne = MODE == ROW_UPDATE && c->ne_loop && !c->big && c->q8() && a.base.Qt != nullptr;      // (NE kernels: Q8 = 2)
-    if (MODE == ROW_UPDATE) c->last_row_ne = ne;
-#define KL_ROW4_CASE(KTV)                                                                                       \
-    case KTV:                                                                                                   \
-        if constexpr (MODE == ROW_UPDATE) {                                                                     \
-            if (grid_y > 1 && c->q8() && a.base.Qt) {      /* column-split pass leaving fp8 ratio tiles */      \
-                if (ne) {      /* ... and the ratio without the numerator's eps */                              \
-                    if (ep) {                                                                                   \
-                        if (odd) hipLaunchKernelGGL((k_rowpass4<KTV, 1, MODE, 1, 8, 1, 2>), grid, dim3(kThreads4), 0, c->stream, a);  \
-                        else hipLaunchKernelGGL((k_rowpass4<KTV, 0, MODE, 1, 8, 1, 2>), grid, dim3(kThreads4), 0, c->stream, a);      \
-                    } else {                                                                                    \
-                        if (odd) hipLaunchKernelGGL((k_rowpass4<KTV, 1, MODE, 0, 8, 1, 2>), grid, dim3(kThreads4), 0, c->stream, a);  \
-                        else hipLaunchKernelGGL((k_rowpass4<KTV, 0, MODE, 0, 8, 1, 2>), grid, dim3(kThreads4), 0, c->stream, a);      \
-                    }                                                                                           \
-                    break;                                                                                      \
-                }                                                                                               \
-                if (ep) {                                                                                       \
-                    if (odd) hipLaunchKernelGGL((k_rowpass4<KTV, 1, MODE, 1, 8, 1, 1>), grid, dim3(kThreads4), 0, c->stream, a);  \
-                    else hipLaunchKernelGGL((k_rowpass4<KTV, 0, MODE, 1, 8, 1, 1>), grid, dim3(kThreads4), 0, c->stream, a);      \
-                } else {                                                                                        \
-                    if (odd) hipLaunchKernelGGL((k_rowpass4<KTV, 1, MODE, 0, 8, 1, 1>), grid, dim3(kThreads4), 0, c->stream, a);  \
-                    else hipLaunchKernelGGL((k_rowpass4<KTV, 0, MODE, 0, 8, 1, 1>), grid, dim3(kThreads4), 0, c->stream, a);      \
-                }                                                                                               \
-                break;                                                                                          \
-            }                                                                                                   \
-            if (grid_y > 1) {         /* column-split pass: its own instantiations (SPLIT = 1) */               \
-                if (ep) {                                                                                       \
-                    if (odd) hipLaunchKernelGGL((k_rowpass4<KTV, 1, MODE, 1, 8, 1>), grid, dim3(kThreads4), 0, c->stream, a);  \
-                    else hipLaunchKernelGGL((k_rowpass4<KTV, 0, MODE, 1, 8, 1>), grid, dim3(kThreads4), 0, c->stream, a);      \
-                } else {                                                                                        \
-                    if (odd) hipLaunchKernelGGL((k_rowpass4<KTV, 1, MODE, 0, 8, 1>), grid, dim3(kThreads4), 0, c->stream, a);  \
-                    else hipLaunchKernelGGL((k_rowpass4<KTV, 0, MODE, 0, 8, 1>), grid, dim3(kThreads4), 0, c->stream, a);      \
-                }                                                                                               \
-                break;                                                                                          \
-            }                                                                                                   \
-        }                                                                                                       \
-        if constexpr (MODE == ROW_UPDATE) {                                                                     \
-            if (c->q8() && a.base.Qt) {     /* fp8 ratio tiles for the column pass */                             \
-                if (ne) {                                                                                       \
-                    if (ep) {                                                                                   \
-                        if (odd) hipLaunchKernelGGL((k_rowpass4<KTV, 1, MODE, 1, 8, 0, 2>), grid, dim3(kThreads4), 0, c->stream, a);  \
-                        else hipLaunchKernelGGL((k_rowpass4<KTV, 0, MODE, 1, 8, 0, 2>), grid, dim3(kThreads4), 0, c->stream, a);      \
-                    } else {                                                                                    \
-                        if (odd) hipLaunchKernelGGL((k_rowpass4<KTV, 1, MODE, 0, 8, 0, 2>), grid, dim3(kThreads4), 0, c->stream, a);  \
-                        else hipLaunchKernelGGL((k_rowpass4<KTV, 0, MODE, 0, 8, 0, 2>), grid, dim3(kThreads4), 0, c->stream, a);      \
-                    }                                                                                           \
-                    break;                                                                                      \
-                }                                                                                               \
-                if (ep) {                                                                                       \
-                    if (odd) hipLaunchKernelGGL((k_rowpass4<KTV, 1, MODE, 1, 8, 0, 1>), grid, dim3(kThreads4), 0, c->stream, a);  \
-                    else hipLaunchKernelGGL((k_rowpass4<KTV, 0, MODE, 1, 8, 0, 1>), grid, dim3(kThreads4), 0, c->stream, a);      \
-                } else {                                                                                        \
-                    if (odd) hipLaunchKernelGGL((k_rowpass4<KTV, 1, MODE, 0, 8, 0, 1>), grid, dim3(kThreads4), 0, c->stream, a);  \
-                    else hipLaunchKernelGGL((k_rowpass4<KTV, 0, MODE, 0, 8, 0, 1>), grid, dim3(kThreads4), 0, c->stream, a);      \
-                }                                                                                               \
-                break;                                                                                          \
-            }                                                                                                   \
-        }                                                                                                       \
-        if (ep) {                                                                                               \
-            if (odd) hipLaunchKernelGGL((k_rowpass4<KTV, 1, MODE, 1>), grid, dim3(kThreads4), 0, c->stream, a);  \
-            else hipLaunchKernelGGL((k_rowpass4<KTV, 0, MODE, 1>), grid, dim3(kThreads4), 0, c->stream, a);      \
-        } else {                                                                                                \
-            if (odd) hipLaunchKernelGGL((k_rowpass4<KTV, 1, MODE, 0>), grid, dim3(kThreads4), 0, c->stream, a);  \
-            else hipLaunchKernelGGL((k_rowpass4<KTV, 0, MODE, 0>), grid, dim3(kThreads4), 0, c->stream, a);      \
-        }                                                                                                       \
-        break;
-#define KL_ROW4_BIG(KTV)                                                                                        \
-    case KTV:                                                                                                   \
-        if constexpr (MODE == ROW_UPDATE) {                                                                     \
-            if (c->q8() && a.base.Qt) {     /* FUSED order leaving fp8 ratio tiles */                           \
-                if (ep) hipLaunchKernelGGL((k_rowpass4<KTV, 0, MODE, 1, 4, 0, 1>), grid, dim3(256), 0, c->stream, a);   \
-                else hipLaunchKernelGGL((k_rowpass4<KTV, 0, MODE, 0, 4, 0, 1>), grid, dim3(256), 0, c->stream, a);      \
-                break;                                                                                          \
-            }                                                                                                   \
-        }                                                                                                       \
-        if (ep) hipLaunchKernelGGL((k_rowpass4<KTV, 0, MODE, 1, 4>), grid, dim3(256), 0, c->stream, a);   \
-        else hipLaunchKernelGGL((k_rowpass4<KTV, 0, MODE, 0, 4>), grid, dim3(256), 0, c->stream, a);      \
-        break;
-    switch (c->KT) {
-        KL_ROW4_CASE(1) KL_ROW4_CASE(2) KL_ROW4_CASE(3) KL_ROW4_CASE(4)
-        KL_ROW4_CASE(5) KL_ROW4_CASE(6) KL_ROW4_CASE(7)
-        KL_ROW4_BIG(8) KL_ROW4_BIG(10) KL_ROW4_BIG(12) KL_ROW4_BIG(14) KL_ROW4_BIG(16)
-        default: fail(KLNMF_ERR_UNSUPP, "ping-pong row pass: 224 < k <= 256 runs on the generation-1 kernel");
-    }
-#undef KL_ROW4_BIG
-#undef KL_ROW4_CASE
+// Which instantiation a row pass takes (the one place that derives it; rowpass4_list.hip.h has the kernels and their index).
+// `tiles`: the pass leaves ratio tiles for the column pass; grid_y > 1: the column-split pass (8-wave update kernels only:
+// fast_rowpass refuses it for big).  NE kernels (Q8 = 2): see begin_fp8_loop.
+RowPass4Key rowpass4_key(const klnmf_ctx *c, int mode, bool tiles, int grid_y) {
+    const bool upd = mode == ROW_UPDATE;
+    const bool q8 = upd && c->q8() && tiles;
+    const bool ne = q8 && c->ne_loop && !c->big;
+    return RowPass4Key{c->KT, 2 * c->KT - c->ks, mode, c->kc >= 0 ? 1 : 0, c->big ? 4 : kWaves4, (upd && grid_y > 1) ? 1 : 0,
+                       q8 ? (ne ? 2 : 1) : 0};
+}
+
+void launch_rowpass4_kt(klnmf_ctx *c, int mode, const RowPass4Args &a, int grid_x, int grid_y = 1) {
+    struct Table {
+        void (*slot[kRowPass4Count])(RowPass4Args) = {};
+        Table() { KL_RP4_LIST_1(KL_RP4_SLOT) KL_RP4_LIST_2(KL_RP4_SLOT) KL_RP4_LIST_3(KL_RP4_SLOT) }
+    };
+    static const Table table;
+    const RowPass4Key key = rowpass4_key(c, mode, a.base.Qt != nullptr, grid_y);
+    if (mode == ROW_UPDATE) c->last_row_ne = key.q8 == 2;
+    const int idx = rowpass4_index(key);
+    if (idx < 0) fail(KLNMF_ERR_UNSUPP, "ping-pong row pass: 224 < k <= 256 runs on the generation-1 kernel");
+    // (the lists cover the index, proved at compile time: an empty slot cannot be met -- and is never launched)
+    if (!table.slot[idx]) fail(KLNMF_ERR_UNSUPP, "ping-pong row pass: no kernel in slot " + std::to_string(idx));
+    hipLaunchKernelGGL(table.slot[idx], dim3(grid_x, grid_y), dim3(64 * key.nw), 0, c->stream, a);
     HIPCHK(hipGetLastError());
 }
 
@@ -105,6 +38,8 @@ void launch_rowpass4_kt(klnmf_ctx *c, const RowPass4Args &a, int grid_x, int gri
 int w8_probe_col(const klnmf_ctx *c) { return (c->KP - 1 >= c->k && c->KP - 1 != c->kc) ? c->KP - 1 : -1; }
 
 void fast_rowpass(klnmf_ctx *c, int mode, int store_q = 0) {
+    // (klnmf_set_problem never chooses either for big: the 4-wave kernels have no column-split form)
+    if (c->big && (c->row_chunks > 1 || c->tail_wg > 0)) fail(KLNMF_ERR_UNSUPP, "ping-pong row pass: no column-split pass for 224 < k <= 512");
     RowPassArgs a{};
     a.VtA = c->VtA;
     a.Qt = (store_q && mode == ROW_UPDATE) ? c->Qt : nullptr;
@@ -134,7 +69,7 @@ void fast_rowpass(klnmf_ctx *c, int mode, int store_q = 0) {
     if (mode == ROW_UPDATE && c->row_chunks > 1) {     // few rows: column chunks in blockIdx.y, W rule from the slabs
         a4.base.gpart = c->Gpart;
         a4.base.ct_chunk = c->row_ct_chunk;
-        launch_rowpass4_kt<ROW_UPDATE>(c, a4, grid4, c->row_chunks);
+        launch_rowpass4_kt(c, ROW_UPDATE, a4, grid4, c->row_chunks);
         const int64_t rows = (int64_t)c->nrt * 32;
         hipLaunchKernelGGL(k_wrule_slabs, dim3(grid_for(rows * (c->KP / 4))), dim3(256), 0, c->stream,
                            (const float *)c->Gpart, c->row_chunks, rows * c->KP, (const float *)c->W32[c->cur],
@@ -148,7 +83,7 @@ void fast_rowpass(klnmf_ctx *c, int mode, int store_q = 0) {
         // hybrid: the full rounds of workgroups take whole rows; the last partial round (tail_wg < CUs workgroups
         // that would each run a whole row block's length on an otherwise idle chip) is split into column chunks
         // and its W rule applied from the slabs
-        launch_rowpass4_kt<ROW_UPDATE>(c, a4, grid4 - c->tail_wg);
+        launch_rowpass4_kt(c, ROW_UPDATE, a4, grid4 - c->tail_wg);
         EventPair evt{};
         if (c->prof_now) evt = begin_event(c, c->ev_tail);
         RowPass4Args t4 = a4;
@@ -156,7 +91,7 @@ void fast_rowpass(klnmf_ctx *c, int mode, int store_q = 0) {
         t4.base.rt0 = c->tail_rt0();
         t4.base.gpart = c->Gpart;
         t4.base.ct_chunk = c->tail_ct_chunk;
-        launch_rowpass4_kt<ROW_UPDATE>(c, t4, c->tail_wg, c->tail_chunks);
+        launch_rowpass4_kt(c, ROW_UPDATE, t4, c->tail_wg, c->tail_chunks);
         const int64_t row0 = (int64_t)t4.base.rt0 * 32, rows = (int64_t)(c->nrt - t4.base.rt0) * 32;
         hipLaunchKernelGGL(k_wrule_slabs, dim3(grid_for(rows * (c->KP / 4))), dim3(256), 0, c->stream,
                            (const float *)c->Gpart, c->tail_chunks, rows * c->KP,
@@ -167,11 +102,7 @@ void fast_rowpass(klnmf_ctx *c, int mode, int store_q = 0) {
         if (c->prof_now) { HIPCHK(hipEventRecord(evt.b, c->stream)); HIPCHK(hipEventRecord(ev.b, c->stream)); }
         return;
     }
-    switch (mode) {
-        case ROW_UPDATE: launch_rowpass4_kt<ROW_UPDATE>(c, a4, grid4); break;
-        case ROW_INIT: launch_rowpass4_kt<ROW_INIT>(c, a4, grid4); break;
-        default: launch_rowpass4_kt<ROW_LOSS>(c, a4, grid4); break;
-    }
+    launch_rowpass4_kt(c, mode, a4, grid4);
     if (c->prof_now) HIPCHK(hipEventRecord(ev.b, c->stream));
 }
 
@@ -201,11 +132,6 @@ ColPassQArgs colq_part_args(klnmf_ctx *c, const klnmf_ctx::PartCfg &p) {
 // errors.  Every check is followed by a poll (poll_fp8_overflow) -- a host synchronisation, i.e. a pipeline bubble of some
 // 50 us: at the cadence of round 5's first monitor (every 8th) that was 3 % of configuration 2's 0.2 ms iterations.
 bool monitor_due(int64_t n8) { return n8 == 1 || n8 == 2 || n8 == 4 || n8 == 8 || n8 == 16 || (n8 >= 32 && (n8 & 31) == 0); }
-
-
-
-
-
 
 // ------------------------------------------------------------ exact pieces ---
 // CSR input: ratio on the stored entries + loss (nmf.py:301-308, 331-334)
@@ -459,7 +385,7 @@ void exact_H(klnmf_ctx *c, bool from_slabs = false) {
 void launch_monitor(klnmf_ctx *c, bool use8) {
     c->mon_pending = false;
     c->mon_dry_pending = false;
-    if (!c->mon_part || !c->sw.q8_monitor || !c->q8_loop || c->in_capture) return;
+    if (!c->mon_part || !c->sw.q8_monitor || !c->q8_loop) return;
     const bool dry = c->iter_in_loop == 1 && !c->q8();
     if (!dry && !(c->q8() && monitor_due(c->stat_q8_tiles))) return;
     MonArgs a{};
@@ -637,7 +563,7 @@ void launch_post(klnmf_ctx *c, PostMode mode, const klnmf_ctx::PartCfg *parts, i
 // torch-sequenced loop exchanges loss_xchg[1] only then, BEHIND the column pass's k_post (distributed.py) -- every rank holds
 // the same loop state, so every rank answers alike.
 bool fp8_poll_due(const klnmf_ctx *c) {
-    if (c->is_exact() || !c->q8_loop || c->in_capture) return false;
+    if (c->is_exact() || !c->q8_loop) return false;
     if (c->mon_dry_pending) return true;
     const bool q8_then = c->iter_in_loop + 1 >= 2 && (!c->big || (c->W8 != nullptr && c->w8_meas));      // q8() after the advance
     return q8_then && monitor_due(c->stat_q8_tiles);
@@ -664,9 +590,9 @@ void poll_resolve(klnmf_ctx *c) {
     if (c->q8_loop) poll_verdict(c, c->poll_agreed);
 }
 
-void poll_fp8_overflow(klnmf_ctx *c, bool agreed) {
+static void poll_fp8_overflow(klnmf_ctx *c, bool agreed) {
     poll_resolve(c);
-    if (!c->q8_loop || c->in_capture) return;
+    if (!c->q8_loop) return;
     const bool dry = c->mon_dry_pending;          // the dry run of the iteration just enqueued decides whether the next one takes fp8 tiles
     c->mon_dry_pending = false;
     if (!dry && !(c->q8() && monitor_due(c->stat_q8_tiles))) return;
@@ -686,7 +612,6 @@ void poll_fp8_overflow(klnmf_ctx *c, bool agreed) {
     c->poll_inflight = true;
     c->poll_agreed = agreed;
 }
-
 
 // fused_tol != nullptr (klnmf_run): the stop rule rides in the launch that reduces the loss (no k_decide launch)
 void piece_rowpass(klnmf_ctx *c, int fit, const double *fused_tol, bool defer_to_post) {
@@ -830,6 +755,49 @@ void fetch_results(klnmf_ctx *c, double *errors_out, int64_t *n_done, int *stopp
     }
 }
 
+// ---------------------------------------------------------------- the loop driver ---
+// What every loop entry does once its own refusals and fp8 decision are through (check_v_overflow + begin_fp8_loop, comm_loop_entry
+// or the agreed form): empty DevState, and remember where W and the dictionary master stand (fetch_results finds the current
+// ones from n_done).
+void loop_open(klnmf_ctx *c) {
+    reset_state(c);
+    c->loop_start_cur = c->cur;
+    c->loop_hswaps = 0; c->loop_h0 = c->H32; c->loop_h1 = c->H32alt;
+}
+
+// Behind an iteration's last launch: the W ping-pong advances, and the fp8 regime's verdict is polled.  `agreed`: the poll reads
+// loss_xchg[1] as the exchange left it (loops on a communicator, in a group or in pieces) instead of this context's DevState.
+// `poll`: the loops in one call (local_iteration, comm_iteration) poll behind fit iterations only, the loop in pieces and the
+// group behind every iteration, as each always did.  Mostly that is one behaviour: poll_fp8_overflow returns at once when
+// !q8_loop (after poll_resolve, which does nothing with no poll in flight), and begin_fp8_loop leaves q8_loop false in the
+// exact modes; in a transform no update pass stores ratio tiles, so stat_q8_tiles stays 0, monitor_due(0) is false and
+// mon_dry_pending is never set -- a poll there does nothing.  The exception that keeps the parameter: ONE loop continued by
+// klnmf_run_more first with fit = 1, then with fit = 0, carries a non-zero stat_q8_tiles (and possibly a poll in flight) into its
+// transform iterations; an unconditional poll would copy, record and resolve there where `if (fit)` does not.
+void loop_advance(klnmf_ctx *c, bool poll, bool agreed) {
+    c->cur ^= 1;
+    c->iter_in_loop += 1;
+    if (poll) poll_fp8_overflow(c, agreed);
+}
+
+// One iteration of a loop in one context: the stop rule rides in the launch that reduces the loss (every mode), and a fit's
+// loss reduction in k_post behind the column pass -- no launch of their own (a small problem's iteration IS its kernels'
+// latencies: 4-7 launches of a few microseconds each)
+void local_iteration(klnmf_ctx *c, int fit, double tol_abs) {
+    piece_rowpass(c, fit, &tol_abs);
+    if (fit) piece_fit_tail(c);
+    loop_advance(c, fit != 0, false);
+}
+
+// Has the stop rule fired?  (The remaining iterations would be no-ops and need not be enqueued.  One read-back and
+// synchronisation: the loops ask every 16th iteration, and only with a tolerance.)
+bool stop_fired(klnmf_ctx *c) {
+    DevState hs{};
+    HIPCHK(hipMemcpyAsync(&hs, c->st, sizeof(DevState), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return hs.stop != 0;
+}
+
 Refusals read_refusals(klnmf_ctx *c) {
     if (c->is_exact()) return Refusals{};
     if (!c->refusals_dirty) return Refusals{};          // the last check of this state passed (a failing one stays dirty)
@@ -955,10 +923,7 @@ int klnmf_loop_begin(klnmf_ctx *c) {
             check_v_overflow(c);
             begin_fp8_loop(c);
         }
-        reset_state(c);
-        c->loop_start_cur = c->cur;
-        c->loop_hswaps = 0; c->loop_h0 = c->H32; c->loop_h1 = c->H32alt;
-        c->loop_iters = 0;
+        loop_open(c);
     });
 }
 
@@ -976,10 +941,7 @@ int klnmf_loop_begin_agreed(klnmf_ctx *c, double sum_x_all, double cells_all, do
         if (!(sum_x_all >= 0) || !(cells_all > 0)) fail(KLNMF_ERR_ARG, "klnmf_loop_begin_sharded: the all-reduced sums must be given");
         check_v_overflow(c);
         begin_fp8_loop(c, sum_x_all * c->v_scale, cells_all, nnz_all, fp8_shape_all);      // (the caller's sums are in the data's own units)
-        reset_state(c);
-        c->loop_start_cur = c->cur;
-        c->loop_hswaps = 0; c->loop_h0 = c->H32; c->loop_h1 = c->H32alt;
-        c->loop_iters = 0;
+        loop_open(c);
     });
 }
 
@@ -991,20 +953,10 @@ int klnmf_run_more(klnmf_ctx *c, int64_t iters, int fit, double tol_abs) {
         need_problem(c);
         if (iters < 0) fail(KLNMF_ERR_ARG, "iters < 0");
         if (comm_multi(c)) {                   // the loop of klnmf_run_sharded, continued
-            for (int64_t it = 0; it < iters; ++it) {
-                comm_iteration(c, fit, tol_abs);
-                c->loop_iters += 1;
-            }
+            for (int64_t it = 0; it < iters; ++it) comm_iteration(c, fit, tol_abs);
             return;
         }
-        for (int64_t it = 0; it < iters; ++it) {
-            piece_rowpass(c, fit, &tol_abs);      // (every mode: the stop rule rides in the loss reduction's launch)
-            if (fit) piece_fit_tail(c);
-            c->cur ^= 1;
-            c->loop_iters += 1;
-            c->iter_in_loop += 1;
-            if (fit) poll_fp8_overflow(c);
-        }
+        for (int64_t it = 0; it < iters; ++it) local_iteration(c, fit, tol_abs);
     });
 }
 
@@ -1049,12 +1001,9 @@ int klnmf_iter_update_H(klnmf_ctx *c) {
 int klnmf_iter_advance(klnmf_ctx *c) {
     return guarded([&] {
         need_problem(c);
-        c->cur ^= 1;
-        c->loop_iters += 1;
-        c->iter_in_loop += 1;
         // the loop in pieces gives fp8 tiles up after bulk saturation like the loops in one call: the count is read where the
         // caller's exchange left it (loss_xchg[1]: summed over the ranks by the loss all-reduce, this context's own without one)
-        if (!c->is_exact()) poll_fp8_overflow(c, true);
+        loop_advance(c, true, true);
     });
 }
 
@@ -1073,73 +1022,10 @@ int klnmf_run(klnmf_ctx *c, int64_t max_iter, int fit, double tol_abs, double *e
         if (max_iter > c->cap) fail(KLNMF_ERR_ARG, "max_iter exceeds the capacity given to klnmf_set_problem");
         check_v_overflow(c);
         begin_fp8_loop(c);
-        reset_state(c);
-        c->loop_start_cur = c->cur;
-        c->loop_hswaps = 0; c->loop_h0 = c->H32; c->loop_h1 = c->H32alt;
-        // bf16 modes: the stop rule inside the loss kernel -- one launch fewer per iteration (a small problem's
-        // iteration IS its kernel latencies: 7 launches of 4-10 us each).  Summing the column pass's slabs inside the
-        // H rule as well (from_slabs) was measured and is NOT used: its k blocks walk the slabs serially, 47 -> 68 us.
-        auto one_iteration = [&] {
-            piece_rowpass(c, fit, &tol_abs);      // (every mode: the stop rule rides in the loss reduction's launch)
-            if (fit) piece_fit_tail(c);
-            c->cur ^= 1;
-            c->iter_in_loop += 1;
-            if (fit) poll_fp8_overflow(c);
-        };
-        auto stopped_already = [&]() -> bool {        // the stop rule may have fired: the remaining (no-op) iterations need not be enqueued
-            DevState hs{};
-            HIPCHK(hipMemcpyAsync(&hs, c->st, sizeof(DevState), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            return hs.stop != 0;
-        };
-        // Launch-bound problems (the reference's own data: 10^2..10^4 rows, 4-7 kernels of a few microseconds per
-        // iteration): two consecutive iterations -- both positions of the W ping-pong -- captured once into a hipGraph
-        // and replayed.  The first two iterations run eagerly (they may carry the measured image scales of W0 and the
-        // re-pack that follows them).  KLNMF_GRAPH=0 turns it off, =1 forces it for any size.
-        int64_t it = 0;
-        // Measured (scripts/small_problem_timing.py, 200 x 450 .. 10 000 x 4096): 29.5 us per iteration replayed against
-        // 28.3 eager -- the iteration is the kernels' own few microseconds and their dependent boundaries, which a graph
-        // keeps (MI355X_MICROARCH.md: "dependent kernel boundary ... eager = hipGraph"), not host launch cost.  Off unless asked for.
-        // (never on a loop that may take fp8 tiles: a replay would reuse the captured iterations' stochastic-rounding seeds and skip the
-        // monitor's checks and polls -- the premises of the fp8 regime)
-        const bool want_graph = c->stream != nullptr && !c->profiling && max_iter >= 12 && c->sw.graph != 0 && !c->q8_loop;
-        if (want_graph) {
-            for (; it < 2; ++it) one_iteration();
-            hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
-            const int cur_before = c->cur;
-            hipError_t ge = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
-            if (ge == hipSuccess) {
-                c->in_capture = true;
-                try {
-                    one_iteration();
-                    one_iteration();
-                } catch (...) {
-                    c->in_capture = false;
-                    (void)hipStreamEndCapture(c->stream, &graph);
-                    if (graph) (void)hipGraphDestroy(graph);
-                    throw;
-                }
-                c->in_capture = false;
-                ge = hipStreamEndCapture(c->stream, &graph);
-                if (ge == hipSuccess) ge = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-            }
-            c->cur = cur_before;                       // nothing has run yet: the capture only recorded the launches
-            if (ge == hipSuccess && exec) {
-                int64_t replays = 0;
-                for (; it + 2 <= max_iter; it += 2) {
-                    HIPCHK(hipGraphLaunch(exec, c->stream));
-                    if (tol_abs > 0 && (++replays & 7) == 0 && stopped_already()) { it = max_iter; break; }
-                }
-            } else {
-                (void)hipGetLastError();               // capture not available here: the eager loop below does the work
-            }
-            if (exec) (void)hipGraphExecDestroy(exec);
-            if (graph) (void)hipGraphDestroy(graph);
-        }
-        for (; it < max_iter; ++it) {
-            one_iteration();
-            if (tol_abs > 0 && (it & 15) == 15 && stopped_already()) break;
+        loop_open(c);
+        for (int64_t it = 0; it < max_iter; ++it) {
+            local_iteration(c, fit, tol_abs);
+            if (tol_abs > 0 && (it & 15) == 15 && stop_fired(c)) break;
         }
         fetch_results(c, errors_out, n_done, stopped);
     });

@@ -1,7 +1,9 @@
 // Host side of libklnmf.so, shared by its translation units (include/klnmf.h has the contract and the reference interfaces each
 // entry point replaces):
 //   api_context.hip  contexts, problems, uploads and downloads (K6: learner.py:53-56 stack_data; nmf.py:147-157 _init)
-//   api_loop.hip     the loop of nmf.py:212-222 and its pieces: launch sequencing, stop rule, fp8 regime and its monitor
+//   api_loop.hip     the loop of nmf.py:212-222 and its pieces: launch sequencing (the row pass's kernel looked up in the table
+//                    built from rowpass4_list.hip.h), stop rule, fp8 regime and its monitor; the loop driver every loop of
+//                    every unit runs on (loop_open, local_iteration, loop_advance, stop_fired)
 //   api_comm.hip     row shards over the GPUs of a node: the RCCL communicator, the agreed loop entry, the exchange (nmf.py:349)
 //   api_eval.hip     evaluation and introspection: reconstruction products (learner.py:80-84), distances, queries, profiling
 //   api_group.hip    a group of contexts (row shards, one device each, a device may repeat) driven from one host thread: the
@@ -33,7 +35,8 @@
 #include "sparseb.hip.h"
 #include "mfma.hip.h"
 #include "mfma4.hip.h"
-// the k_rowpass4 instantiations live in rowpass4_inst_{1,2,3}.hip (built in parallel); here they are only declared
+// the k_rowpass4 instantiations live in rowpass4_inst_{1,2,3}.hip (built in parallel); here they are only declared, and
+// launch_rowpass4_kt (api_loop.hip) takes their addresses: no host unit carries device code for them
 #include "rowpass4_list.hip.h"
 namespace klnmf {
 KL_RP4_LIST_1(KL_RP4_DECLARE) KL_RP4_LIST_2(KL_RP4_DECLARE) KL_RP4_LIST_3(KL_RP4_DECLARE)
@@ -191,7 +194,6 @@ struct DevSwitches {
     // at any f > L.  Buffers are sized for what these force; klnmf_query (KLNMF_Q_EX_*) reports the effective values.
     int ex_rc = 0, ex_wc = 0;
     int64_t ex_hseg = 0;
-    int graph = 0;              // KLNMF_GRAPH=1: two iterations captured into a hipGraph and replayed (measured: no gain)
     static DevSwitches read() {
         DevSwitches d;
         auto num = [](const char *name, int dflt) { const char *e = std::getenv(name); return e ? std::atoi(e) : dflt; };
@@ -211,7 +213,6 @@ struct DevSwitches {
         d.comm_parts = num("KLNMF_COMM_PARTS", 1);
         d.comm_overlap = num("KLNMF_COMM_OVERLAP", 1) != 0;
         d.comm_single = num("KLNMF_COMM_SINGLE", 0) != 0;
-        d.graph = num("KLNMF_GRAPH", 0);
         d.sp_cb = num("KLNMF_SP_CB", 0);
         d.sp_rb = num("KLNMF_SP_RB", 0);
         d.ex_rc = std::max(0, num("KLNMF_EX_ROW_CHUNKS", 0));
@@ -233,7 +234,6 @@ struct klnmf_ctx {
     bool have_problem = false;
     int cur = 0;          // index of the current W buffer
     int loop_start_cur = 0;
-    int64_t loop_iters = 0;
 
     // common device state
     DevState *st = nullptr;
@@ -303,7 +303,6 @@ struct klnmf_ctx {
     bool ne_ok = false;                       // the problem's shape has NE kernels (fp16 V, k <= 224, enough rows for fp8 ratio tiles)
     bool ne_loop = false;                     // this loop's fp8-tile update passes drop the numerator's eps (NE kernels; begin_fp8_loop)
     bool last_row_ne = false;                 // ... and the update pass just launched was one of them (its loss needs DevState.corr_eps)
-    bool in_capture = false;                  // a hipGraph capture is recording this context's launches (no synchronising polls)
     // the saturation counters of the last loop as its end found them (DevState is reset by the next entry point)
     int64_t stat_w8_sat = 0, stat_w8_fallbacks = 0, stat_q8_sat = 0, stat_q8_unfixed = 0;
     // ---- the fp8 monitor (monitor.hip.h): partial sums of the monitored iteration; what k_post is to do with them; the last
@@ -503,7 +502,10 @@ void piece_colpass(klnmf_ctx *c);
 void piece_update_H(klnmf_ctx *c);
 void piece_fit_tail(klnmf_ctx *c);
 void fetch_results(klnmf_ctx *c, double *errors_out, int64_t *n_done, int *stopped);
-void poll_fp8_overflow(klnmf_ctx *c, bool agreed = false);
+void loop_open(klnmf_ctx *c);
+void loop_advance(klnmf_ctx *c, bool poll, bool agreed);
+void local_iteration(klnmf_ctx *c, int fit, double tol_abs);
+bool stop_fired(klnmf_ctx *c);
 bool fp8_poll_due(const klnmf_ctx *c);
 bool fused_w8_stage(klnmf_ctx *c);
 void launch_monitor(klnmf_ctx *c, bool use8);

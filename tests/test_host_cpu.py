@@ -363,21 +363,44 @@ def test_bench_power_clock_sampler_is_harmless_without_a_card():
 
 
 def test_every_launched_rowpass4_instantiation_is_in_the_list():
-    """The parallel build declares the k_rowpass4 instantiations `extern` in ctx.hip.h (launched from api_loop.hip) and defines them in
-    rowpass4_inst_*.hip from the lists of rowpass4_list.hip.h: an instantiation that the launch code names but the lists lack
-    would be compiled a second time in the loop unit (slow, silently); one that the lists name twice fails the build.  Checked
-    on the text: every `k_rowpass4<KTV, a, MODE, b, c, d, e>` pattern of the launch macros appears in the lists' shapes."""
+    """The k_rowpass4 instantiations are named in ONE place, the X-macro lists of rowpass4_list.hip.h: rowpass4_inst_*.hip define
+    them, ctx.hip.h declares them `extern`, and the launch looks its kernel up in a table built from the same lists (a
+    static_assert there proves that the lists and the table's index cover each other).  An instantiation named anywhere else
+    would be compiled a second time, silently, in the unit that names it.
+    (a) on the text: under csrc/ the template-id `k_rowpass4<` is only ever followed by the lists' macro parameters;
+    (b) on the built library: its gfx950 code objects define 264 distinct k_rowpass4 kernels, each exactly once -- nothing
+    compiled twice, nothing compiled outside the lists."""
+    import collections
+    import glob
     import re
+    import subprocess
+    import sys
+    import tempfile
     import __graft_entry__ as ge
-    api = open(os.path.join(ge.CSRC, 'api_loop.hip')).read()
+    params = 'KT, ODD, MODE, EP, NW, SPLIT, Q8>'
+    for path in sorted(glob.glob(os.path.join(ge.CSRC, '*.hip')) + glob.glob(os.path.join(ge.CSRC, '*.hip.h'))):
+        text = open(path).read()
+        for m in re.finditer(r'k_rowpass4<', text):
+            assert text.startswith(params, m.end()), (os.path.basename(path), text[m.start():m.end() + 40])
     lst = open(os.path.join(ge.CSRC, 'rowpass4_list.hip.h')).read()
-    launched = set()
-    for m in re.finditer(r'k_rowpass4<KTV, (\d), MODE, (\d)(?:, (\w+), (\d)(?:, (\d))?)?>', api):
-        odd, ep, nw, split, q8 = m.groups()
-        launched.add(((nw or '8'), split or '0', q8 or '0'))
-    small = set(re.findall(r'X\(KT, ODD, \d, EP, (8), (\d), (\d)\)', lst))
-    big = set(re.findall(r'X\(KT, 0, \d, EP, (4), (\d), (\d)\)', lst))
-    assert launched and launched <= (small | big), launched - (small | big)
+    assert 'static_assert(rowpass4_lists_match_index()' in lst
+    if not os.path.exists(ge.LIB):
+        pytest.skip('libklnmf.so has not been built')
+    sys.path.insert(0, os.path.join(ge.ROOT, 'scripts'))
+    try:
+        import kernel_fingerprint as kf
+    finally:
+        sys.path.pop(0)
+    defined = collections.Counter()
+    with tempfile.TemporaryDirectory() as tmp:
+        for co in kf.device_code(ge.LIB, tmp):
+            table = subprocess.run([kf.OBJDUMP, '-t', co], capture_output=True, text=True, check=True).stdout
+            for line in table.splitlines():
+                cols = line.split()
+                if 'k_rowpass4' in line and ' F ' in line and not cols[-1].endswith('.kd'):
+                    defined[cols[-1]] += 1
+    assert len(defined) == 7 * 32 + 5 * 8, len(defined)
+    assert set(defined.values()) == {1}, [name for name, count in defined.items() if count != 1]
 
 
 def test_csr_input_and_large_k_never_change_arithmetic_silently(capsys):
