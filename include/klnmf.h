@@ -394,6 +394,12 @@ int klnmf_all_distances_device(int device, int dtype, int metric, int64_t na, in
 #define KLNMF_Q_EX_H_SEGMENTS     18
 #define KLNMF_Q_EX_H_FROM_SLABS   19
 int klnmf_query(klnmf_ctx *ctx, int what, int64_t *value);
+/* The launch plan of a problem without a context or a device (replaces nothing of the reference): what klnmf_query would answer
+ * right after klnmf_set_problem(n, f, k) -- with nnz >= 0 after klnmf_set_problem_sparse(n, f, k, nnz) -- on a context of `precision`
+ * whose device has `cu_count` compute units, for the items of the plan: KLNMF_Q_RATIO_TILE_BYTES, KLNMF_Q_SP_COL_BLOCKS / _ROW_BLOCKS,
+ * KLNMF_Q_EX_ROW_CHUNKS / _W_CHUNKS / _H_SEGMENTS / _H_FROM_SLABS.  Returns the refusal where that call would refuse the shape.  It
+ * reads the development switches as that call does, makes no HIP call, and runs on a machine without a GPU. */
+int klnmf_plan_query(int precision, int64_t n, int64_t f, int64_t k, int64_t nnz, int cu_count, int what, int64_t *value);
 /*   KLNMF_QF_SUM_V  the sum of the uploaded V as stored (16-bit modes; 0 in the exact modes), in the data's own units */
 #define KLNMF_QF_SUM_V            0
 /*   KLNMF_QF_NNZ_V  how many entries of the uploaded V are > 0 as stored (16-bit modes) */

@@ -111,6 +111,7 @@ SIGNATURES = {
     'klnmf_profile_read_tail': (_c.c_int, [_ctx_p, _c.POINTER(_i64), _c.POINTER(_c.c_double), _c.POINTER(_i64), _c.c_int]),
     'klnmf_synchronize': (_c.c_int, [_ctx_p]),
     'klnmf_query': (_c.c_int, [_ctx_p, _c.c_int, _c.POINTER(_i64)]),
+    'klnmf_plan_query': (_c.c_int, [_c.c_int, _i64, _i64, _i64, _i64, _c.c_int, _c.c_int, _c.POINTER(_i64)]),
     'klnmf_set_H_device': (_c.c_int, [_ctx_p, _c.c_void_p, _c.c_int, _i64, _i64, _i64, _c.c_int]),
     'klnmf_get_W_device': (_c.c_int, [_ctx_p, _c.c_void_p, _c.c_int, _i64]),
     'klnmf_upload_V_device_rows_dt': (_c.c_int, [_ctx_p, _c.c_void_p, _c.c_int, _c.c_void_p, _i64, _i64, _i64, _i64, _i64,
@@ -255,6 +256,17 @@ Q_SP_COL_BLOCKS, Q_SP_ROW_BLOCKS = 14, 15
 Q_EX_ROW_CHUNKS, Q_EX_W_CHUNKS, Q_EX_H_SEGMENTS, Q_EX_H_FROM_SLABS = 16, 17, 18, 19
 QF_SUM_V, QF_NNZ_V, QF_MON_STAT, QF_MON_THRESHOLD = 0, 1, 2, 3
 QF_KL_OVER_SUM_V = 9
+
+
+def plan_query(precision, n, f, k, what, nnz=-1, cu_count=256):
+    """klnmf_plan_query: what `Context.query(what)` answers right after set_problem(n, f, k) -- with nnz >= 0 after
+    set_problem_sparse -- on a device with `cu_count` compute units, for the items of the launch plan (Q_RATIO_TILE_BYTES,
+    Q_SP_*, Q_EX_*).  No context, no GPU.  Raises NativeError where that call would refuse the shape."""
+    if isinstance(precision, str):
+        precision = PRECISIONS[precision]
+    v = _i64(0)
+    _check(load().klnmf_plan_query(int(precision), int(n), int(f), int(k), int(nnz), int(cu_count), int(what), ctypes.byref(v)))
+    return int(v.value)
 
 
 def selftest(device=0):

@@ -6,16 +6,6 @@ DevBlockCache g_block_cache;
 
 namespace {
 
-// ---- the fp8 monitor (monitor.hip.h) -------------------------------------------------------------------------------------------
-void monitor_setup(klnmf_ctx *c) {
-    c->mon_part = nullptr;
-    c->mon_pending = false;
-    if (!c->q8_ok) return;
-    c->mon_part = (float *)c->dalloc((size_t)kMonBlocks * 2 * 2 * c->KP * 32 * 4);
-    c->mon_spread = (float *)c->dalloc((size_t)2 * kMonBlocks * 96 * 4);
-}
-
-
 void fast_pack_W(klnmf_ctx *c) {
     hipLaunchKernelGGL(k_pack_W, dim3(grid_for(c->n_pad * c->KP, 256, 8192)), dim3(256), 0,
                        c->stream, (const float *)c->W32[c->cur], c->Wb[c->cur], c->n_pad, c->KP,
@@ -40,7 +30,6 @@ void choose_eps_carrier(klnmf_ctx *c) {
     c->kc = (c->kc_shape >= 0 && fits) ? c->kc_shape : -1;
 }
 
-
 // ------------------------------------------------------------- loop pieces ---
 // Empty V tile buffers: true zeros (padding rows and columns are inert; an all-zero row of V gives an exactly zero row of W,
 // as in the reference -- also under the update pass without the numerator's eps, whose ratio carries a 2^-100 addend instead
@@ -48,7 +37,6 @@ void choose_eps_carrier(klnmf_ctx *c) {
 void fill_v_tiles(klnmf_ctx *c, void *tiles, size_t bytes) {
     HIPCHK(hipMemsetAsync(tiles, 0, bytes, c->stream));
 }
-
 
 // ---------------------------------------------------------------- uploads ---
 template <typename S>
@@ -83,8 +71,6 @@ void check_block(klnmf_ctx *c, int64_t rows, int64_t cols, int64_t ld, int64_t r
         ld < cols)
         fail(KLNMF_ERR_ARG, "V block out of range");
 }
-
-
 
 // dense [rows,cols] host array -> device array of the context's element type / padded fp32
 void set_matrix(klnmf_ctx *c, const void *src, int dtype, int64_t rows, int64_t cols, void *exact_dst,
@@ -148,6 +134,131 @@ void get_matrix(klnmf_ctx *c, void *dst, int dtype, int64_t rows, int64_t cols, 
     HIPCHK(e);
     HIPCHK(e2);
     HIPCHK(e3);
+}
+
+// ------------------------------------------------------------ a new problem ---
+// [count] floats `value` into each of `dsts`
+void fill_floats(klnmf_ctx *c, std::initializer_list<float *> dsts, int count, float value) {
+    const std::vector<float> v((size_t)count, value);
+    for (float *d : dsts) HIPCHK(hipMemcpyAsync(d, v.data(), v.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+}
+
+// The buffers of a dense problem in the exact modes, as the plan sizes them.  (The order of the dalloc calls is kept in all three
+// functions: the block cache hands blocks out by size class.)
+void alloc_dense_exact(klnmf_ctx *c) {
+    const size_t es = c->esize(), n = (size_t)c->n, f = (size_t)c->f, k = (size_t)c->k;
+    c->loss_red = (double2 *)c->dalloc(sizeof(double2) * kLossRedMax);
+    c->V = c->dalloc(n * f * es);
+    c->Q = c->dalloc(n * f * es);
+    for (void *&w : c->W) w = c->dalloc(n * k * es);
+    c->H = c->dalloc(k * f * es);
+    c->Npart = c->dalloc((size_t)c->nsplit * k * f * es);
+    if (c->hseg_n > 1) c->hpart = (double *)c->dalloc(sizeof(double) * k * c->hseg_n);
+    c->numer = c->dalloc(k * f * es);
+    if (c->wsplit > 1) c->Wpart = c->dalloc((size_t)c->wsplit * n * k * es);
+    c->loss_part = (double *)c->dalloc(sizeof(double) * c->loss_part_count);
+    if (c->x3_fused()) {
+        c->x3_hs = (float *)c->dalloc(sizeof(float) * F3_KMAX);
+        c->x3_xmax = (unsigned *)c->dalloc(sizeof(unsigned) * F3_KMAX);
+        c->x3_qr = (float *)c->dalloc(sizeof(float) * n);
+        c->x3_loss = (double *)c->dalloc(sizeof(double) * ((n + F3_TR - 1) / F3_TR));
+    }
+}
+
+// ... in the 16-bit mode, with unit scales until a dictionary is packed / an e4m3 image is measured
+void alloc_dense_16(klnmf_ctx *c) {
+    const size_t kp4 = (size_t)c->KP * 4;
+    c->loss_red = (double2 *)c->dalloc(sizeof(double2) * kLossRedMax);
+    c->VtA = c->dalloc(c->v_bytes);      // (true zeros: fill_v_tiles)
+    c->Qt = (unsigned char *)c->dalloc(c->qt_bytes);
+    if (c->q8_ok) c->q8_list = (uint2 *)c->dalloc(sizeof(uint2) * kQ8ListCap);
+    if (c->w8) {
+        c->W8 = (unsigned char *)c->dalloc(c->w8_bytes);
+        c->w8s = (float *)c->dalloc(kp4);
+        fill_floats(c, {c->w8s}, c->KP, 256.f);
+    }
+    for (int i = 0; i < 2; ++i) {
+        c->W32[i] = (float *)c->dalloc(c->w32_bytes);
+        c->Wb[i] = (opnd_t *)c->dalloc(c->wb_bytes);
+    }
+    c->H32 = (float *)c->dalloc(c->h32_bytes);
+    c->Ht4 = (opnd_t *)c->dalloc(c->ht4_bytes);
+    choose_eps_carrier(c);
+    c->hsum = (double *)c->dalloc((size_t)c->KP * 8);
+    for (float **t : {&c->tcur, &c->t_hs, &c->t_unit}) *t = (float *)c->dalloc(kp4);
+    c->wmax = (unsigned *)c->dalloc(kp4);
+    fill_floats(c, {c->tcur, c->t_hs, c->t_unit}, c->KP, kOpScaleW);      // until a dictionary is packed (k_update_pack_H)
+    c->NpartF = (float *)c->dalloc(c->npartF_bytes);
+    c->numerF = (float *)c->dalloc(c->numerF_bytes);
+    c->H32alt = (float *)c->dalloc(c->h32_bytes);
+    if (c->W8) {
+        c->w8tab = (unsigned *)c->dalloc((size_t)kW8TabRows * kp4);      // (zero-filled)
+        c->w8s_next = (float *)c->dalloc(kp4);
+        HIPCHK(hipMemcpyAsync(c->w8s_next, c->w8s, kp4, hipMemcpyDeviceToDevice, c->stream));
+    }
+    if (c->q8_ok) {      // the fp8 monitor (monitor.hip.h)
+        c->mon_part = (float *)c->dalloc((size_t)kMonBlocks * 2 * 2 * c->KP * 32 * 4);
+        c->mon_spread = (float *)c->dalloc((size_t)2 * kMonBlocks * 96 * 4);
+    }
+    if (c->gpart_bytes) c->Gpart = (float *)c->dalloc(c->gpart_bytes);
+    c->loss_part2 = (double2 *)c->dalloc(c->loss_part2_bytes);
+}
+
+// ... of a CSR problem
+void alloc_csr(klnmf_ctx *c) {
+    const size_t es = c->esize(), n = (size_t)c->n, f = (size_t)c->f, k = (size_t)c->k, nnz = (size_t)c->nnz, nz1 = nnz > 0 ? nnz : 1;
+    for (void *&w : c->W) w = c->dalloc(n * k * es);
+    c->H = c->dalloc(k * f * es);
+    c->HT = c->dalloc(k * f * es);
+    c->numer = c->dalloc(k * f * es);
+    c->sp_indptr = (int64_t *)c->dalloc(sizeof(int64_t) * (n + 1));
+    c->sp_indices = (int64_t *)c->dalloc(sizeof(int64_t) * nz1);
+    c->csc_indptr = (int64_t *)c->dalloc(sizeof(int64_t) * (f + 1));
+    c->csc_rows = (int64_t *)c->dalloc(sizeof(int64_t) * nz1);
+    c->csc_perm = (int64_t *)c->dalloc(sizeof(int64_t) * nz1);
+    c->csc_work = (int64_t *)c->dalloc(sizeof(int64_t) * CscWork(c->nnz).elems);
+    c->sp_data = c->dalloc(nz1 * es);
+    c->sp_q = c->dalloc(nz1 * es);
+    c->sp_row_loss = (double *)c->dalloc(sizeof(double) * n);
+    if (c->hseg_n > 1) c->hpart = (double *)c->dalloc(sizeof(double) * k * c->hseg_n);
+    c->sp_wpart = (double *)c->dalloc(sizeof(double) * c->sp_nblk * k);
+    c->sp_prod = (double *)c->dalloc(sizeof(double) * k);
+    if (!c->sp_blocked) return;
+    c->sp_idx32 = (int *)c->dalloc(sizeof(int) * nnz);
+    c->csc_rows32 = (int *)c->dalloc(sizeof(int) * nnz);
+    c->csc_perm32 = (int *)c->dalloc(sizeof(int) * nnz);
+    c->sp_blkptr = (int64_t *)c->dalloc(sizeof(int64_t) * n * (c->sp_cb + 1));
+    c->csc_blkptr = (int64_t *)c->dalloc(sizeof(int64_t) * f * (c->sp_rb + 1));
+    c->sp_loss_part = (double *)c->dalloc(sizeof(double) * (size_t)c->sp_cb * n);
+    c->sp_G = c->dalloc((size_t)c->sp_cb * n * k * es);
+    c->sp_NT = c->dalloc((size_t)c->sp_rb * f * k * es);
+    c->sp_bad = (int *)c->dalloc(sizeof(int));
+}
+
+// What klnmf_set_problem and klnmf_set_problem_sparse (nnz >= 0) do.  The plan of the shape first (plan.hip.h): what it refuses is
+// refused before anything is touched -- except where it says that the previous problem goes first.  Then the previous problem
+// is released (free_all: ProblemState back to its defaults), the plan and the switches it was made with are stored, and the
+// buffers it sizes are taken.
+void set_problem(klnmf_ctx *c, int64_t n, int64_t f, int64_t k, int64_t cap, int64_t nnz) {
+    const DevSwitches sw = DevSwitches::read();
+    const ProblemPlan plan = plan_problem(c->prec, n, f, k, nnz, c->cu_count, sw);
+    if (plan.refuse != KLNMF_OK && !plan.refuse_releases) fail(plan.refuse, plan.refuse_msg);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->free_all();
+    if (plan.refuse != KLNMF_OK) fail(plan.refuse, plan.refuse_msg);
+    static_cast<ProblemPlan &>(*c) = plan;
+    c->sw = sw;
+    c->cap = cap;
+    c->st = (DevState *)c->dalloc(sizeof(DevState));
+    c->errors = (double *)c->dalloc(sizeof(double) * (cap > 0 ? cap : 1));
+    c->loss_xchg = (double *)c->dalloc(sizeof(double) * 2);
+    if (c->sparse) alloc_csr(c);
+    else if (c->is_exact()) alloc_dense_exact(c);
+    else alloc_dense_16(c);
+    reset_state(c);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->have_problem = true;
 }
 
 // =============================================================== exports ===
@@ -283,269 +394,8 @@ int klnmf_destroy(klnmf_ctx *c) {
 int klnmf_set_problem(klnmf_ctx *c, int64_t n, int64_t f, int64_t k, int64_t cap) {
     return guarded([&] {
         use(c);
-        if (n <= 0 || f <= 0 || k <= 0 || cap < 0) fail(KLNMF_ERR_ARG, "n, f, k must be positive");
-        if (n > (1LL << 30) || f > (1LL << 30) || k > (1LL << 20))
-            fail(KLNMF_ERR_UNSUPP, "dimension too large");
-        if (c->is_exact() && n > (int64_t)65535 * GT)
-            fail(KLNMF_ERR_UNSUPP, "KLNMF_PREC_F64 / F32 / BF16X3 / F16X3: more than 65535 x 64 rows per context (row tiles ride on gridDim.y); "
-                                   "shard the rows or use the 16-bit mode");
-        HIPCHK(hipStreamSynchronize(c->stream));
-        c->free_all();
-        c->sw = DevSwitches::read();
-        c->Gpart = nullptr; c->row_chunks = 1; c->tail_wg = 0; c->tail_chunks = 1;
-        c->Wpart = nullptr; c->wsplit = 1;
-        c->hseg_n = 1; c->hpart = nullptr;
-        c->n = n; c->f = f; c->k = k; c->cap = cap;
-        c->cur = 0;
-        c->w_is_init = false;
-        c->sparse = false;
-        c->v_uploaded = false;
-        c->refusals_dirty = true;
-        c->v_scale = 1.0;
-        c->nnz = 0;
-        c->st = (DevState *)c->dalloc(sizeof(DevState));
-        c->errors = (double *)c->dalloc(sizeof(double) * (cap > 0 ? cap : 1));
-        c->loss_xchg = (double *)c->dalloc(sizeof(double) * 2);
-        c->loss_red = (double2 *)c->dalloc(sizeof(double2) * kLossRedMax);
-        if (c->is_exact()) {
-            const size_t es = c->esize();
-            c->V = c->dalloc((size_t)n * f * es);
-            c->Q = c->dalloc((size_t)n * f * es);
-            c->W[0] = c->dalloc((size_t)n * k * es);
-            c->W[1] = c->dalloc((size_t)n * k * es);
-            c->H = c->dalloc((size_t)k * f * es);
-            // 64 x 64 output tiles (k_gemm).  Measured (profiles/r04_exact_modes.txt): with the register prefetch they win over
-            // 128 x 128 tiles at every shape tried (2000 x 4096, k = 200, fp64: 440 us per iteration against 455, 537 before):
-            // four waves per SIMD hide more than the halved LDS traffic gains.
-            auto tiles_of = [](int64_t M, int64_t N, int64_t TL) { return ((M + TL - 1) / TL) * ((N + TL - 1) / TL); };
-            c->q_tt = 4;
-            const int64_t smax = (n + 63) / 64;          // at least four contraction steps per chunk
-            auto n_split = [&](int tt) {
-                const int64_t tiles = tiles_of(k, f, 16 * tt);
-                int64_t s = (4 * (int64_t)c->cu_count + tiles - 1) / tiles;
-                if (s > smax) s = smax;
-                if (s < 1) s = 1;
-                return s;
-            };
-            c->n_tt = 4;
-            int64_t s = c->sw.ex_rc > 0 ? (int64_t)c->sw.ex_rc : n_split(c->n_tt);      // (KLNMF_EX_ROW_CHUNKS: ctx.hip.h)
-            int64_t chunk = (n + s - 1) / s;
-            chunk = (chunk + GK - 1) / GK * GK;
-            s = (n + chunk - 1) / chunk;
-            c->nsplit = (int)s;
-            c->kchunk = (int)chunk;
-            c->Npart = c->dalloc((size_t)s * k * f * es);
-            c->hseg = 4096;          // dictionary rows of 16 384 columns and more: the H rule in segments (exact_H)
-            c->hseg_n = f >= 16384 ? (int)((f + c->hseg - 1) / c->hseg) : 1;
-            if (c->sw.ex_hseg > 0) {                    // (KLNMF_EX_H_SEG)
-                c->hseg = c->sw.ex_hseg;
-                c->hseg_n = f > c->hseg ? (int)((f + c->hseg - 1) / c->hseg) : 1;
-            }
-            c->hpart = c->hseg_n > 1 ? (double *)c->dalloc(sizeof(double) * (size_t)k * c->hseg_n) : nullptr;
-            c->numer = c->dalloc((size_t)k * f * es);
-            // W rule: n*k/4096 output tiles, each contracting over all of f.  With fewer tiles than CUs split f so that
-            // the grid covers the chip about twice.
-            {
-                auto w_split = [&](int tt) {
-                    const int64_t wt = tiles_of(k, n, 16 * tt);
-                    int64_t w = wt < c->cu_count ? (2 * (int64_t)c->cu_count + wt - 1) / wt : 1;
-                    return std::min<int64_t>(w, (f + 4 * GK - 1) / (4 * GK));
-                };
-                c->w_tt = 4;
-                int64_t ws = w_split(c->w_tt);
-                ws = std::min<int64_t>(ws, (f + 4 * GK - 1) / (4 * GK));
-                if (c->sw.ex_wc > 0) ws = c->sw.ex_wc;      // (KLNMF_EX_W_CHUNKS)
-                while (ws > 1 && ws * n * k * (int64_t)es > ((int64_t)256 << 20)) --ws;
-                int64_t wch = (f + ws - 1) / ws;
-                wch = (wch + GK - 1) / GK * GK;
-                ws = (f + wch - 1) / wch;
-                c->wsplit = (int)ws;
-                c->wchunk = (int)wch;
-                if (ws > 1) c->Wpart = c->dalloc((size_t)ws * n * k * es);
-            }
-            c->loss_part_count = ((f + GT - 1) / GT) * ((n + GT - 1) / GT);
-            c->loss_part = (double *)c->dalloc(sizeof(double) * c->loss_part_count);
-            c->x3_ready = false;
-            c->x3_hs = c->x3_qr = nullptr; c->x3_xmax = nullptr; c->x3_loss = nullptr;
-            if (c->x3_fused()) {
-                c->x3_hs = (float *)c->dalloc(sizeof(float) * F3_KMAX);
-                c->x3_xmax = (unsigned *)c->dalloc(sizeof(unsigned) * F3_KMAX);
-                c->x3_qr = (float *)c->dalloc(sizeof(float) * n);
-                c->x3_loss = (double *)c->dalloc(sizeof(double) * ((n + F3_TR - 1) / F3_TR));
-            }
-        } else {
-            c->KT = (int)((k + 31) / 32);
-            c->ks = (int)((k + 15) / 16);
-            c->big = false;
-            if (k > 512) fail(KLNMF_ERR_UNSUPP, "k > 512 runs in KLNMF_PREC_F32 / F64 / BF16X3 / F16X3 (the 16-bit MFMA kernels cover k <= 512)");
-            if (c->KT >= 8) {
-                // 224 < k <= 512: 4-wave workgroups of the row pass (whole register file per wave, FUSED order) and the
-                // component-split column passes; component tiles in pairs, the W.H contraction over all of them
-                c->big = true;
-                c->KT = 2 * (int)((k + 63) / 64);
-                c->ks = 2 * c->KT;
-            }
-            c->KP = 32 * c->KT;
-            // both passes work on 64-row / 64-column stages: pad to 64 (zero padding is inert)
-            c->n_pad = (n + 63) / 64 * 64;
-            c->f_pad = (f + 127) / 128 * 128;            // the row pass walks 4 column tiles per loop body
-            c->nrt = (int)(c->n_pad / 32);
-            c->nct = (int)(c->f_pad / 32);
-            c->nct_used = (int)((f + 63) / 64 * 2);      // column tiles that hold data (column pass)
-            c->v_scale = 1.0;
-            c->v_uploaded = false;
-            c->refusals_dirty = true;
-            const int total_stages = c->nrt / kStageRowTiles;
-            // the fp16 W images are streamed by global_load_lds in whole 8 KiB rounds, i.e. a stage's copy reads on into the rows
-            // behind it: pad the tail by what ONE copy covers.  (64 rows until round 4: at KP = 32 a row is 64 bytes and a copy 128
-            // rows -- the last stage read 2 KiB past the image; found by scripts/shape_fuzz.py as a memory access fault at
-            // 16 305 x 28, k = 8, where the image is exactly 1 MiB and ends on a mapping boundary.)
-            const int64_t copy_rows = (colq_w_area(c->KP) + (int64_t)w_ld(c->KP) * 2 - 1) / ((int64_t)w_ld(c->KP) * 2);
-            c->w_rows = (int64_t)total_stages * 32 * kStageRowTiles + std::max<int64_t>(64, copy_rows);
-            const size_t vbytes = (size_t)c->nrt * c->nct * 1024 * 2;
-            // fp8 ratio tiles: only the H numerator -- a sum over all rows -- sees their 3-bit significands; its relative
-            // error falls like 0.036 sqrt(2 / n), so they are used from 32 769 / 65 536 rows per context on (row_chunks_possible_q8;
-            // KLNMF_QTILE = 8 / 16 forces either), where the bytes matter
-            const bool col8_off = c->sw.col8 == 0;
-            const bool q8_kt = !c->big || !col8_off;      // (k > 224: fp8 tiles only with the fp8 x fp8 column pass)
-            // ... and from one column tile of data on: below that the tiles are mostly padding (nothing to gain), and a handful of
-            // columns is fitted so exactly that the loss itself goes to 0 (the 16-bit mode's own operand rounding then shows)
-            c->q8_ok = q8_kt && f >= 32 && c->row_chunks_possible_q8(n, c->big);
-            if (c->sw.qtile != 0) c->q8_ok = q8_kt && c->sw.qtile == 8;
-            c->q8_loop = false;
-            c->iter_in_loop = 0;
-            c->v_max = 0.0;
-            c->ne_ok = c->q8_ok && !c->big;      // (q8_ok: enough rows for fp8 ratio tiles -- where the NE kernels exist)
-            c->VtA = c->dalloc(vbytes, false);
-            fill_v_tiles(c, c->VtA, vbytes);
-            c->Qt = (unsigned char *)c->dalloc((size_t)c->nrt * c->nct * kQTile);      // (fp8 tiles use the first half of the buffer)
-            c->W8 = nullptr; c->w8s = nullptr; c->w8_meas = false;
-            c->q8_list = c->q8_ok ? (uint2 *)c->dalloc(sizeof(uint2) * kQ8ListCap) : nullptr;
-            // fp8 x fp8 column pass (e4m3 image of W_new): where the H-numerator product is worth the conversion launch --
-            // k > 96 and 65 536 rows or more; below that the f16-operand column pass reads the fp8 tiles (C2, k = 50: 0.053 ms
-            // against 0.050 + 0.03 ms of conversions; profiles/r03_c2_schedules.txt)
-            const bool col8_size = c->big || (c->KT >= 4 && n >= 65536) || c->sw.col8 >= 1;
-            if (c->q8_ok && !col8_off && col8_size) {
-                c->W8 = (unsigned char *)c->dalloc((size_t)(c->n_pad + 64) * w8_ld(c->KP) + 65536);
-                c->w8s = (float *)c->dalloc((size_t)c->KP * 4);
-                const std::vector<float> unit8((size_t)c->KP, 256.f);
-                HIPCHK(hipMemcpyAsync(c->w8s, unit8.data(), unit8.size() * 4, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(hipStreamSynchronize(c->stream));
-            }
-            for (int i = 0; i < 2; ++i) {
-                c->W32[i] = (float *)c->dalloc((size_t)c->n_pad * c->KP * 4);
-                c->Wb[i] = (opnd_t *)c->dalloc((size_t)c->w_rows * w_ld(c->KP) * 2);
-            }
-            c->H32 = (float *)c->dalloc((size_t)c->KP * c->f_pad * 4);
-            c->Ht4 = (opnd_t *)c->dalloc((size_t)c->nct * h4_tile_bytes(c->KP) + kObj4);
-            // eps through a pad component (k_update_pack_H): the row pass's W epilogue keeps the carrier column at 2^-10; needs
-            // a spare component inside the MFMA-1 contraction range
-            c->kc_shape = (k < 16 * c->ks && c->sw.eps_pad) ? (int)k : -1;
-            choose_eps_carrier(c);
-            c->hsum = (double *)c->dalloc((size_t)c->KP * 8);
-            c->tcur = (float *)c->dalloc((size_t)c->KP * 4);
-            c->t_hs = (float *)c->dalloc((size_t)c->KP * 4);
-            c->t_unit = (float *)c->dalloc((size_t)c->KP * 4);
-            c->wmax = (unsigned *)c->dalloc((size_t)c->KP * 4);
-            c->images_measured = false;
-            {
-                const std::vector<float> unit((size_t)c->KP, kOpScaleW);      // until a dictionary is packed (k_update_pack_H)
-                for (float *t : {c->tcur, c->t_hs, c->t_unit})
-                    HIPCHK(hipMemcpyAsync(t, unit.data(), unit.size() * 4, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(hipStreamSynchronize(c->stream));
-            }
-            // column pass decomposition: column blocks of 8 tiles x row chunks; keep the grid a
-            // multiple of 8 (XCD remap) and close to a multiple of the CU count
-            const int ctw = c->big ? kWavesPerWG / 2 : kWavesPerWG;      // column tiles per workgroup (colq.hip.h, KSPLIT)
-            c->ncb = (c->nct_used + ctw - 1) / ctw;
-            auto chunks_for = [&](int ncb) {      // row chunks of a column pass over `ncb` column blocks: the grid fills the chip once
-                int nch = 8;                      // (one workgroup is resident per CU; two per CU measured 1-3 % slower)
-                while ((int64_t)nch * ncb < c->cu_count && nch * 2 <= total_stages) nch += 8;
-                while (nch > 8 && ((int64_t)nch * ncb) % c->cu_count != 0 &&
-                       (int64_t)(nch - 8) * ncb >= c->cu_count) nch -= 8;
-                if (nch > total_stages) nch = total_stages > 0 ? ((total_stages + 7) / 8) * 8 : 8;
-                return nch;
-            };
-            const int nch = chunks_for(c->ncb);
-            c->nchunks = nch;
-            c->stages_per_chunk = (total_stages + nch - 1) / nch;
-            c->whole = klnmf_ctx::PartCfg{0, c->ncb, 0, c->nct_used, 0, (int)f, (int)c->f_pad, nch, c->stages_per_chunk, 0, 0};
-            // column parts for loops on a communicator (overlap of the numerator's all-reduce with the column pass)
-            c->nparts_cfg = std::min(std::min(kPostMaxParts, std::max(1, c->sw.comm_parts)), c->ncb);
-            int64_t split_numer = 0, split_slabs = 0;
-            if (c->nparts_cfg > 1) {
-                for (int p = 0; p < c->nparts_cfg; ++p) {
-                    klnmf_ctx::PartCfg &q = c->parts[p];
-                    q.cb0 = (int)((int64_t)c->ncb * p / c->nparts_cfg);
-                    q.ncb = (int)((int64_t)c->ncb * (p + 1) / c->nparts_cfg) - q.cb0;
-                    q.ct0 = q.cb0 * ctw;
-                    q.nct = std::min(c->nct_used - q.ct0, q.ncb * ctw);
-                    q.col0 = q.ct0 * 32;
-                    q.ld = q.ncb * ctw * 32;
-                    q.ncols = (int)std::min<int64_t>(f - q.col0, q.ld);
-                    q.nchunks = chunks_for(q.ncb);
-                    q.spc = (total_stages + q.nchunks - 1) / q.nchunks;
-                    q.numer_off = split_numer;
-                    q.slab_off = split_slabs;
-                    split_numer += (int64_t)c->KP * q.ld;
-                    split_slabs += (int64_t)q.nchunks * c->KP * q.ld;
-                }
-            }
-            c->NpartF = (float *)c->dalloc((size_t)std::max<int64_t>((int64_t)nch * c->KP * c->f_pad, split_slabs) * 4);
-            c->numerF = (float *)c->dalloc((size_t)std::max<int64_t>((int64_t)c->KP * c->f_pad, split_numer) * 4);
-            c->H32alt = (float *)c->dalloc((size_t)c->KP * c->f_pad * 4);
-            c->loop_hswaps = 0;
-            c->w8tab = nullptr; c->w8s_next = nullptr; c->conv_ran = false;
-            if (c->W8) {
-                c->w8tab = (unsigned *)c->dalloc((size_t)kW8TabRows * c->KP * 4);      // (zero-filled)
-                c->w8s_next = (float *)c->dalloc((size_t)c->KP * 4);
-                HIPCHK(hipMemcpyAsync(c->w8s_next, c->w8s, (size_t)c->KP * 4, hipMemcpyDeviceToDevice, c->stream));
-            }
-            monitor_setup(c);
-            // Column-split update pass: with fewer than half as many 8-wave workgroups as CUs (n < ~32 000 rows; the
-            // reference's own data sets have 10^2..10^3) split every row block's columns over blockIdx.y so that the grid
-            // fills the chip once.  KLNMF_ROW_SPLIT = 0 / N (development switch) forces it off / to N chunks.
-            // (row_chunks and tail_wg below: only under !big -- the column-split kernels exist for the 8-wave workgroups alone,
-            // and fast_rowpass refuses a big problem that carries either)
-            c->row_chunks = 1;
-            c->row_ct_chunk = c->nct;
-            if (!c->big && !c->q8_ok) {
-                const int nwg = (c->nrt + kWaves4 - 1) / kWaves4;
-                int want = (2 * nwg <= c->cu_count) ? c->cu_count / nwg : 1;
-                if (c->sw.row_split >= 0) want = std::max(1, c->sw.row_split);
-                want = std::min(want, c->nct / 4);
-                const int64_t slab_bytes = (int64_t)c->nrt * 32 * c->KP * 4;
-                while (want > 1 && want * slab_bytes > (int64_t)256 << 20) --want;
-                if (want > 1) {
-                    c->row_ct_chunk = 4 * ((c->nct / 4 + want - 1) / want);
-                    c->row_chunks = (c->nct + c->row_ct_chunk - 1) / c->row_ct_chunk;
-                }
-                if (c->row_chunks > 1) c->Gpart = (float *)c->dalloc((size_t)c->row_chunks * slab_bytes);
-            }
-            // Hybrid update pass: more workgroups than CUs, and a last partial round of at most half the CUs (one
-            // workgroup per CU: 254 registers).  Its workgroups are split into as many column chunks as fill the chip
-            // once (n = 10^6: 67 workgroups x 3 chunks; 90 000 rows: 96 x 2).  KLNMF_ROW_TAIL = 0 (development switch): off.
-            c->tail_wg = 0; c->tail_chunks = 1; c->tail_ct_chunk = c->nct;
-            if (!c->big && c->row_chunks == 1) {
-                const int nwg = (c->nrt + kWaves4 - 1) / kWaves4;
-                const int rem = nwg % c->cu_count;
-                int want = (nwg > c->cu_count && rem > 0) ? c->cu_count / rem : 1;
-                if (c->sw.row_tail >= 0) want = std::min(want, std::max(1, c->sw.row_tail));
-                want = std::min(std::min(want, 4), c->nct / 4);
-                if (want > 1) {
-                    c->tail_ct_chunk = 4 * ((c->nct / 4 + want - 1) / want);
-                    c->tail_chunks = (c->nct + c->tail_ct_chunk - 1) / c->tail_ct_chunk;
-                    if (c->tail_chunks > 1) {
-                        c->tail_wg = rem;
-                        c->Gpart = (float *)c->dalloc((size_t)c->tail_chunks * (c->nrt - c->tail_rt0()) * 32 * c->KP * 4);
-                    }
-                }
-            }
-            c->loss_part2 = (double2 *)c->dalloc(sizeof(double2) * std::max<int64_t>(c->loss_parts(), (int64_t)c->nrt * c->row_chunks));
-        }
-        reset_state(c);
-        HIPCHK(hipStreamSynchronize(c->stream));
-        c->have_problem = true;
+        if (cap < 0) fail(KLNMF_ERR_ARG, "n, f, k must be positive");
+        set_problem(c, n, f, k, cap, -1);
     });
 }
 
@@ -553,9 +403,8 @@ int klnmf_release_problem(klnmf_ctx *c) {
     return guarded([&] {
         use(c);
         HIPCHK(hipStreamSynchronize(c->stream));
-        c->free_all();              // device blocks back to the per-process cache (large ones to the driver)
-        c->profiling = false;
-        c->images_measured = false;
+        c->free_all();              // device blocks back to the per-process cache (large ones to the driver), ProblemState to its defaults
+        c->profiling = false;       // (the two settings of ContextState that end with a problem: ctx.hip.h)
         c->ratio_eps = kEpsRatio;
     });
 }
@@ -640,85 +489,9 @@ extern "C" {
 int klnmf_set_problem_sparse(klnmf_ctx *c, int64_t n, int64_t f, int64_t k, int64_t cap, int64_t nnz) {
     return guarded([&] {
         use(c);
-        if (!c->is_exact()) fail(KLNMF_ERR_UNSUPP, "CSR input runs in the exact modes (KLNMF_PREC_F64 / F32 / BF16X3 / F16X3); densify for the bf16 kernels");
-        if (n <= 0 || f <= 0 || k <= 0 || cap < 0 || nnz < 0) fail(KLNMF_ERR_ARG, "n, f, k must be positive, nnz >= 0");
-        if (n > (1LL << 30) || f > (1LL << 30) || k > (1LL << 20)) fail(KLNMF_ERR_UNSUPP, "dimension too large");
-        HIPCHK(hipStreamSynchronize(c->stream));
-        c->free_all();
-        c->Gpart = nullptr; c->row_chunks = 1; c->tail_wg = 0; c->tail_chunks = 1;
-        c->Wpart = nullptr; c->wsplit = 1;
-        c->n = n; c->f = f; c->k = k; c->cap = cap;
-        c->cur = 0;
-        c->sparse = true;
-        c->v_uploaded = false;
-        c->refusals_dirty = true;
-        c->v_scale = 1.0;
-        c->nnz = nnz;
-        const size_t es = c->esize();
-        c->st = (DevState *)c->dalloc(sizeof(DevState));
-        c->errors = (double *)c->dalloc(sizeof(double) * (cap > 0 ? cap : 1));
-        c->loss_xchg = (double *)c->dalloc(sizeof(double) * 2);
-        c->V = nullptr; c->Q = nullptr; c->Npart = nullptr; c->loss_part = nullptr;
-        c->W[0] = c->dalloc((size_t)n * k * es);
-        c->W[1] = c->dalloc((size_t)n * k * es);
-        c->H = c->dalloc((size_t)k * f * es);
-        c->HT = c->dalloc((size_t)k * f * es);
-        c->numer = c->dalloc((size_t)k * f * es);
-        c->sp_indptr = (int64_t *)c->dalloc(sizeof(int64_t) * (n + 1));
-        c->sp_indices = (int64_t *)c->dalloc(sizeof(int64_t) * (nnz > 0 ? nnz : 1));
-        c->csc_indptr = (int64_t *)c->dalloc(sizeof(int64_t) * (f + 1));
-        c->csc_rows = (int64_t *)c->dalloc(sizeof(int64_t) * (nnz > 0 ? nnz : 1));
-        c->csc_perm = (int64_t *)c->dalloc(sizeof(int64_t) * (nnz > 0 ? nnz : 1));
-        c->csc_work = (int64_t *)c->dalloc(sizeof(int64_t) * CscWork(nnz).elems);
-        c->sp_data = c->dalloc((size_t)(nnz > 0 ? nnz : 1) * es);
-        c->sp_q = c->dalloc((size_t)(nnz > 0 ? nnz : 1) * es);
-        c->sp_row_loss = (double *)c->dalloc(sizeof(double) * n);
-        c->sp_nblk = (n + kSpColsumRows - 1) / kSpColsumRows;
-        // dictionary rows of 16 384 columns and more: the H rule and the loss term's row sums in segments of 4096
-        c->hseg = 4096;
-        c->hseg_n = f >= 16384 ? (int)((f + c->hseg - 1) / c->hseg) : 1;
-        c->hpart = c->hseg_n > 1 ? (double *)c->dalloc(sizeof(double) * (size_t)k * c->hseg_n) : nullptr;
-        c->sp_wpart = (double *)c->dalloc(sizeof(double) * c->sp_nblk * k);
-        c->sp_prod = (double *)c->dalloc(sizeof(double) * k);
-        // blocks for the L2 (sparseb.hip.h): kSpBlockBytes of H^T per column block / of W per row block, as many blocks as the
-        // slabs of partial sums allow (1 GiB each)
-        c->sp_blocked = k <= 512 && nnz > 0 && n < ((int64_t)1 << 31) && f < ((int64_t)1 << 31) && nnz < ((int64_t)1 << 31);
-        if (c->sp_blocked) {
-            const int64_t per = std::max<int64_t>(64, (kSpBlockBytes / (int64_t)(k * es)) / 64 * 64);
-            const int64_t slab_cap = (int64_t)1 << 30;
-            // How many blocks: as many as make a block's gathered rows fit the L2 (`per` rows of k x es bytes) -- but a (row, block)
-            // cell must still fill the kernels' trips, or the gather slots of its last trip run empty.  Measured (round 5, 20 000 x
-            // 110 000, 0.5 %, k = 50, fp64; profiles/r05_sparse_blocks.txt): 15 column blocks (37 entries per cell) cut the fused
-            // pass's fabric traffic from 4.5 to 1.1 GB and cost it 0.87 instead of 0.66 ms; 4 blocks (137 per cell): 0.62 ms; 3 row
-            // blocks (33 per cell, groups of 16) take the H-side pass from 0.61 to 0.51 ms, 6 (17 per cell) back to 0.63.  So: at
-            // least 128 entries per cell of the CSR order, 32 of the CSC order.  KLNMF_SP_CB / KLNMF_SP_RB (development) override.
-            int64_t cb = std::min<int64_t>((f + per - 1) / per, std::max<int64_t>(1, nnz / std::max<int64_t>(1, n) / 128));
-            int64_t rb = std::min<int64_t>((n + per - 1) / per, std::max<int64_t>(1, nnz / std::max<int64_t>(1, f) / 32));
-            const DevSwitches sw = DevSwitches::read();
-            if (sw.sp_cb > 0) cb = std::min<int64_t>(sw.sp_cb, (f + 63) / 64);
-            if (sw.sp_rb > 0) rb = std::min<int64_t>(sw.sp_rb, (n + 63) / 64);
-            cb = std::max<int64_t>(1, std::min(cb, slab_cap / std::max<int64_t>(1, n * k * (int64_t)es)));
-            rb = std::max<int64_t>(1, std::min(rb, slab_cap / std::max<int64_t>(1, f * k * (int64_t)es)));
-            cb = std::min<int64_t>(cb, ((int64_t)1 << 31) / std::max<int64_t>(1, n) - 1);      // (blocks x rows ride on gridDim.x)
-            rb = std::min<int64_t>(rb, ((int64_t)1 << 31) / std::max<int64_t>(1, f) - 1);
-            if (cb < 1 || rb < 1) c->sp_blocked = false;
-            c->sp_cb = (int)cb; c->sp_rb = (int)rb;
-            c->sp_cb_cols = (f + cb - 1) / cb; c->sp_rb_rows = (n + rb - 1) / rb;
-        }
-        if (c->sp_blocked) {
-            c->sp_idx32 = (int *)c->dalloc(sizeof(int) * nnz);
-            c->csc_rows32 = (int *)c->dalloc(sizeof(int) * nnz);
-            c->csc_perm32 = (int *)c->dalloc(sizeof(int) * nnz);
-            c->sp_blkptr = (int64_t *)c->dalloc(sizeof(int64_t) * n * (c->sp_cb + 1));
-            c->csc_blkptr = (int64_t *)c->dalloc(sizeof(int64_t) * f * (c->sp_rb + 1));
-            c->sp_loss_part = (double *)c->dalloc(sizeof(double) * (size_t)c->sp_cb * n);
-            c->sp_G = c->dalloc((size_t)c->sp_cb * n * k * es);
-            c->sp_NT = c->dalloc((size_t)c->sp_rb * f * k * es);
-            c->sp_bad = (int *)c->dalloc(sizeof(int));
-        }
-        reset_state(c);
-        HIPCHK(hipStreamSynchronize(c->stream));
-        c->have_problem = true;
+        if (!c->is_exact()) fail(KLNMF_ERR_UNSUPP, kCsrNeedsExact);
+        if (cap < 0 || nnz < 0) fail(KLNMF_ERR_ARG, "n, f, k must be positive, nnz >= 0");
+        set_problem(c, n, f, k, cap, nnz);
     });
 }
 

@@ -173,13 +173,12 @@ int klnmf_query(klnmf_ctx *c, int what, int64_t *value) {
     return guarded([&] {
         use(c);
         if (!value) fail(KLNMF_ERR_ARG, "null value");
+        static const ProblemPlan no_plan;
+        if (plan_answer(c->have_problem ? static_cast<const ProblemPlan &>(*c) : no_plan, what, value)) return;      // (the plan items: plan.hip.h)
         switch (what) {
             case KLNMF_Q_FP8_LOOP: *value = c->q8_loop ? 1 : 0; break;
             case KLNMF_Q_FP8_TILE_ITERS: *value = c->stat_q8_tiles; break;
             case KLNMF_Q_FP8_COL_ITERS: *value = c->stat_col8; break;
-            case KLNMF_Q_RATIO_TILE_BYTES:          // per element of V: 0 = no stored ratio tiles, 2 = 16-bit, 1 = fp8 once a loop allows them
-                *value = (c->have_problem && c->Qt) ? (c->q8_ok ? 1 : 2) : 0;
-                break;
             case KLNMF_Q_W8_SATURATED: *value = c->stat_w8_sat; break;
             case KLNMF_Q_W8_FALLBACKS: *value = c->stat_w8_fallbacks; break;
             case KLNMF_Q_RATIO_SATURATED: *value = c->stat_q8_sat; break;
@@ -189,12 +188,6 @@ int klnmf_query(klnmf_ctx *c, int what, int64_t *value) {
             case KLNMF_Q_MON_TRIPS: *value = c->stat_mon_trips; break;
             case KLNMF_Q_MON_GAVE_UP: *value = c->stat_mon_gave_up ? 1 : 0; break;
             case KLNMF_Q_FP8_POLL_DUE: *value = (c->have_problem && fp8_poll_due(c)) ? 1 : 0; break;
-            case KLNMF_Q_SP_COL_BLOCKS: *value = (c->have_problem && c->sparse && c->sp_blocked) ? c->sp_cb : 0; break;
-            case KLNMF_Q_SP_ROW_BLOCKS: *value = (c->have_problem && c->sparse && c->sp_blocked) ? c->sp_rb : 0; break;
-            case KLNMF_Q_EX_ROW_CHUNKS: *value = (c->have_problem && c->is_exact() && !c->sparse) ? c->nsplit : 0; break;
-            case KLNMF_Q_EX_W_CHUNKS: *value = (c->have_problem && c->is_exact() && !c->sparse) ? c->wsplit : 0; break;
-            case KLNMF_Q_EX_H_SEGMENTS: *value = (c->have_problem && c->is_exact() && !c->sparse) ? c->hseg_n : 0; break;
-            case KLNMF_Q_EX_H_FROM_SLABS: *value = (c->have_problem && c->is_exact() && h_from_slabs(c)) ? 1 : 0; break;
             case KLNMF_Q_COMM_RANKS: {
                 int cnt = 1;
                 if (c->comm) RCCLCHK(rccl().CommCount(c->comm, &cnt));
@@ -203,6 +196,17 @@ int klnmf_query(klnmf_ctx *c, int what, int64_t *value) {
             }
             default: fail(KLNMF_ERR_ARG, "klnmf_query: unknown item");
         }
+    });
+}
+
+int klnmf_plan_query(int precision, int64_t n, int64_t f, int64_t k, int64_t nnz, int cu_count, int what, int64_t *value) {
+    return guarded([&] {
+        if (!value) fail(KLNMF_ERR_ARG, "null value");
+        if (!prec_is_exact(precision) && precision != KLNMF_PREC_F16) fail(KLNMF_ERR_ARG, "unknown precision mode");
+        if (cu_count <= 0) fail(KLNMF_ERR_ARG, "klnmf_plan_query: cu_count must be positive");
+        const ProblemPlan plan = plan_problem(precision, n, f, k, nnz, cu_count, DevSwitches::read());
+        if (plan.refuse != KLNMF_OK) fail(plan.refuse, plan.refuse_msg);
+        if (!plan_answer(plan, what, value)) fail(KLNMF_ERR_ARG, "klnmf_plan_query: not an item of the plan");
     });
 }
 

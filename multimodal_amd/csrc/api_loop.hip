@@ -184,7 +184,7 @@ void sparse_Q(klnmf_ctx *c, int write_q, double eps, const DecideArgs &dec) {
 // launch on the split-operand bf16 MFMA (split3.hip.h, same arguments and epilogues).  KLNMF_PREC_F16X3 with k > 256 runs
 // bf16x3's kernels throughout; with k <= 256 what its fused loop kernels do not cover (single steps, W0, the loss alone) runs
 // on the fp32 kernel, which keeps a step within 2^-18 of sum |a.b| (f16x3.hip.h)
-#define KL_GEMM_TT(tt, T, EPI, grid, stream, ...)                                                                     \
+#define KL_GEMM_TT(T, EPI, grid, stream, ...)                                                                         \
     do {                                                                                                            \
         if constexpr (std::is_same<T, float>::value) {                                                              \
             if (c->prec == KLNMF_PREC_BF16X3 || (c->prec == KLNMF_PREC_F16X3 && c->k > F3_KMAX)) {                  \
@@ -201,11 +201,10 @@ void exact_Q(klnmf_ctx *c, int write_q, double eps = kEpsRatio, DecideArgs dec =
     if (c->sparse) { sparse_Q<T>(c, write_q, eps, dec); return; }
     if (write_q) c->x3_ready = false;
     EpiQ<T> epi{(const T *)c->V, (T *)c->Q, c->f, c->loss_part, write_q, 0.0, (T)eps};
-    const int TL = 16 * c->q_tt;
-    dim3 grid((unsigned)((c->f + TL - 1) / TL), (unsigned)((c->n + TL - 1) / TL), 1);
+    dim3 grid((unsigned)((c->f + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), 1);
     EventPair ev{};
     if (c->prof_now) ev = begin_event(c, c->ev_row);
-    KL_GEMM_TT(c->q_tt, T, EpiQ<T>, grid, c->stream, (int)c->n, (int)c->f,
+    KL_GEMM_TT(T, EpiQ<T>, grid, c->stream, (int)c->n, (int)c->f,
                (int)c->k, (const T *)c->W[c->cur], (int64_t)c->k, (int64_t)1,
                (const T *)c->H, (int64_t)c->f, (int64_t)1, (int)c->k + GK,
                (const DevState *)c->st, epi);
@@ -282,9 +281,8 @@ void exact_W(klnmf_ctx *c, const void *qsrc, int multiply) {
     }
     if (c->wsplit > 1) {     // few rows: contraction over f split into chunks (blockIdx.z), W rule from the slabs
         EpiWpart<T> epip{(T *)c->Wpart, c->k, c->n * c->k};
-        const int TLw = 16 * c->w_tt;
-        dim3 gridp((unsigned)((c->k + TLw - 1) / TLw), (unsigned)((c->n + TLw - 1) / TLw), (unsigned)c->wsplit);
-        KL_GEMM_TT(c->w_tt, T, EpiWpart<T>, gridp, c->stream, (int)c->n, (int)c->k,
+        dim3 gridp((unsigned)((c->k + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), (unsigned)c->wsplit);
+        KL_GEMM_TT(T, EpiWpart<T>, gridp, c->stream, (int)c->n, (int)c->k,
                    (int)c->f, (const T *)qsrc, (int64_t)c->f, (int64_t)1, (const T *)c->H,
                    (int64_t)1, (int64_t)c->f, c->wchunk, (const DevState *)c->st, epip);
         HIPCHK(hipGetLastError());
@@ -296,9 +294,8 @@ void exact_W(klnmf_ctx *c, const void *qsrc, int multiply) {
         return;
     }
     EpiW<T> epi{(const T *)c->W[c->cur], (T *)c->W[c->cur ^ 1], c->k, multiply};
-    const int TLw = 16 * c->w_tt;
-    dim3 grid((unsigned)((c->k + TLw - 1) / TLw), (unsigned)((c->n + TLw - 1) / TLw), 1);
-    KL_GEMM_TT(c->w_tt, T, EpiW<T>, grid, c->stream, (int)c->n, (int)c->k,
+    dim3 grid((unsigned)((c->k + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), 1);
+    KL_GEMM_TT(T, EpiW<T>, grid, c->stream, (int)c->n, (int)c->k,
                (int)c->f, (const T *)qsrc, (int64_t)c->f, (int64_t)1, (const T *)c->H,
                (int64_t)1, (int64_t)c->f, (int)c->f + GK, (const DevState *)c->st, epi);
     HIPCHK(hipGetLastError());
@@ -334,12 +331,11 @@ void exact_N(klnmf_ctx *c, int widx, bool sum_slabs = true) {
         return;
     }
     EpiN<T> epi{(T *)c->Npart, c->f, c->k * c->f};
-    const int TLn = 16 * c->n_tt;
-    dim3 grid((unsigned)((c->f + TLn - 1) / TLn), (unsigned)((c->k + TLn - 1) / TLn), (unsigned)c->nsplit);
+    dim3 grid((unsigned)((c->f + GT - 1) / GT), (unsigned)((c->k + GT - 1) / GT), (unsigned)c->nsplit);
     EventPair ev{};
     if (c->prof_now) ev = begin_event(c, c->ev_col);
     if (c->x3_fused() && c->x3_ready && widx == (c->cur ^ 1)) x3_colpass(c);
-    else KL_GEMM_TT(c->n_tt, T, EpiN<T>, grid, c->stream, (int)c->k, (int)c->f,
+    else KL_GEMM_TT(T, EpiN<T>, grid, c->stream, (int)c->k, (int)c->f,
                (int)c->n, (const T *)c->W[widx], (int64_t)1, (int64_t)c->k,
                (const T *)c->Q, (int64_t)c->f, (int64_t)1, c->kchunk,
                (const DevState *)c->st, epi);
@@ -840,19 +836,8 @@ void check_v_overflow(klnmf_ctx *c) { raise_refusals(c, read_refusals(c)); }
 // formats: since round 4 fp8-tile numerators are sqrt(2) larger than 16-bit-tile ones); negative: this context's own.
 void begin_fp8_loop(klnmf_ctx *c, double sum_x_global, double cells_global, double nnz_global, int ok_all) {
     c->sw = DevSwitches::read();
-    c->q8_loop = false;
-    c->iter_in_loop = 0;
-    c->sr_launches = 0;
-    c->w8_meas = false;
-    c->stat_q8_tiles = 0;
-    c->stat_col8 = 0;
-    c->ne_loop = false;
-    c->last_row_ne = false;
-    c->mon_checks = 0;
-    c->mon_pending = false;
-    c->mon_dry_pending = false;
-    c->stat_mon_gave_up = false;
-    if (c->poll_inflight) { (void)hipEventSynchronize(c->poll_ev); c->poll_inflight = false; }      // (a loop abandoned without klnmf_loop_end)
+    if (c->poll_inflight) (void)hipEventSynchronize(c->poll_ev);      // (a loop abandoned without klnmf_loop_end)
+    static_cast<LoopState &>(*c) = LoopState();
     c->loop_sum_x_all = sum_x_global;              // (stored units; < 0: fetch_results takes this context's own sum)
     if (c->is_exact() || !c->q8_ok || ok_all == 0) return;
     if (c->W8 != nullptr && c->w8tab != nullptr) {
@@ -863,7 +848,6 @@ void begin_fp8_loop(klnmf_ctx *c, double sum_x_global, double cells_global, doub
         HIPCHK(hipMemcpyAsync(c->w8s, unit8.data(), unit8.size() * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->w8s_next, unit8.data(), unit8.size() * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        c->conv_ran = false;
     }
     if (c->sw.qtile != 0) {
         c->q8_loop = c->sw.qtile == 8;

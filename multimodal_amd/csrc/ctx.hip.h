@@ -8,7 +8,9 @@
 //   api_eval.hip     evaluation and introspection: reconstruction products (learner.py:80-84), distances, queries, profiling
 //   api_group.hip    a group of contexts (row shards, one device each, a device may repeat) driven from one host thread: the
 //                    exchange of group.hip.h between their streams, the loop of klnmf_group_run
-// This header: error handling, the device block cache, the development switches and the context itself.
+// This header: error handling, the device block cache, the development switches and the context itself -- its state in four
+// groups, one per lifetime (ContextState, ProblemState, LoopState, LoopRecord); plan.hip.h: the launch plan of a problem, the
+// value ProblemState is built on.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -222,160 +224,31 @@ struct DevSwitches {
     }
 };
 
-struct klnmf_ctx {
-    DevSwitches sw;
+#include "plan.hip.h"
+
+namespace klnmf_host {
+
+// The context's state in four groups, one per lifetime.  klnmf_ctx derives from all four (c->field everywhere); a reset is the
+// assignment of a default-constructed group, never a list of fields.
+// ---- as long as the context: untouched by klnmf_set_problem*
+//   * ratio_eps survives klnmf_set_problem* and is reset by klnmf_release_problem;
+//   * profile_every and profile_seq survive both calls; profiling survives klnmf_set_problem* and is cleared by
+//     klnmf_release_problem;
+//   * the communicator (comm, its stream, events and scratch) survives both.
+struct ContextState {
     int device = 0;
     int prec = KLNMF_PREC_F64;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     int cu_count = 256;
-
-    int64_t n = 0, f = 0, k = 0, cap = 0;
-    bool have_problem = false;
-    int cur = 0;          // index of the current W buffer
-    int loop_start_cur = 0;
-
-    // common device state
-    DevState *st = nullptr;
-    double *errors = nullptr;
-    double *loss_xchg = nullptr;
-    double2 *loss_red = nullptr;              // [kLossRedMax] pairs of the loss slices (k_slab_sum -> k_post; 16-bit modes)
-    std::vector<std::pair<void *, size_t>> allocs;      // (block, size class)
-
-    // exact modes (T = double or float)
-    void *V = nullptr, *W[2] = {nullptr, nullptr}, *H = nullptr, *Q = nullptr;
-    void *Npart = nullptr, *numer = nullptr;
-    double *loss_part = nullptr;
-    int64_t loss_part_count = 0;
-    int nsplit = 1, kchunk = 0;
-    int wsplit = 1, wchunk = 0;       // exact modes: feature chunks of the W rule's contraction (few rows), slabs in Wpart
-    int q_tt = 4, w_tt = 4, n_tt = 4; // exact modes: outputs per thread and axis of the three GEMMs (k_gemm: 4 = 64 x 64 tiles, 8 = 128 x 128)
-    void *Wpart = nullptr;
-
-    // CSR input in the exact modes (sparse.hip.h): structure of X in CSR and CSC order, ratio values, H^T
-    bool sparse = false;
-    int64_t nnz = 0;
-    int64_t *sp_indptr = nullptr, *sp_indices = nullptr, *csc_indptr = nullptr, *csc_rows = nullptr, *csc_perm = nullptr;
-    void *sp_data = nullptr, *sp_q = nullptr, *HT = nullptr;
-    double *sp_row_loss = nullptr, *sp_wpart = nullptr, *sp_prod = nullptr;
-    int64_t sp_nblk = 0;
-    // ... blocked for the L2 (sparseb.hip.h; k <= 512): int32 copies of the indices, column blocks of the CSR order and row blocks
-    // of the CSC order with their pointers, the slabs of partial sums
-    bool sp_blocked = false;
-    int sp_cb = 1, sp_rb = 1;                 // column blocks / row blocks
-    int64_t sp_cb_cols = 0, sp_rb_rows = 0;
-    int *sp_idx32 = nullptr, *csc_rows32 = nullptr, *csc_perm32 = nullptr;
-    int64_t *sp_blkptr = nullptr, *csc_blkptr = nullptr;      // [n][cb + 1], [f][rb + 1]
-    double *sp_loss_part = nullptr;           // [cb][n]
-    void *sp_G = nullptr, *sp_NT = nullptr;   // [cb][n][k], [rb][f][k]
-    int *sp_bad = nullptr;
-    int64_t *csc_work = nullptr;      // workspace of the device-side CSC build (csc.hip.h, CscWork: klnmf_upload_csr_rows)
-    double *hpart = nullptr;          // exact modes, long rows: [k][hseg_n] partial row sums of the H rule / of the CSR loss term
-    int hseg_n = 1; int64_t hseg = 0; // segments per dictionary row and their length (1: the one-block-per-row kernels)
-
-    // bf16 modes
-    int KT = 0, KP = 0, ks = 0;
-    int64_t n_pad = 0, f_pad = 0, w_rows = 0;
-    int nrt = 0, nct = 0, nct_used = 0, nst = 0, ncb = 0, nchunks = 0, stages_per_chunk = 0;
-    int row_chunks = 1, row_ct_chunk = 0;     // column-split update pass (few rows): chunks, column tiles per chunk
-    float *Gpart = nullptr;                   // [row_chunks][nrt * 32][KP] partial Q.H^T
-    // hybrid update pass (many rows): the workgroups of the last partial round run column-split (tail_chunks chunks of
-    // tail_ct_chunk column tiles each) so that they fill the chip; tail_wg = 0: none.  Gpart then holds the tail's slabs.
-    int tail_wg = 0, tail_chunks = 1, tail_ct_chunk = 0;
-    unsigned char *W8 = nullptr;              // e4m3 image of W_new for the fp8 x fp8 column pass (colq8x.hip.h; KLNMF_COL8=0: off)
-    float *w8s = nullptr;                     // [KP] power-of-two scales of the e4m3 image
-    bool w8_meas = false;                     // the maxima table holds a measurement of this loop
-    int64_t loss_parts() const {               // entries of loss_part2 an update pass writes
-        if (tail_wg > 0) return (int64_t)nrt + (int64_t)(tail_chunks - 1) * (nrt - tail_rt0());
-        return (int64_t)nrt * row_chunks;
-    }
-    int tail_rt0() const { return (((nrt + 7) / 8) - tail_wg) * 8; }
-    void *VtA = nullptr;          // V as 32 x 32 fp16 tiles in the row pass's accumulator order (k_tile_V)
-    unsigned char *Qt = nullptr;  // ratio tiles the row pass leaves for the column pass
-    // fp8 ratio tiles (1 B per element of V instead of the 16-bit operands) for the H rule.  q8_ok: the problem's shape
-    // allows them (klnmf_set_problem); q8_loop: this loop's data do (decided at the loop's entry); they are used from the
-    // loop's third iteration on (the first updates from W0 = V.H0^T can carry ratios far beyond fp8's range).
-    bool q8_ok = false, q8_loop = false;
-    int64_t iter_in_loop = 0;
-    // what the last loop actually ran (klnmf_query): iterations whose ratio tiles were fp8, whose column pass was fp8 x fp8
-    int64_t stat_q8_tiles = 0, stat_col8 = 0;
-    uint2 *q8_list = nullptr;                 // [kQ8ListCap] saturated ratio entries of the current iteration (colq.hip.h)
-    bool ne_ok = false;                       // the problem's shape has NE kernels (fp16 V, k <= 224, enough rows for fp8 ratio tiles)
-    bool ne_loop = false;                     // this loop's fp8-tile update passes drop the numerator's eps (NE kernels; begin_fp8_loop)
-    bool last_row_ne = false;                 // ... and the update pass just launched was one of them (its loss needs DevState.corr_eps)
-    // the saturation counters of the last loop as its end found them (DevState is reset by the next entry point)
-    int64_t stat_w8_sat = 0, stat_w8_fallbacks = 0, stat_q8_sat = 0, stat_q8_unfixed = 0;
-    // ---- the fp8 monitor (monitor.hip.h): partial sums of the monitored iteration; what k_post is to do with them; the last
-    // loop's record (klnmf_query / klnmf_query_f64)
-    float *mon_part = nullptr, *mon_spread = nullptr;
-    bool mon_pending = false;                 // this iteration's first summing launch turns the partial sums into the statistic
-    bool mon_dry_pending = false;             // ... and it was the dry run of the loop's second iteration: poll before the third
-    int mon_ncols = 0; float mon_noise_scale = 0.f;
-    int64_t mon_checks = 0, stat_mon_checks = 0, stat_mon_trips = 0;
-    double stat_mon_max = 0.0, stat_mon_dbg[3] = {0, 0, 0}, stat_mon_spread = 1.0;
-    bool stat_mon_gave_up = false;
+    std::vector<std::pair<void *, size_t>> allocs;      // (block, size class) of the current problem's device blocks
+    double ratio_eps = kEpsRatio;   // only the step API honours a non-default value
     // polls of the monitor's verdict (poll_fp8_overflow).  The dry run's poll synchronises (its answer decides the NEXT iteration's
     // kernels); every later one is deferred: the counts are copied to pinned host memory behind the monitored iteration, an event
     // marks the copy, and the answer is read one iteration later, when the event has long passed -- the stream never drains
     // (a synchronising poll cost a pipeline bubble plus a pageable read-back per check: 5 checks in bench.py's 40 timed iterations)
     void *poll_host = nullptr;                // pinned: a DevState or the two doubles of the loss exchange
     hipEvent_t poll_ev = nullptr;
-    bool poll_inflight = false, poll_agreed = false;
-    // the 16-bit mode's data condition (DESIGN.md section 6: below KL / sum(V) of about 2e-3 the f16 operands' own noise can pass 1e-4
-    // of the loss): sum of V over ALL shards as the loop's entry was given it (stored units; < 0: this context's own), and the
-    // last loop's final KL / sum(V) (klnmf_query_f64 KLNMF_QF_KL_OVER_SUM_V; < 0: no loop yet / exact mode)
-    double loop_sum_x_all = -1.0, stat_kl_over_sumv = -1.0;
-    // the refusal counters of DevState (v_overflow, op_range) change only on uploads and image measurements: they are read
-    // back (one copy + synchronisation) only when one of those happened since the last check
-    bool refusals_dirty = true;
-    // single-context fit loops: the loss reduction + stop decision of an iteration ride in the slab-sum launch behind the
-    // column pass (k_sum_partials_f32) instead of a launch of their own behind the row pass; set by piece_rowpass,
-    // consumed by the next fast_colpass.  KLNMF_LOSS_DEFER=0: off.
-    LossArgs pending_loss{nullptr, 0, 0.0, nullptr, 0, nullptr, 0.0, nullptr, 0};
-    double v_max = 0.0;          // the maximum announced with klnmf_set_v_max (0: none)
-    // fp8 ratio tiles in this iteration?  k > 256 (FUSED row pass, KSPLIT = 2 column pass) has only the fp8 x fp8 column pass
-    // for them: there the W image's scales must have been measured (the loop's second iteration does that)
-    bool q8() const { return q8_loop && iter_in_loop >= 2 && (!big || (W8 != nullptr && w8_meas)); }
-    float *W32[2] = {nullptr, nullptr};
-    opnd_t *Wb[2] = {nullptr, nullptr};
-    float *H32 = nullptr;
-    // ---- one launch behind the column pass (post.hip.h) ----
-    float *H32alt = nullptr;                  // the dictionary master is ping-pong there: k_post reads H32, writes H32alt, then they swap
-    int64_t loop_hswaps = 0;                  // H rules enqueued since the loop's entry (how many the device executed: n_done -- fetch_results)
-    float *loop_h0 = nullptr, *loop_h1 = nullptr;      // H32 / H32alt as the loop found them
-    unsigned *w8tab = nullptr;                // [kW8TabRows][KP] maxima of the conversion kernel (k_post: -> w8s_next, emptied)
-    float *w8s_next = nullptr;                // [KP] scales of the NEXT image: k_post writes them, then w8s / w8s_next swap
-    bool conv_ran = false;                    // this iteration's conversion ran: k_post derives the next scales
-
-    // Column parts of the H numerator.  `whole`: all columns as one part (layout [KP][f_pad], what every single-context loop
-    // and the exchange API use).  `parts[0 .. nparts_cfg)`: the split layout of loops on a communicator -- part p = a range of
-    // column blocks with its own slabs [nchunks][KP][ld] and numerator [KP][ld] (contiguous: one ncclAllReduce each), so that
-    // the all-reduce of part p overlaps the column pass of part p + 1 (KLNMF_COMM_PARTS, default 1 = no split)
-    struct PartCfg { int cb0, ncb, ct0, nct, col0, ncols, ld, nchunks, spc; int64_t numer_off, slab_off; };
-    PartCfg whole{}, parts[kPostMaxParts]{};
-    int nparts_cfg = 1;
-    bool piece_split = false, piece_use8 = false;      // loop in pieces: the numerator was produced in parts (klnmf_iter_colpass_part)
-    hipStream_t comm_stream = nullptr;        // all-reduces of the parts before the last one (overlap)
-    hipEvent_t ev_part[kPostMaxParts] = {}, ev_ar[kPostMaxParts] = {};
-    opnd_t *Ht4 = nullptr;
-    int kc = -1;                 // eps-carrying pad component of the ping-pong path (k_update_pack_H), -1: none
-    int kc_shape = -1;           // ... as the shape allows it; kc = kc_shape only while the carrier pair fits fp16 (choose_eps_carrier)
-    double *hsum = nullptr;
-    // per-component power-of-two scales of the fp16 operand images (mfma.hip.h, opnd_t), [KP] each: of the current images;
-    // hs-based (from the dictionary's row sums); the constant 2^-13 of a row-normalised dictionary; measured from a W
-    float *tcur = nullptr, *t_hs = nullptr, *t_unit = nullptr;
-    unsigned *wmax = nullptr;
-    bool images_measured = false;    // the current images carry measured scales: valid for one update (see opnd_t)
-    unsigned sr_launches = 0;        // row pass launches of the current loop (the seeds of the tiles' stochastic rounding)
-    bool w_is_init = false;          // the current W is W0 = V.H0^T of klnmf_init_W, untouched since: a dictionary set NOW still meets
-                                     // ratios of about f / k on its first update (the ratio scale of k_ratio_scale must stay on)
-    float *NpartF = nullptr, *numerF = nullptr;
-    double2 *loss_part2 = nullptr;
-
-    // profiling
-    double ratio_eps = kEpsRatio;   // only the step API honours a non-default value
-    double v_scale = 1.0;           // storage factor c of the 16-bit V (power of two)
-    bool v_uploaded = false;
 
     bool profiling = false;
     // every `profile_every`-th iteration of a loop has its row-pass / column-pass launches bracketed by HIP events (1: every one).
@@ -383,40 +256,154 @@ struct klnmf_ctx {
     // were 3.5 % of one rank's 0.65 ms shard iteration (profiles/r06_timelines_shard.txt), so bench.py samples every 4th
     int profile_every = 1;
     int64_t profile_seq = 0;
-    bool prof_now = false;           // this iteration's launches are bracketed (set by piece_rowpass)
     std::vector<EventPair> ev_row, ev_col, ev_tail;      // ev_tail: the column-split tail + slabs part of a hybrid row pass
 
     // row shards over the GPUs of a node (klnmf_comm_*, klnmf_run_sharded): this rank's RCCL communicator
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_size = 1;
     double *comm_scratch = nullptr;       // 8 doubles on the device, owned by the communicator (not by a problem)
+    hipStream_t comm_stream = nullptr;        // all-reduces of the parts before the last one (overlap)
+    hipEvent_t ev_part[kPostMaxParts] = {}, ev_ar[kPostMaxParts] = {};
+};
 
+// ---- as long as a problem: the plan (plan.hip.h: every shape-derived count), every device buffer, and what uploads and setters
+// leave on them.  Default-constructed by klnmf_set_problem* (behind free_all, before the new plan is stored) and by
+// klnmf_release_problem.
+struct ProblemState : ProblemPlan {
+    DevSwitches sw;               // as klnmf_set_problem* read them; read afresh at every loop entry
+    int64_t cap = 0;
+    bool have_problem = false;
+    int cur = 0;          // index of the current W buffer
+    // where W and the dictionary master stood at the loop's entry (loop_open; fetch_results): they point into THIS problem's buffers
+    int loop_start_cur = 0;
+    int64_t loop_hswaps = 0;                  // H rules enqueued since the loop's entry (how many the device executed: n_done -- fetch_results)
+    float *loop_h0 = nullptr, *loop_h1 = nullptr;      // H32 / H32alt as the loop found them
+
+    // common device state
+    DevState *st = nullptr;
+    double *errors = nullptr;
+    double *loss_xchg = nullptr;
+    double2 *loss_red = nullptr;              // [kLossRedMax] pairs of the loss slices (k_slab_sum -> k_post; 16-bit modes)
+
+    // exact modes (T = double or float)
+    void *V = nullptr, *W[2] = {nullptr, nullptr}, *H = nullptr, *Q = nullptr;
+    void *Npart = nullptr, *numer = nullptr;
+    double *loss_part = nullptr;
+    void *Wpart = nullptr;
+    float *x3_hs = nullptr, *x3_qr = nullptr;     // per-component H scales; per-row ratio scales of the column pass
+    unsigned *x3_xmax = nullptr;                  // per-component maxima of W_new qr (bit patterns of non-negative floats)
+    double *x3_loss = nullptr;                    // one loss partial per 64 rows
+
+    // CSR input in the exact modes (sparse.hip.h): structure of X in CSR and CSC order, ratio values, H^T
+    int64_t *sp_indptr = nullptr, *sp_indices = nullptr, *csc_indptr = nullptr, *csc_rows = nullptr, *csc_perm = nullptr;
+    void *sp_data = nullptr, *sp_q = nullptr, *HT = nullptr;
+    double *sp_row_loss = nullptr, *sp_wpart = nullptr, *sp_prod = nullptr;
+    // ... blocked for the L2 (sparseb.hip.h; k <= 512): int32 copies of the indices, column blocks of the CSR order and row blocks
+    // of the CSC order with their pointers, the slabs of partial sums
+    int *sp_idx32 = nullptr, *csc_rows32 = nullptr, *csc_perm32 = nullptr;
+    int64_t *sp_blkptr = nullptr, *csc_blkptr = nullptr;      // [n][cb + 1], [f][rb + 1]
+    double *sp_loss_part = nullptr;           // [cb][n]
+    void *sp_G = nullptr, *sp_NT = nullptr;   // [cb][n][k], [rb][f][k]
+    int *sp_bad = nullptr;
+    int64_t *csc_work = nullptr;      // workspace of the device-side CSC build (csc.hip.h, CscWork: klnmf_upload_csr_rows)
+    double *hpart = nullptr;          // exact modes, long rows: [k][hseg_n] partial row sums of the H rule / of the CSR loss term
+
+    // 16-bit mode
+    float *Gpart = nullptr;                   // [row_chunks][nrt * 32][KP] partial Q.H^T (hybrid update pass: the tail's slabs)
+    unsigned char *W8 = nullptr;              // e4m3 image of W_new for the fp8 x fp8 column pass (colq8x.hip.h; plan: w8)
+    float *w8s = nullptr;                     // [KP] power-of-two scales of the e4m3 image
+    void *VtA = nullptr;          // V as 32 x 32 fp16 tiles in the row pass's accumulator order (k_tile_V)
+    unsigned char *Qt = nullptr;  // ratio tiles the row pass leaves for the column pass
+    uint2 *q8_list = nullptr;                 // [kQ8ListCap] saturated ratio entries of the current iteration (colq.hip.h)
+    float *mon_part = nullptr, *mon_spread = nullptr;      // the fp8 monitor (monitor.hip.h): partial sums of the monitored iteration
+    float *W32[2] = {nullptr, nullptr};
+    opnd_t *Wb[2] = {nullptr, nullptr};
+    float *H32 = nullptr;
+    // ---- one launch behind the column pass (post.hip.h) ----
+    float *H32alt = nullptr;                  // the dictionary master is ping-pong there: k_post reads H32, writes H32alt, then they swap
+    unsigned *w8tab = nullptr;                // [kW8TabRows][KP] maxima of the conversion kernel (k_post: -> w8s_next, emptied)
+    float *w8s_next = nullptr;                // [KP] scales of the NEXT image: k_post writes them, then w8s / w8s_next swap
+    opnd_t *Ht4 = nullptr;
+    int kc = -1;                 // eps-carrying pad component of the ping-pong path (k_update_pack_H), -1: none; kc = kc_shape only
+                                 // while the carrier pair fits fp16 (choose_eps_carrier)
+    double *hsum = nullptr;
+    // per-component power-of-two scales of the fp16 operand images (mfma.hip.h, opnd_t), [KP] each: of the current images;
+    // hs-based (from the dictionary's row sums); the constant 2^-13 of a row-normalised dictionary; measured from a W
+    float *tcur = nullptr, *t_hs = nullptr, *t_unit = nullptr;
+    unsigned *wmax = nullptr;
+    float *NpartF = nullptr, *numerF = nullptr;
+    double2 *loss_part2 = nullptr;
+
+    double v_scale = 1.0;           // storage factor c of the 16-bit V (power of two)
+    double v_max = 0.0;          // the maximum announced with klnmf_set_v_max (0: none)
+    bool v_uploaded = false;
+    bool images_measured = false;    // the current images carry measured scales: valid for one update (see opnd_t)
+    bool w_is_init = false;          // the current W is W0 = V.H0^T of klnmf_init_W, untouched since: a dictionary set NOW still meets
+                                     // ratios of about f / k on its first update (the ratio scale of k_ratio_scale must stay on)
+    // the refusal counters of DevState (v_overflow, op_range) change only on uploads and image measurements: they are read
+    // back (one copy + synchronisation) only when one of those happened since the last check
+    bool refusals_dirty = true;
+};
+
+// ---- as long as a loop: default-constructed at every loop entry (begin_fp8_loop), and nowhere else -- q8_loop, ne_loop and the
+// iteration counts below answer klnmf_query on a context whose problem has been released or replaced, until the next loop entry.
+struct LoopState {
+    // fp8 ratio tiles: q8_loop: this loop's data allow them (decided at the loop's entry; q8_ok of the plan: the shape does); they
+    // are used from the loop's third iteration on (the first updates from W0 = V.H0^T can carry ratios far beyond fp8's range).
+    bool q8_loop = false;
+    int64_t iter_in_loop = 0;
+    // what the loop actually ran (klnmf_query): iterations whose ratio tiles were fp8, whose column pass was fp8 x fp8
+    int64_t stat_q8_tiles = 0, stat_col8 = 0;
+    bool stat_mon_gave_up = false;
+    bool w8_meas = false;                     // the maxima table holds a measurement of this loop
+    bool ne_loop = false;                     // this loop's fp8-tile update passes drop the numerator's eps (NE kernels; begin_fp8_loop)
+    bool last_row_ne = false;                 // ... and the update pass just launched was one of them (its loss needs DevState.corr_eps)
+    // the fp8 monitor (monitor.hip.h): what k_post is to do with the monitored iteration's partial sums
+    bool mon_pending = false;                 // this iteration's first summing launch turns the partial sums into the statistic
+    bool mon_dry_pending = false;             // ... and it was the dry run of the loop's second iteration: poll before the third
+    int mon_ncols = 0; float mon_noise_scale = 0.f;
+    int64_t mon_checks = 0;
+    bool poll_inflight = false, poll_agreed = false;
+    // the 16-bit mode's data condition (DESIGN.md section 6: below KL / sum(V) of about 2e-3 the f16 operands' own noise can pass 1e-4
+    // of the loss): sum of V over ALL shards as the loop's entry was given it (stored units; < 0: this context's own)
+    double loop_sum_x_all = -1.0;
+    // single-context fit loops: the loss reduction + stop decision of an iteration ride in the slab-sum launch behind the
+    // column pass (k_sum_partials_f32) instead of a launch of their own behind the row pass; set by piece_rowpass,
+    // consumed by the next fast_colpass.  KLNMF_LOSS_DEFER=0: off.
+    LossArgs pending_loss{nullptr, 0, 0.0, nullptr, 0, nullptr, 0.0, nullptr, 0};
+    bool conv_ran = false;                    // this iteration's conversion ran: k_post derives the next scales
+    bool piece_split = false, piece_use8 = false;      // loop in pieces: the numerator was produced in parts (klnmf_iter_colpass_part)
+    unsigned sr_launches = 0;        // row pass launches of the current loop (the seeds of the tiles' stochastic rounding)
+    bool x3_ready = false;           // Q, x3_qr and x3_xmax are the last fused row pass's (its column pass may run)
+    bool prof_now = false;           // this iteration's launches are bracketed (set by piece_rowpass)
+};
+
+// ---- the last loop's record as fetch_results wrote it (klnmf_query / klnmf_query_f64): never reset, overwritten whole by the next
+// fetch_results -- readable on a context whose problem has been released or replaced.  (DevState, where the counters come from,
+// is emptied by the next entry point.)
+struct LoopRecord {
+    int64_t stat_w8_sat = 0, stat_w8_fallbacks = 0, stat_q8_sat = 0, stat_q8_unfixed = 0;
+    int64_t stat_mon_checks = 0, stat_mon_trips = 0;
+    double stat_mon_max = 0.0, stat_mon_dbg[3] = {0, 0, 0}, stat_mon_spread = 1.0;
+    double stat_kl_over_sumv = -1.0;          // the final KL / sum(V) (KLNMF_QF_KL_OVER_SUM_V; < 0: no loop yet / exact mode)
+};
+
+}  // namespace klnmf_host
+
+struct klnmf_ctx : ContextState, ProblemState, LoopState, LoopRecord {
+    // fp8 ratio tiles in this iteration?  k > 256 (FUSED row pass, KSPLIT = 2 column pass) has only the fp8 x fp8 column pass
+    // for them: there the W image's scales must have been measured (the loop's second iteration does that)
+    bool q8() const { return q8_loop && iter_in_loop >= 2 && (!big || (W8 != nullptr && w8_meas)); }
     // the exact modes' storage, loop and kernels; KLNMF_PREC_BF16X3 is the fp32 side of them with the dense contractions on
     // the split-operand bf16 kernel (split3.hip.h); KLNMF_PREC_F16X3 the same storage and step kernels, its fit and transform
     // loop on the fused split-fp16 kernels where x3_fused() (f16x3.hip.h)
-    bool is_exact() const {
-        return prec == KLNMF_PREC_F64 || prec == KLNMF_PREC_F32 || prec == KLNMF_PREC_BF16X3 || prec == KLNMF_PREC_F16X3;
-    }
+    bool is_exact() const { return prec_is_exact(prec); }
     // fp32 storage (the exact modes other than f64)
     bool is_f32() const { return prec == KLNMF_PREC_F32 || prec == KLNMF_PREC_BF16X3 || prec == KLNMF_PREC_F16X3; }
     // KLNMF_PREC_F16X3 on dense input with k <= 256: the loop's row pass is k_rowpass_x3 and its column pass k_colpass_x3
     // (k > 256 and CSR input: the bf16x3 kernels / the fp32 sparse kernels)
-    bool x3_fused() const { return prec == KLNMF_PREC_F16X3 && !sparse && k <= F3_KMAX; }
-    float *x3_hs = nullptr, *x3_qr = nullptr;     // per-component H scales; per-row ratio scales of the column pass
-    unsigned *x3_xmax = nullptr;                  // per-component maxima of W_new qr (bit patterns of non-negative floats)
-    double *x3_loss = nullptr;                    // one loss partial per 64 rows
-    bool x3_ready = false;                        // Q, x3_qr and x3_xmax are the last fused row pass's (its column pass may run)
-    // fp8 ratio tiles from how many rows per context?  Their e4m3 rounding only enters the H numerator, a sum over all rows
-    // (relative error ~ 0.036 sqrt(2 / n)); measured against the fp64 oracle (scripts/fp8_rows_survey.py,
-    // profiles/r03_fp8_rows_survey.txt): final-KL deviation 1.7e-5 .. 3.5e-5 from 4096 to 50 000 rows at k = 50, 6.7e-6 .. 1.5e-5
-    // at k = 200 -- a floor that does not depend on n, a fifth of the 1e-4 budget.  k <= 224: from 32 769 rows, where the
-    // column-split update pass of small problems no longer runs (round 2: 65 536; C2 = 50 000 rows now qualifies).
-    // 256 < k <= 512: 65 536, the size fixture G14 pins.
-    static bool row_chunks_possible_q8(int64_t n, bool big_k) { return big_k ? n >= 65536 : n > 32768; }
-    // ping-pong row pass (mfma4.hip.h): fp16-stored V; 8-wave workgroups for KT <= 7, 4-wave ones for 10 <= KT <= 16 (even)
-    // big: 224 < k <= 512 (KT = 8 .. 16, even): 4-wave workgroups, FUSED order, component-split column passes
-    bool big = false;
-    size_t esize() const { return prec == KLNMF_PREC_F64 ? 8 : 4; }
+    bool x3_fused() const { return x3; }
+    size_t esize() const { return prec_esize(prec); }
 
     void *dalloc(size_t bytes, bool zero = true) {
         if (bytes == 0) bytes = 16;
@@ -435,17 +422,17 @@ struct klnmf_ctx {
         if (zero) HIPCHK(hipMemsetAsync(p, 0, bytes, stream));
         return p;
     }
-    void free_all() {      // callers have synchronised the stream: no kernel of this context still touches the blocks
+    // The problem ends: its blocks go back to the cache and its state to the defaults.  Callers have synchronised the stream: no
+    // kernel of this context still touches the blocks.
+    void free_all() {
         for (auto &b : allocs)
             if (!g_block_cache.give(device, b.second, b.first)) (void)hipFree(b.first);
         allocs.clear();
-        for (auto &e : ev_row) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-        for (auto &e : ev_col) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-        for (auto &e : ev_tail) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-        ev_tail.clear();
-        ev_row.clear();
-        ev_col.clear();
-        have_problem = false;
+        for (auto *v : {&ev_row, &ev_col, &ev_tail}) {
+            for (auto &e : *v) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
+            v->clear();
+        }
+        static_cast<ProblemState &>(*this) = ProblemState();
     }
 };
 
@@ -468,12 +455,6 @@ inline void comm_release(klnmf_ctx *c) {
 inline void need_problem(klnmf_ctx *c) {
     use(c);
     if (!c->have_problem) fail(KLNMF_ERR_ARG, "klnmf_set_problem has not been called");
-}
-
-// A single-context fit loop (piece_fit_tail) applies the H rule straight from the row chunks' slabs (k_update_H_slabs) where that
-// is a few thousand loads per row; beyond, and in segments, the slabs are summed first (k_sum_partials).  KLNMF_Q_EX_H_FROM_SLABS.
-inline bool h_from_slabs(const klnmf_ctx *c) {
-    return !c->sparse && c->hseg_n == 1 && (int64_t)c->nsplit * c->f <= 8192;
 }
 
 inline EventPair begin_event(klnmf_ctx *c, std::vector<EventPair> &v) {

@@ -67,7 +67,7 @@ F16_MIN_KL_OVER_SUM_V = 3e-3
 
 MAX_K_F16X3 = 256         # the fused split-fp16 loop of 'f16x3' holds a workgroup's Q.H^T of all components in registers
 MAX_K_MFMA = 512          # the 16-bit MFMA kernels hold a wave's accumulators of all components in registers: k <= 512
-MAX_ROWS_EXACT = 65535 * 64   # the exact modes' row tiles ride on gridDim.y (csrc/api_context.hip: KLNMF_ERR_UNSUPP beyond)
+MAX_ROWS_EXACT = 65535 * 64   # the exact modes' row tiles ride on gridDim.y (csrc/plan.hip.h: KLNMF_ERR_UNSUPP beyond)
 
 # CSR input on a device list runs over row shards (`_fit_group_csr`) when every shard holds at least this many stored entries;
 # below, on the list's first device.  At the measured fp64 rate of the sparse loop (about 8.5 G entries/s: README) 2^20 entries

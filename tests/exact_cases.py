@@ -2,14 +2,15 @@
 them, and a chunked fp64 restatement of the reference's dense update.
 
 `exact_regime` is klnmf_set_problem's size rule for a dense problem in KLNMF_PREC_F64 / F32 / BF16X3 / F16X3
-(csrc/api_context.hip) and piece_fit_tail's choice of H-rule route (csrc/ctx.hip.h, h_from_slabs):
+(csrc/plan.hip.h, plan_dense_exact) and piece_fit_tail's choice of H-rule route (h_from_slabs there):
   * the H numerator W^T.Q in `nsplit` row chunks of `kchunk` rows (a multiple of GK = 16), one slab per chunk (EpiN);
   * the W rule's Q.H^T in one piece (EpiW) or in `wsplit` feature chunks of `wchunk` columns (EpiWpart + k_wrule_exact);
   * the H rule in `hseg_n` segments of 4096 columns (k_update_H_part + k_update_H_norm) from f = 16 384 on;
   * a single-context fit loop applies the H rule straight from the slabs (k_update_H_slabs) while nsplit * f <= 8192 and
     the rule is in one segment, otherwise from their sum (k_sum_partials + k_update_H).
-tests/test_exact_cpu.py checks that CASES reach every route and edge at 256 CUs (the MI355X); tests/test_exact_gpu.py
-checks that the library reports the regime this module computes for the device's own CU count.
+tests/test_exact_cpu.py checks that CASES reach every route and edge at 256 CUs (the MI355X) and that the library's own rule
+(klnmf_plan_query: no device needed) gives what this module computes; tests/test_exact_gpu.py checks the same on a context,
+for the device's own CU count.
 
 `ref_step` / `ref_fit` are the oracle's dense update (oracle/klnmf_oracle.py, nmf.py:212-222, 232-257, 297-351) in fp64
 with the W rule's contraction summed over the same feature chunks and the H numerator over the same row chunks as the

@@ -1,9 +1,13 @@
 """CPU side of the dense exact-mode tests (tests/test_exact_gpu.py): the regime query's constants, the host rule's
 restatement and the routes the case list reaches, and the chunked fp64 reference.  No GPU needed."""
+import json
 import os
 import re
+import subprocess
+import sys
 
 import numpy as np
+import pytest
 from numpy.testing import assert_allclose
 
 from multimodal_amd import _native
@@ -152,6 +156,79 @@ def test_the_wpart_cap_cannot_bind_at_256_cus():
         finally:
             ec.WPART_CAP = saved
         assert lifted == capped, (n, f, k)
+
+
+Q_REGIME = (_native.Q_EX_ROW_CHUNKS, _native.Q_EX_W_CHUNKS, _native.Q_EX_H_SEGMENTS, _native.Q_EX_H_FROM_SLABS)
+SWITCHES = ('KLNMF_EX_ROW_CHUNKS', 'KLNMF_EX_W_CHUNKS', 'KLNMF_EX_H_SEG')
+
+_PLAN_CHILD = '''
+import json, sys
+from multimodal_amd import _native as nat
+prec, n, f, k = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
+items = (nat.Q_EX_ROW_CHUNKS, nat.Q_EX_W_CHUNKS, nat.Q_EX_H_SEGMENTS, nat.Q_EX_H_FROM_SLABS)
+print(json.dumps([nat.plan_query(prec, n, f, k, q, cu_count=256) for q in items]))
+'''
+
+
+def plan_regime(prec, n, f, k):
+    return tuple(_native.plan_query(prec, n, f, k, q, cu_count=CU) for q in Q_REGIME)
+
+
+def test_the_library_plan_equals_the_restated_rule_at_256_cus(monkeypatch):
+    """klnmf_plan_query -- klnmf_set_problem's own rule (csrc/plan.hip.h), reached without a device -- against
+    exact_cases.query_regime: every case in both element sizes, every forced route (the switches through the environment of a
+    child process with KLNMF_DEV=1), a seeded sweep of random shapes, and the two shape refusals.  Equality throughout."""
+    for name in SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    for case in ec.CASES + [ec.MID]:
+        n, f, k = case[:3]
+        for prec, esize in (('f64', 8), ('f32', 4)):
+            assert plan_regime(prec, n, f, k) == ec.query_regime(n, f, k, CU, esize=esize), (prec, n, f, k)
+    # the other fp32-storage modes share f32's rule
+    for prec in ('bf16x3', 'f16x3'):
+        assert plan_regime(prec, *ec.MID) == ec.query_regime(*ec.MID, cu_count=CU, esize=4)
+    # forced routes
+    n, f, k = ec.MID
+    forced = ([('row_chunks', r) for r in ec.FORCED_ROW_CHUNKS] + [('w_chunks', w) for w in ec.FORCED_W_CHUNKS]
+              + [('h_seg', L) for L in ec.FORCED_H_SEG])
+    names = dict(zip(('row_chunks', 'w_chunks', 'h_seg'), SWITCHES))
+    for what, value in forced:
+        env = dict(os.environ)
+        for name in SWITCHES:
+            env.pop(name, None)
+        env['KLNMF_DEV'] = '1'
+        env[names[what]] = str(value)
+        for prec, esize in (('f64', 8), ('f32', 4)):
+            out = subprocess.run([sys.executable, '-c', _PLAN_CHILD, prec, str(n), str(f), str(k)], cwd=ROOT, env=env,
+                                 stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=180)
+            assert out.returncode == 0, out.stderr.decode(errors='replace')[-2000:]
+            got = tuple(json.loads(out.stdout.decode().strip().splitlines()[-1]))
+            want = ec.query_regime(n, f, k, CU, esize=esize, **{what: value})
+            assert got == want, (what, value, prec)
+            assert got != ec.query_regime(n, f, k, CU, esize=esize)          # the switch was honoured
+    # a seeded sweep: n <= 65535 * 64, f <= 40 000, k <= 1100 (log-uniform n, so that small and large row counts both occur)
+    rng = np.random.default_rng(20240)
+    count = 0
+    for _ in range(2500):
+        n = int(min(ec.ROWS_MAX, np.exp(rng.uniform(0, np.log(ec.ROWS_MAX)))))
+        f = int(rng.integers(1, 40001))
+        k = int(rng.integers(1, 1101))
+        for prec, esize in (('f64', 8), ('f32', 4)):
+            assert plan_regime(prec, n, f, k) == ec.query_regime(n, f, k, CU, esize=esize), (prec, n, f, k)
+        count += 1
+    assert count >= 2000
+    # the refusals of the shape: the exact modes' row limit, the 16-bit mode's component limit
+    for prec in ('f64', 'f32', 'bf16x3', 'f16x3'):
+        assert plan_regime(prec, *ec.LARGEST_N)[0] >= 1
+        with pytest.raises(_native.NativeError) as err:
+            plan_regime(prec, ec.ROWS_MAX + 1, 3, 2)
+        assert err.value.code == _native.ERR_UNSUPP and '65535 x 64 rows' in str(err.value)
+    assert _native.plan_query('f16', 300, 700, 512, _native.Q_RATIO_TILE_BYTES, cu_count=CU) == 2
+    with pytest.raises(_native.NativeError) as err:
+        _native.plan_query('f16', 300, 700, 513, _native.Q_RATIO_TILE_BYTES, cu_count=CU)
+    assert err.value.code == _native.ERR_UNSUPP and 'k > 512' in str(err.value)
+    # a 16-bit-mode problem has no exact regime
+    assert plan_regime('f16', *ec.MID) == (0, 0, 0, 0)
 
 
 def test_chunked_reference_equals_the_oracle():

@@ -36,6 +36,48 @@ def test_library_exports_every_declared_symbol():
     assert lib.klnmf_version() == 100
 
 
+def _csrc(name):
+    with open(os.path.join(ROOT, 'multimodal_amd', 'csrc', name)) as fh:
+        return fh.read()
+
+
+def test_problem_counts_are_assigned_by_the_plan_alone():
+    """Every shape-derived count of a problem is a field of ProblemPlan (csrc/plan.hip.h) and reaches the context as one
+    assignment of the whole plan: api_context.hip assigns none of them, and the hand-written reset lists are gone."""
+    plan = _csrc('plan.hip.h')
+    counts = ('nsplit kchunk wsplit wchunk hseg hseg_n loss_part_count sp_nblk sp_blocked sp_cb sp_rb sp_cb_cols sp_rb_rows KT KP ks '
+              'big n_pad f_pad w_rows nrt nct nct_used ncb nchunks stages_per_chunk q8_ok ne_ok kc_shape row_chunks row_ct_chunk '
+              'tail_wg tail_chunks tail_ct_chunk nparts_cfg whole sparse nnz n f k').split()
+    for name in counts:
+        assert re.search(r'\b%s\b' % name, plan[plan.index('struct ProblemPlan'):plan.index('inline bool h_from_slabs')]), name
+    pattern = re.compile(r'c->(%s)\s*=[^=]' % '|'.join(counts))
+    for unit in ('api_context.hip', 'api_loop.hip', 'api_eval.hip', 'api_comm.hip', 'api_group.hip'):
+        assert not pattern.search(_csrc(unit)), (unit, pattern.search(_csrc(unit)).group(0))
+    ctx = _csrc('api_context.hip')
+    assert ctx.count('static_cast<ProblemPlan &>(*c) = plan;') == 1
+    # the dead parameters stay out
+    for unit in ('ctx.hip.h', 'plan.hip.h', 'api_context.hip', 'api_loop.hip'):
+        assert not re.search(r'\b(q_tt|w_tt|n_tt|nst)\b', _csrc(unit)), unit
+    # resets are assignments of a default-constructed group: one for the problem (free_all), one for the loop (begin_fp8_loop)
+    assert _csrc('ctx.hip.h').count('static_cast<ProblemState &>(*this) = ProblemState();') == 1
+    assert _csrc('api_loop.hip').count('static_cast<LoopState &>(*c) = LoopState();') == 1
+
+
+def test_the_development_switches_are_read_at_the_call_sites_that_remain_by_design():
+    sites = {}
+    for name in sorted(os.listdir(os.path.join(ROOT, 'multimodal_amd', 'csrc'))):
+        if name.endswith('.hip') or name.endswith('.hip.h'):
+            n = len(re.findall(r'DevSwitches::read\(\)', _csrc(name)))
+            if n:
+                sites[name] = n
+    assert sites == {
+        'api_context.hip': 1,       # set_problem: both klnmf_set_problem entry points, before the plan
+        'api_loop.hip': 1,          # begin_fp8_loop: every loop entry
+        'api_comm.hip': 1,          # comm_multi: KLNMF_COMM_SINGLE, asked outside problems and loops
+        'api_eval.hip': 1,          # klnmf_plan_query: as klnmf_set_problem reads them, without a context
+    }
+
+
 def _no_gpu():
     try:
         import torch

@@ -23,6 +23,28 @@ def test_sparse_block_query_constants_match_the_header():
     assert not set(defined.values()) & set(others)
 
 
+def test_the_library_plan_gives_the_recorded_csr_block_counts(monkeypatch):
+    """klnmf_set_problem_sparse's block rule (csrc/plan.hip.h, reached without a device through klnmf_plan_query): at the bench
+    shape -- 20 000 x 110 000, 10 972 250 stored entries, k = 50, fp64 -- 4 column blocks and 3 row blocks, the figures DESIGN.md
+    section 3.5 records; k = 513 and a structure without entries run unblocked."""
+    def blocks(prec, n, f, k, nnz):
+        return tuple(_native.plan_query(prec, n, f, k, q, nnz=nnz) for q in (_native.Q_SP_COL_BLOCKS, _native.Q_SP_ROW_BLOCKS))
+    for name in ('KLNMF_SP_CB', 'KLNMF_SP_RB'):
+        monkeypatch.delenv(name, raising=False)
+    assert blocks('f64', 20000, 110000, 50, 10972250) == (4, 3)
+    assert blocks('f64', 20000, 110000, 513, 10972250) == (0, 0)
+    assert blocks('f64', 20000, 110000, 50, 0) == (0, 0)
+    assert blocks('f32', 20000, 110000, 513, 10972250) == (0, 0)
+    # the dense items of a CSR problem answer 0, as klnmf_query does
+    assert _native.plan_query('f64', 20000, 110000, 50, _native.Q_EX_ROW_CHUNKS, nnz=10972250) == 0
+    # CSR input runs in the exact modes only
+    try:
+        blocks('f16', 20000, 110000, 50, 10972250)
+        raise AssertionError('the 16-bit mode accepted a CSR plan')
+    except _native.NativeError as err:
+        assert err.code == _native.ERR_UNSUPP and 'CSR input runs in the exact modes' in str(err)
+
+
 def test_chunked_reference_equals_the_oracle():
     X = sc.designed_csr(141, 150, 1, 1, seed=5)
     X.data[5] = 0.0                  # an explicit zero: dropped by both (nmf.py:66)
