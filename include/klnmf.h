@@ -120,6 +120,25 @@ int klnmf_upload_V_device(klnmf_ctx *ctx, const float *dsrc,
 int klnmf_upload_V_device_rows(klnmf_ctx *ctx, const float *dsrc, const int64_t *drow_idx,
                                int64_t rows, int64_t cols, int64_t ld,
                                int64_t row0, int64_t col0, double scale);
+/* Weights on the cost function (nmf.py:159-175: `weights`, "used as coefficients on each element of the data"; the
+ * reference ignores the argument): the sub-block Om[row0:row0+rows, col0:col0+cols] = src of an n x f buffer of the
+ * context's element type beside V, arguments as klnmf_upload_V without the scale.  The first upload of a problem takes
+ * the buffer filled with 1, so a caller uploads only the blocks that carry weights.  From then on the problem is
+ * weighted (klnmf_query KLNMF_Q_WEIGHTED): klnmf_run / klnmf_run_more, the loop in pieces, klnmf_update, klnmf_step_Q / _W /
+ * _H and klnmf_error minimise sum Om o d(V | W.H) (csrc/weighted.hip.h) -- the loss and the stop rule are the weighted
+ * ones, klnmf_step_Q leaves R = Om o Q, a rule's factor is 1 where its denominator (Om.H^T, W^T.Om) is 0, and the H rule
+ * normalises the rows as ever; klnmf_init_W stays W0 = V.H0^T.  Om >= 0 is the caller's contract.  Dense problems in
+ * KLNMF_PREC_F64 / KLNMF_PREC_F32 only: KLNMF_ERR_UNSUPP on a CSR problem and in every other precision, and where a
+ * weighted context enters a loop on a communicator or a group (klnmf_run_sharded, klnmf_loop_begin*_sharded / _agreed,
+ * klnmf_group_create / _run), whose exchange carries no denominator, and where weights are uploaded while such a loop is
+ * open (until klnmf_loop_end).  The weighted loss is available through klnmf_error (and the loops' records) only:
+ * klnmf_loss_terms stays refused in the exact modes, weighted or not.  klnmf_set_problem* and klnmf_release_problem drop
+ * the weights with the problem. */
+int klnmf_upload_weights(klnmf_ctx *ctx, const void *src, int dtype,
+                         int64_t rows, int64_t cols, int64_t ld,
+                         int64_t row0, int64_t col0);
+/* Drop the weights (nmf.py:159-175: back to the reference's unweighted cost): the problem runs the unweighted kernels again. */
+int klnmf_clear_weights(klnmf_ctx *ctx);
 /* Dictionary [k,f], C order (nmf.py:149-155 `_init_dictionary`, learner.py:13
  * `components_ = dictionary`). */
 int klnmf_set_H(klnmf_ctx *ctx, const void *src, int dtype);
@@ -393,6 +412,8 @@ int klnmf_all_distances_device(int device, int dtype, int metric, int64_t na, in
 #define KLNMF_Q_EX_W_CHUNKS       17
 #define KLNMF_Q_EX_H_SEGMENTS     18
 #define KLNMF_Q_EX_H_FROM_SLABS   19
+/*   KLNMF_Q_WEIGHTED         1 if the current problem holds weights (klnmf_upload_weights), 0 otherwise or with no problem */
+#define KLNMF_Q_WEIGHTED          20
 int klnmf_query(klnmf_ctx *ctx, int what, int64_t *value);
 /* The launch plan of a problem without a context or a device (replaces nothing of the reference): what klnmf_query would answer
  * right after klnmf_set_problem(n, f, k) -- with nnz >= 0 after klnmf_set_problem_sparse(n, f, k, nnz) -- on a context of `precision`

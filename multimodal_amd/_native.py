@@ -50,6 +50,8 @@ SIGNATURES = {
     'klnmf_reset_V': (_c.c_int, [_ctx_p]),
     'klnmf_upload_V': (_c.c_int, [_ctx_p, _c.c_void_p, _c.c_int, _i64, _i64, _i64,
                                   _i64, _i64, _c.c_double]),
+    'klnmf_upload_weights': (_c.c_int, [_ctx_p, _c.c_void_p, _c.c_int, _i64, _i64, _i64, _i64, _i64]),
+    'klnmf_clear_weights': (_c.c_int, [_ctx_p]),
     'klnmf_upload_V_device_rows': (_c.c_int, [_ctx_p, _c.c_void_p, _c.c_void_p, _i64, _i64, _i64, _i64, _i64,
                                               _c.c_double]),
     'klnmf_upload_V_device': (_c.c_int, [_ctx_p, _c.c_void_p, _i64, _i64, _i64, _i64,
@@ -254,6 +256,7 @@ Q_MON_CHECKS, Q_MON_TRIPS, Q_MON_GAVE_UP = 10, 11, 12
 Q_FP8_POLL_DUE = 13
 Q_SP_COL_BLOCKS, Q_SP_ROW_BLOCKS = 14, 15
 Q_EX_ROW_CHUNKS, Q_EX_W_CHUNKS, Q_EX_H_SEGMENTS, Q_EX_H_FROM_SLABS = 16, 17, 18, 19
+Q_WEIGHTED = 20
 QF_SUM_V, QF_NNZ_V, QF_MON_STAT, QF_MON_THRESHOLD = 0, 1, 2, 3
 QF_KL_OVER_SUM_V = 9
 
@@ -370,6 +373,26 @@ class Context(object):
         _check(self._lib.klnmf_upload_V(self._h, a.ctypes.data, _np_dtype_code(a),
                                         a.shape[0], a.shape[1], ld, row0, col0,
                                         float(scale)))
+
+    def upload_weights(self, block, row0=0, col0=0):
+        """Om[row0:, col0:] block = block (klnmf_upload_weights): weights on the cost function, >= 0.  The first call of a
+        problem makes it weighted, with every weight not uploaded equal to 1; dense problems in 'f64' / 'f32' only."""
+        a = np.asarray(block)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.ndim != 2:
+            raise ValueError("2-D block expected")
+        if a.strides[1] != a.itemsize or a.strides[0] % a.itemsize or a.strides[0] < a.shape[1] * a.itemsize:
+            a = np.ascontiguousarray(a)
+        ld = a.strides[0] // a.itemsize
+        _check(self._lib.klnmf_upload_weights(self._h, a.ctypes.data, _np_dtype_code(a), a.shape[0], a.shape[1], ld, row0, col0))
+
+    def clear_weights(self):
+        _check(self._lib.klnmf_clear_weights(self._h))
+
+    def weighted(self):
+        """The current problem holds weights (klnmf_query KLNMF_Q_WEIGHTED)."""
+        return bool(self.query(Q_WEIGHTED))
 
     def upload_blocks(self, blocks, scales=None):
         """Upload hstack([s * b ...]) block by block (one fused scale/cast/place

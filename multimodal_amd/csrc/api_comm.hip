@@ -37,6 +37,7 @@ bool comm_multi(const klnmf_ctx *c) { return c->comm != nullptr && (c->comm_size
 // (a rank-local overflow, a rank-local operand range) are all-reduced (max) and every rank fails TOGETHER; the fp8 decision
 // is taken from the all-reduced sums, so that all ranks run the same kernels and N = 1 / N = 8 differ by summation order only.
 void comm_loop_entry(klnmf_ctx *c) {
+    refuse_weighted(c, "a loop on a communicator");      // (shape-like: every rank of a weighted fit holds weights and refuses alike)
     c->refusals_dirty = true;
     const Refusals mine = read_refusals(c);
     DevState ds{};

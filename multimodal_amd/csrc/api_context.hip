@@ -39,21 +39,23 @@ void fill_v_tiles(klnmf_ctx *c, void *tiles, size_t bytes) {
 }
 
 // ---------------------------------------------------------------- uploads ---
+// `om` (a weighted problem's weights, exact modes): the block goes to Om instead of V, and V's upload state is left alone
 template <typename S>
 void place_block(klnmf_ctx *c, const S *dsrc, int64_t rows, int64_t cols, int64_t ld, int64_t row0,
-                 int64_t col0, double scale, const int64_t *row_idx = nullptr) {
+                 int64_t col0, double scale, const int64_t *row_idx = nullptr, bool om = false) {
     const int64_t total = rows * cols;
     const int grid = grid_for(total, 256, 8192);
+    void *dst = om ? c->Om : c->V;
     switch (c->prec) {
         case KLNMF_PREC_F64:
             hipLaunchKernelGGL((k_place_V<double, S>), dim3(grid), dim3(256), 0, c->stream,
-                               (double *)c->V, c->f, dsrc, rows, cols, ld, row0, col0, scale, row_idx);
+                               (double *)dst, c->f, dsrc, rows, cols, ld, row0, col0, scale, row_idx);
             break;
         case KLNMF_PREC_F32:
         case KLNMF_PREC_BF16X3:
         case KLNMF_PREC_F16X3:
             hipLaunchKernelGGL((k_place_V<float, S>), dim3(grid), dim3(256), 0, c->stream,
-                               (float *)c->V, c->f, dsrc, rows, cols, ld, row0, col0, scale, row_idx);
+                               (float *)dst, c->f, dsrc, rows, cols, ld, row0, col0, scale, row_idx);
             break;
         default:
             hipLaunchKernelGGL((k_tile_V<S>), dim3(grid), dim3(256), 0, c->stream,
@@ -62,8 +64,37 @@ void place_block(klnmf_ctx *c, const S *dsrc, int64_t rows, int64_t cols, int64_
             break;
     }
     HIPCHK(hipGetLastError());
+    if (om) return;
     c->v_uploaded = true;
     c->refusals_dirty = true;
+}
+
+// a host block [rows, cols] (leading dimension ld) into V (or Om) through a bounded device staging buffer
+void upload_block(klnmf_ctx *c, const void *src, int dtype, int64_t rows, int64_t cols, int64_t ld, int64_t row0, int64_t col0,
+                  double scale, bool om) {
+    const size_t es = dt_size(dtype);
+    int64_t rows_per = (int64_t)((256ull << 20) / (es * (size_t)ld));
+    if (rows_per < 1) rows_per = 1;
+    if (rows_per > rows) rows_per = rows;
+    void *d = nullptr;
+    HIPCHK(hipMalloc(&d, (size_t)rows_per * ld * es + 16));
+    try {
+        for (int64_t r0 = 0; r0 < rows; r0 += rows_per) {
+            const int64_t rr = std::min(rows_per, rows - r0);
+            const size_t bytes = ((size_t)(rr - 1) * ld + cols) * es;
+            HIPCHK(hipMemcpyAsync(d, (const char *)src + (size_t)r0 * ld * es, bytes,
+                                  hipMemcpyHostToDevice, c->stream));
+            if (dtype == KLNMF_DT_F64)
+                place_block<double>(c, (const double *)d, rr, cols, ld, row0 + r0, col0, scale, nullptr, om);
+            else
+                place_block<float>(c, (const float *)d, rr, cols, ld, row0 + r0, col0, scale, nullptr, om);
+            HIPCHK(hipStreamSynchronize(c->stream));
+        }
+    } catch (...) {
+        (void)hipFree(d);
+        throw;
+    }
+    (void)hipFree(d);
 }
 
 void check_block(klnmf_ctx *c, int64_t rows, int64_t cols, int64_t ld, int64_t row0, int64_t col0) {
@@ -594,30 +625,59 @@ int klnmf_upload_V(klnmf_ctx *c, const void *src, int dtype, int64_t rows, int64
         need_problem(c);
         if (!src) fail(KLNMF_ERR_ARG, "null source");
         check_block(c, rows, cols, ld, row0, col0);
-        const size_t es = dt_size(dtype);
-        // stream the block through a bounded device staging buffer
-        int64_t rows_per = (int64_t)((256ull << 20) / (es * (size_t)ld));
-        if (rows_per < 1) rows_per = 1;
-        if (rows_per > rows) rows_per = rows;
-        void *d = nullptr;
-        HIPCHK(hipMalloc(&d, (size_t)rows_per * ld * es + 16));
-        try {
-            for (int64_t r0 = 0; r0 < rows; r0 += rows_per) {
-                const int64_t rr = std::min(rows_per, rows - r0);
-                const size_t bytes = ((size_t)(rr - 1) * ld + cols) * es;
-                HIPCHK(hipMemcpyAsync(d, (const char *)src + (size_t)r0 * ld * es, bytes,
-                                      hipMemcpyHostToDevice, c->stream));
-                if (dtype == KLNMF_DT_F64)
-                    place_block<double>(c, (const double *)d, rr, cols, ld, row0 + r0, col0, scale);
+        upload_block(c, src, dtype, rows, cols, ld, row0, col0, scale, false);
+    });
+}
+
+// Om[row0 + i, col0 + j] = src[i, j] (nmf.py:159-175: `weights`, which the reference documents and ignores).  The first upload
+// of a problem takes the buffer filled with 1 -- a caller uploads only the blocks that carry weights -- and the denominators'
+// slabs beside it; klnmf_set_problem* / klnmf_release_problem drop them with the problem (ProblemState).
+int klnmf_upload_weights(klnmf_ctx *c, const void *src, int dtype, int64_t rows, int64_t cols, int64_t ld,
+                         int64_t row0, int64_t col0) {
+    return guarded([&] {
+        need_problem(c);
+        if (c->sparse) fail(KLNMF_ERR_UNSUPP, "klnmf_upload_weights: CSR problems have no weighted kernels (the ratio lives on the stored entries only)");
+        if (c->prec != KLNMF_PREC_F64 && c->prec != KLNMF_PREC_F32)
+            fail(KLNMF_ERR_UNSUPP, "klnmf_upload_weights: the weighted kernels exist in KLNMF_PREC_F64 and KLNMF_PREC_F32 only");
+        if (!src) fail(KLNMF_ERR_ARG, "null source");
+        if (dtype != KLNMF_DT_F64 && dtype != KLNMF_DT_F32) fail(KLNMF_ERR_ARG, "unknown dtype");
+        if (c->sharded_loop)
+            fail(KLNMF_ERR_UNSUPP, "klnmf_upload_weights: a loop over row shards is open on this context (klnmf_loop_begin on a communicator, "
+                                   "klnmf_loop_begin_sharded / _agreed) and its exchange carries no denominator; klnmf_loop_end first");
+        check_block(c, rows, cols, ld, row0, col0);
+        const size_t es = c->esize(), n = (size_t)c->n, f = (size_t)c->f, k = (size_t)c->k;
+        if (!c->weighted()) {
+            HIPCHK(hipStreamSynchronize(c->stream));
+            void *om = nullptr;
+            try {
+                om = c->dalloc(n * f * es, false);
+                c->Dpart = c->dalloc((size_t)c->nsplit * k * f * es);
+                c->denom = c->dalloc(k * f * es);
+                if (c->wsplit > 1) c->WDpart = c->dalloc((size_t)c->wsplit * n * k * es);
+                const int64_t count = c->n * c->f;
+                if (c->prec == KLNMF_PREC_F64)
+                    hipLaunchKernelGGL((k_fill<double>), dim3(grid_for(count, 256, 8192)), dim3(256), 0, c->stream, (double *)om, count, 1.0);
                 else
-                    place_block<float>(c, (const float *)d, rr, cols, ld, row0 + r0, col0, scale);
-                HIPCHK(hipStreamSynchronize(c->stream));
+                    hipLaunchKernelGGL((k_fill<float>), dim3(grid_for(count, 256, 8192)), dim3(256), 0, c->stream, (float *)om, count, 1.0f);
+                HIPCHK(hipGetLastError());
+            } catch (...) {                     // all or nothing: a failed first upload leaves the problem unweighted
+                (void)hipStreamSynchronize(c->stream);
+                c->dfree(c->Dpart); c->dfree(c->denom); c->dfree(c->WDpart); c->dfree(om);
+                throw;
             }
-        } catch (...) {
-            (void)hipFree(d);
-            throw;
+            c->Om = om;
         }
-        (void)hipFree(d);
+        if (rows == 0 || cols == 0) return;
+        upload_block(c, src, dtype, rows, cols, ld, row0, col0, 1.0, true);
+    });
+}
+
+int klnmf_clear_weights(klnmf_ctx *c) {
+    return guarded([&] {
+        need_problem(c);
+        if (!c->weighted()) return;
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->dfree(c->Om); c->dfree(c->Dpart); c->dfree(c->denom); c->dfree(c->WDpart);
     });
 }
 

@@ -210,6 +210,7 @@ int klnmf_group_create(klnmf_group **out, klnmf_ctx *const *ctxs, int n) {
             if (c->f != c0->f || c->k != c0->k || c->prec != c0->prec || c->cap != c0->cap)
                 fail(KLNMF_ERR_ARG, "klnmf_group_create: shard " + std::to_string(r) + " differs from shard 0 in f, k, precision or capacity");
             if (c->comm != nullptr) fail(KLNMF_ERR_ARG, "klnmf_group_create: shard " + std::to_string(r) + " holds an RCCL communicator");
+            refuse_weighted(c, "klnmf_group_create");
         }
         klnmf_group *g = new klnmf_group();
         try {
@@ -271,6 +272,7 @@ int klnmf_group_run(klnmf_group *g, int64_t n_total, int64_t max_iter, int fit, 
         int64_t rows = 0;
         for (int r = 0; r < N; ++r) {
             need_problem(g->ctxs[r]);
+            refuse_weighted(g->ctxs[r], "klnmf_group_run");
             rows += g->ctxs[r]->n;
             if (g->ctxs[r]->loss_xchg != g->loss[r])
                 fail(KLNMF_ERR_ARG, "klnmf_group_run: shard " + std::to_string(r) + " was given another problem since klnmf_group_create");

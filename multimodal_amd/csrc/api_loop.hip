@@ -195,10 +195,90 @@ void sparse_Q(klnmf_ctx *c, int write_q, double eps, const DecideArgs &dec) {
         hipLaunchKernelGGL((k_gemm<T, EPI, 4, true>), grid, dim3(256), 0, stream, __VA_ARGS__);                     \
     } while (0)
 
+// ------------------------------------------------------- weighted pieces ---
+// A weighted problem (c->weighted(): klnmf_upload_weights; dense, KLNMF_PREC_F64 / F32) takes the kernels of weighted.hip.h on
+// the unweighted plan's routes; the branch is here, on the host, and no unweighted kernel knows of it.
+template <typename T>
+void weighted_Q(klnmf_ctx *c, int write_q, double eps, const DecideArgs &dec) {
+    EpiQw<T> epi{(const T *)c->V, (const T *)c->Om, (T *)c->Q, c->f, c->loss_part, write_q, 0.0, (T)eps};
+    dim3 grid((unsigned)((c->f + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), 1);
+    EventPair ev{};
+    if (c->prof_now) ev = begin_event(c, c->ev_row);
+    hipLaunchKernelGGL((k_gemm<T, EpiQw<T>, 4, true>), grid, dim3(256), 0, c->stream, (int)c->n, (int)c->f, (int)c->k,
+                       (const T *)c->W[c->cur], (int64_t)c->k, (int64_t)1, (const T *)c->H, (int64_t)c->f, (int64_t)1,
+                       (int)c->k + GK, (const DevState *)c->st, epi);
+    HIPCHK(hipGetLastError());
+    if (c->prof_now) HIPCHK(hipEventRecord(ev.b, c->stream));
+    hipLaunchKernelGGL(k_sum_doubles, dim3(1), dim3(1024), 0, c->stream, (const double *)c->loss_part, (int64_t)grid.x * grid.y,
+                       c->loss_xchg, (const DevState *)c->st, dec);
+    HIPCHK(hipGetLastError());
+}
+
+// W_new = W * (R.H^T) / (Om.H^T): form A of k_gemm_dual, the tile of H^T shared (few rows: feature chunks, two slab sets)
+template <typename T>
+void weighted_W(klnmf_ctx *c) {
+    dim3 grid((unsigned)((c->k + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), (unsigned)c->wsplit);
+    if (c->wsplit > 1) {
+        EpiW2part<T> epip{(T *)c->Wpart, (T *)c->WDpart, c->k, c->n * c->k};
+        hipLaunchKernelGGL((k_gemm_dual<T, EpiW2part<T>, true>), grid, dim3(256), 0, c->stream, (int)c->n, (int)c->k, (int)c->f,
+                           (const T *)c->Q, (int64_t)c->f, (int64_t)1, (const T *)c->H, (int64_t)1, (int64_t)c->f,
+                           (const T *)c->Om, c->wchunk, (const DevState *)c->st, epip);
+        HIPCHK(hipGetLastError());
+        const int64_t count = c->n * c->k;
+        hipLaunchKernelGGL((k_wrule_exact_w<T>), dim3(grid_for(count)), dim3(256), 0, c->stream, (const T *)c->Wpart,
+                           (const T *)c->WDpart, c->wsplit, count, (const T *)c->W[c->cur], (T *)c->W[c->cur ^ 1],
+                           (const DevState *)c->st);
+        HIPCHK(hipGetLastError());
+        return;
+    }
+    EpiW2<T> epi{(const T *)c->W[c->cur], (T *)c->W[c->cur ^ 1], c->k};
+    hipLaunchKernelGGL((k_gemm_dual<T, EpiW2<T>, true>), grid, dim3(256), 0, c->stream, (int)c->n, (int)c->k, (int)c->f,
+                       (const T *)c->Q, (int64_t)c->f, (int64_t)1, (const T *)c->H, (int64_t)1, (int64_t)c->f,
+                       (const T *)c->Om, (int)c->f + GK, (const DevState *)c->st, epi);
+    HIPCHK(hipGetLastError());
+}
+
+// (W[widx]^T.R, W[widx]^T.Om) per row chunk: form B of k_gemm_dual, the tile of W^T shared
+template <typename T>
+void weighted_N(klnmf_ctx *c, int widx, bool sum_slabs) {
+    EpiN2<T> epi{(T *)c->Npart, (T *)c->Dpart, c->f, c->k * c->f};
+    dim3 grid((unsigned)((c->f + GT - 1) / GT), (unsigned)((c->k + GT - 1) / GT), (unsigned)c->nsplit);
+    EventPair ev{};
+    if (c->prof_now) ev = begin_event(c, c->ev_col);
+    hipLaunchKernelGGL((k_gemm_dual<T, EpiN2<T>, false>), grid, dim3(256), 0, c->stream, (int)c->k, (int)c->f, (int)c->n,
+                       (const T *)c->W[widx], (int64_t)1, (int64_t)c->k, (const T *)c->Q, (int64_t)c->f, (int64_t)1,
+                       (const T *)c->Om, c->kchunk, (const DevState *)c->st, epi);
+    HIPCHK(hipGetLastError());
+    if (c->prof_now) HIPCHK(hipEventRecord(ev.b, c->stream));
+    if (!sum_slabs) return;
+    const int64_t count = c->k * c->f;
+    hipLaunchKernelGGL((k_sum_partials_w<T>), dim3(grid_for(count)), dim3(256), 0, c->stream, (const T *)c->Npart,
+                       (const T *)c->Dpart, (T *)c->numer, (T *)c->denom, count, c->nsplit, (const DevState *)c->st);
+    HIPCHK(hipGetLastError());
+}
+
+template <typename T>
+void weighted_H(klnmf_ctx *c, bool from_slabs) {
+    if (from_slabs) {
+        hipLaunchKernelGGL((k_update_H_slabs_w<T>), dim3((unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H, (const T *)c->Npart,
+                           (const T *)c->Dpart, c->nsplit, c->k * c->f, c->f, (const DevState *)c->st);
+    } else if (c->hseg_n > 1) {
+        hipLaunchKernelGGL((k_update_H_part_w<T>), dim3((unsigned)c->hseg_n, (unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
+                           (const T *)c->numer, (const T *)c->denom, c->f, c->hseg, c->hpart, (const DevState *)c->st);
+        hipLaunchKernelGGL((k_update_H_norm<T>), dim3((unsigned)c->hseg_n, (unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
+                           c->f, c->hseg, (const double *)c->hpart, (const DevState *)c->st);
+    } else {
+        hipLaunchKernelGGL((k_update_H_w<T>), dim3((unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H, (const T *)c->numer,
+                           (const T *)c->denom, c->f, (const DevState *)c->st);
+    }
+    HIPCHK(hipGetLastError());
+}
+
 // dec.on: the stop rule rides in the one-block loss reduction (single-context loops: no k_decide launch)
 template <typename T>
 void exact_Q(klnmf_ctx *c, int write_q, double eps = kEpsRatio, DecideArgs dec = DecideArgs{0, nullptr, 0.0, nullptr, 0}) {
     if (c->sparse) { sparse_Q<T>(c, write_q, eps, dec); return; }
+    if (c->weighted()) { weighted_Q<T>(c, write_q, eps, dec); return; }
     if (write_q) c->x3_ready = false;
     EpiQ<T> epi{(const T *)c->V, (T *)c->Q, c->f, c->loss_part, write_q, 0.0, (T)eps};
     dim3 grid((unsigned)((c->f + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), 1);
@@ -279,6 +359,7 @@ void exact_W(klnmf_ctx *c, const void *qsrc, int multiply) {
         HIPCHK(hipGetLastError());
         return;
     }
+    if (c->weighted() && multiply) { weighted_W<T>(c); return; }      // (the start W0 = V.H0^T is unweighted)
     if (c->wsplit > 1) {     // few rows: contraction over f split into chunks (blockIdx.z), W rule from the slabs
         EpiWpart<T> epip{(T *)c->Wpart, c->k, c->n * c->k};
         dim3 gridp((unsigned)((c->k + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), (unsigned)c->wsplit);
@@ -330,6 +411,7 @@ void exact_N(klnmf_ctx *c, int widx, bool sum_slabs = true) {
         if (c->prof_now) HIPCHK(hipEventRecord(evs.b, c->stream));
         return;
     }
+    if (c->weighted()) { weighted_N<T>(c, widx, sum_slabs); return; }
     EpiN<T> epi{(T *)c->Npart, c->f, c->k * c->f};
     dim3 grid((unsigned)((c->f + GT - 1) / GT), (unsigned)((c->k + GT - 1) / GT), (unsigned)c->nsplit);
     EventPair ev{};
@@ -351,6 +433,7 @@ void exact_N(klnmf_ctx *c, int widx, bool sum_slabs = true) {
 
 template <typename T>
 void exact_H(klnmf_ctx *c, bool from_slabs = false) {
+    if (c->weighted()) { weighted_H<T>(c, from_slabs); return; }
     if (from_slabs) {             // (dense, short rows: the rule sums the row chunks' slabs itself -- the same bits, one launch less)
         hipLaunchKernelGGL((k_update_H_slabs<T>), dim3((unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H, (const T *)c->Npart,
                            c->nsplit, c->k * c->f, c->f, (const DevState *)c->st);
@@ -652,6 +735,14 @@ void piece_rowpass(klnmf_ctx *c, int fit, const double *fused_tol, bool defer_to
     HIPCHK(hipGetLastError());
 }
 
+// loops whose exchange carries the H numerator alone (communicator, group): a weighted context is refused at their entries
+void refuse_weighted(const klnmf_ctx *c, const char *who) {
+    if (c->weighted())
+        fail(KLNMF_ERR_UNSUPP, std::string(who) + ": the context holds weights (klnmf_upload_weights) and the exchange between row "
+                                   "shards carries no denominator of the weighted H rule; run the weighted problem in one context "
+                                   "or klnmf_clear_weights first");
+}
+
 void piece_decide(klnmf_ctx *c, double tol_abs) {
     hipLaunchKernelGGL(k_decide, dim3(1), dim3(1), 0, c->stream, c->st,
                        (const double *)c->loss_xchg, tol_abs, c->errors, c->cap);
@@ -903,6 +994,7 @@ int klnmf_loop_begin(klnmf_ctx *c) {
         need_problem(c);
         if (comm_multi(c)) {
             comm_loop_entry(c);                // the entry of klnmf_run_sharded: agreed refusals, agreed fp8 decision
+            c->sharded_loop = true;
         } else {
             check_v_overflow(c);
             begin_fp8_loop(c);
@@ -922,9 +1014,11 @@ int klnmf_loop_begin_sharded_nnz(klnmf_ctx *c, double sum_x_all, double cells_al
 int klnmf_loop_begin_agreed(klnmf_ctx *c, double sum_x_all, double cells_all, double nnz_all, int fp8_shape_all) {
     return guarded([&] {
         need_problem(c);
+        refuse_weighted(c, "klnmf_loop_begin_sharded");
         if (!(sum_x_all >= 0) || !(cells_all > 0)) fail(KLNMF_ERR_ARG, "klnmf_loop_begin_sharded: the all-reduced sums must be given");
         check_v_overflow(c);
         begin_fp8_loop(c, sum_x_all * c->v_scale, cells_all, nnz_all, fp8_shape_all);      // (the caller's sums are in the data's own units)
+        c->sharded_loop = true;
         loop_open(c);
     });
 }
@@ -995,6 +1089,7 @@ int klnmf_loop_end(klnmf_ctx *c, double *errors_out, int64_t *n_done, int *stopp
     return guarded([&] {
         need_problem(c);
         fetch_results(c, errors_out, n_done, stopped);
+        c->sharded_loop = false;
     });
 }
 

@@ -32,6 +32,7 @@
 #include "../../include/klnmf.h"
 #include "common.hip.h"
 #include "exact.hip.h"
+#include "weighted.hip.h"
 #include "split3.hip.h"
 #include "f16x3.hip.h"
 #include "sparseb.hip.h"
@@ -290,6 +291,10 @@ struct ProblemState : ProblemPlan {
     void *Npart = nullptr, *numer = nullptr;
     double *loss_part = nullptr;
     void *Wpart = nullptr;
+    // a weighted problem (weighted.hip.h; dense, KLNMF_PREC_F64 / F32): the n x f weights Om beside V -- allocated filled with 1
+    // by the first klnmf_upload_weights, dropped by klnmf_clear_weights -- and the denominators' slabs and sums, laid out as
+    // Npart / numer / Wpart are.  Om != nullptr IS "the current problem is weighted" (klnmf_query KLNMF_Q_WEIGHTED).
+    void *Om = nullptr, *Dpart = nullptr, *denom = nullptr, *WDpart = nullptr;
     float *x3_hs = nullptr, *x3_qr = nullptr;     // per-component H scales; per-row ratio scales of the column pass
     unsigned *x3_xmax = nullptr;                  // per-component maxima of W_new qr (bit patterns of non-negative floats)
     double *x3_loss = nullptr;                    // one loss partial per 64 rows
@@ -376,6 +381,8 @@ struct LoopState {
     unsigned sr_launches = 0;        // row pass launches of the current loop (the seeds of the tiles' stochastic rounding)
     bool x3_ready = false;           // Q, x3_qr and x3_xmax are the last fused row pass's (its column pass may run)
     bool prof_now = false;           // this iteration's launches are bracketed (set by piece_rowpass)
+    bool sharded_loop = false;       // the open loop's pieces are exchanged between row shards by the caller (klnmf_loop_begin on a
+                                     // communicator, klnmf_loop_begin_sharded / _agreed; until klnmf_loop_end): no weights may arrive
 };
 
 // ---- the last loop's record as fetch_results wrote it (klnmf_query / klnmf_query_f64): never reset, overwritten whole by the next
@@ -404,6 +411,7 @@ struct klnmf_ctx : ContextState, ProblemState, LoopState, LoopRecord {
     // (k > 256 and CSR input: the bf16x3 kernels / the fp32 sparse kernels)
     bool x3_fused() const { return x3; }
     size_t esize() const { return prec_esize(prec); }
+    bool weighted() const { return Om != nullptr; }
 
     void *dalloc(size_t bytes, bool zero = true) {
         if (bytes == 0) bytes = 16;
@@ -421,6 +429,16 @@ struct klnmf_ctx : ContextState, ProblemState, LoopState, LoopRecord {
         allocs.push_back({p, cls});
         if (zero) HIPCHK(hipMemsetAsync(p, 0, bytes, stream));
         return p;
+    }
+    // one block of the current problem back to the cache before the problem ends (callers have synchronised the stream)
+    void dfree(void *&p) {
+        for (size_t i = 0; i < allocs.size(); ++i) {
+            if (allocs[i].first != p) continue;
+            if (!g_block_cache.give(device, allocs[i].second, p)) (void)hipFree(p);
+            allocs.erase(allocs.begin() + (std::ptrdiff_t)i);
+            break;
+        }
+        p = nullptr;
     }
     // The problem ends: its blocks go back to the cache and its state to the defaults.  Callers have synchronised the stream: no
     // kernel of this context still touches the blocks.
@@ -497,6 +515,7 @@ Refusals read_refusals(klnmf_ctx *c);
 void raise_refusals(klnmf_ctx *c, const Refusals &r);
 void check_v_overflow(klnmf_ctx *c);
 void begin_fp8_loop(klnmf_ctx *c, double sum_x_global = -1.0, double cells_global = -1.0, double nnz_global = -1.0, int ok_all = -1);
+void refuse_weighted(const klnmf_ctx *c, const char *who);
 // api_comm.hip
 bool comm_multi(const klnmf_ctx *c);
 void comm_loop_entry(klnmf_ctx *c);

@@ -28,17 +28,19 @@ def _checked(blocks):
     return checked
 
 
-def _coefficients_on(dictionary, blocks, scales, iter_nmf):
-    """tol=0 transform of the (virtually) stacked blocks on a fixed dictionary."""
+def _coefficients_on(dictionary, blocks, scales, iter_nmf, weights=None):
+    """tol=0 transform of the (virtually) stacked blocks on a fixed dictionary; `weights`: None or one entry per block
+    (`KLdivNMF._fit_blocks`)."""
     model = NMF(n_components=dictionary.shape[0], max_iter=iter_nmf, tol=0)
     model.components_ = dictionary
-    return model._transform_blocks(_checked(blocks), scales)
+    return model._transform_blocks(_checked(blocks), scales, weights=weights)
 
 
-def fit_coefficients(data_obs, dictionary, iter_nmf=100, verbose=False):
+def fit_coefficients(data_obs, dictionary, iter_nmf=100, verbose=False, weights=None):
     """Non-negative coefficients of `data_obs` on `dictionary`
-    (reference learner.py:11-15: tol=0 transform for iter_nmf iterations)."""
-    return _coefficients_on(dictionary, [data_obs], [1.], iter_nmf)
+    (reference learner.py:11-15: tol=0 transform for iter_nmf iterations).  `weights`: None, or an array broadcastable to
+    `data_obs` -- weights on the cost function, 0 = a missing entry (`KLdivNMF.fit_transform`)."""
+    return _coefficients_on(dictionary, [data_obs], [1.], iter_nmf, weights=None if weights is None else [weights])
 
 
 class MultimodalLearner(object):
@@ -81,9 +83,12 @@ class MultimodalLearner(object):
                             zip(data_matrices, self._scales(modalities))])
 
     # ---- dictionary ----
-    def train(self, data_matrices, iterations):
+    def train(self, data_matrices, iterations, weights=None):
         """Fit the dictionary on all modalities: `iterations` multiplicative
-        updates with tol=0 (reference learner.py:31-41)."""
+        updates with tol=0 (reference learner.py:31-41).  `weights`: None, or a list with one entry per modality, each None
+        or an array broadcastable to that modality's block -- weights on the cost function, uploaded block by block beside
+        the data (`KLdivNMF.fit_transform`).  An (n, 1) column of 0 / 1 marks the samples in which a modality is missing.
+        The modality coefficients `coef` keep scaling the data only."""
         n_samples = data_matrices[0].shape[0]
         for m, d in zip(data_matrices, self.dim):
             assert(m.shape == (n_samples, d))
@@ -91,7 +96,7 @@ class MultimodalLearner(object):
             raise NotImplemented        # as the reference (learner.py:37-38)
         self.nmf_train = NMF(n_components=self.k, max_iter=iterations, tol=0)
         self.nmf_train._fit_blocks(_checked(data_matrices), self._scales(self.mod),
-                                   _fit=True)
+                                   _fit=True, weights=weights)
         self.dico = self.nmf_train.components_
 
     def get_dico(self, modality=None):
@@ -105,13 +110,13 @@ class MultimodalLearner(object):
         return safe_hstack([self.get_dico(modality=m) for m in modalities])
 
     # ---- inference ----
-    def reconstruct_internal_multi(self, orig_mods, test_data, iterations):
+    def reconstruct_internal_multi(self, orig_mods, test_data, iterations, weights=None):
         """Internal coefficients from a subset of modalities
-        (reference learner.py:71-78)."""
+        (reference learner.py:71-78).  `weights`: as in `train`, one entry per modality of `orig_mods`."""
         for mod, data in zip(orig_mods, test_data):
             assert(data.shape[1] == self.dim[self.get_index(mod)])
         return _coefficients_on(self.get_stacked_dicos(orig_mods), test_data,
-                                self._scales(orig_mods), iterations)
+                                self._scales(orig_mods), iterations, weights=weights)
 
     def reconstruct_internal(self, orig_mod, test_data, iterations):
         return self.reconstruct_internal_multi([orig_mod], [test_data],

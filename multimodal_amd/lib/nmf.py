@@ -145,6 +145,44 @@ def sparse_precision(precision):
     return 'f32'
 
 
+def weighted_precision(precision):
+    """The arithmetic a weighted fit runs in (array `weights`): the weighted kernels exist in the two exact modes with plain
+    operands (csrc/weighted.hip.h).  'f64' / 'auto' -> f64, 'f32' -> f32; every other mode runs them in fp32 and says so once
+    on stderr (the `sparse_precision` pattern)."""
+    if precision in ('auto', 'f64'):
+        return 'f64'
+    if _native.PRECISIONS[precision] == _native.PREC_F64:
+        return 'f64'
+    if _native.PRECISIONS[precision] == _native.PREC_F32:
+        return 'f32'
+    _note_once(('weights', precision), "KLdivNMF: weights with precision=%r run on the fp32 weighted kernels (precision='f32'); "
+               "the weighted update exists in 'f64' and 'f32' only\n" % (precision,))
+    return 'f32'
+
+
+def check_weights(weights, shape, sparse=False):
+    """`weights` as the loop honours it: None for a scalar (np.ndim 0: the reference's default 1., ignored as the reference
+    ignores it), else a read-only float array broadcast to `shape` with np.broadcast_to.  ValueError -- on the host, before
+    anything is uploaded -- for weights that do not broadcast to `shape`, negative or non-finite weights, and weights
+    together with CSR input (the sparse branch's ratio lives on the stored entries only)."""
+    if weights is None or np.ndim(weights) == 0:
+        return None
+    w = np.asarray(weights)
+    if w.dtype not in (np.float32, np.float64):
+        w = w.astype(np.float64)
+    if sparse:
+        raise ValueError("weights are not supported with CSR input: pass a dense array")
+    try:
+        wb = np.broadcast_to(w, tuple(shape))
+    except ValueError:
+        raise ValueError("weights of shape %s do not broadcast to the data's shape %s" % (w.shape, tuple(shape)))
+    if not np.isfinite(w).all():
+        raise ValueError("Non-finite values in weights passed to NMF.fit")
+    if (w < 0).any():
+        raise ValueError("Negative values in weights passed to NMF.fit")
+    return wb
+
+
 def _devices_of(device):
     """`device` as a tuple of GPU indices: an int is a one-entry list; a sequence of ints is a list (entries may repeat)."""
     if isinstance(device, (int, np.integer)) and not isinstance(device, bool):
@@ -288,9 +326,11 @@ class KLdivNMF(object):
         301-308, 331-334): SDDMM + SpMM kernels of the exact modes, in the arithmetic `sparse_precision` names."""
         return any(sp.issparse(b) for b in blocks)
 
-    def _context(self, exact=False, shape=None, sparse=False):
+    def _context(self, exact=False, shape=None, sparse=False, weighted=False):
         prec = self.precision
-        if sparse:                                # CSR input: f64 ('auto', 'f64') or f32 (everything else), never densified
+        if weighted:                              # array weights: f64 ('auto', 'f64') or f32 (everything else)
+            prec = weighted_precision(prec)
+        elif sparse:                                # CSR input: f64 ('auto', 'f64') or f32 (everything else), never densified
             prec = sparse_precision(prec)
         elif prec == 'auto' and shape is None:    # single steps and loss evaluations: exact
             prec = 'f64'
@@ -318,17 +358,38 @@ class KLdivNMF(object):
     def fit_transform(self, X, y=None, weights=1., _fit=True,
                       return_errors=False, scale_W=False):
         """Learn a NMF model for X and return the transformed data
-        (reference nmf.py:159-230).  `y`, `weights`, `scale_W` are accepted and
-        ignored exactly as in the reference."""
+        (reference nmf.py:159-230).  `y` and `scale_W` are accepted and
+        ignored exactly as in the reference.
+
+        `weights` (nmf.py:171-174: "weights on the cost function used as coefficients on each element of the data ...
+        standard numpy broadcasting is used"; the reference then never reads it): an ARRAY -- anything with np.ndim >= 1,
+        broadcast to X.shape -- is honoured: the loop minimises sum(weights * d(X | W.H)), its loss record and stop rule are
+        the weighted ones, and an entry of weight 0 is missing data (`check_weights`: ValueError for a shape that does not
+        broadcast, negative or non-finite weights, CSR input).  A scalar, the default 1. included, is ignored exactly as
+        before: that path is bit-identical to the unweighted one.  The weighted update (csrc/weighted.hip.h) is
+        W <- W * (R.H^T) / (weights.H^T), H <- rows normalised of H * (W^T.R) / (W^T.weights) with R = weights * ratio, a
+        factor 1 where a denominator is 0; with weights of 1 and dictionary rows summing to 1 this is the reference's
+        loop.  With a dictionary whose rows do not sum to 1 (a transform on a column slice of a dictionary) the weighted W
+        rule divides by the row sums where the reference's does not.  It runs in 'f64' ('f64', 'auto') or 'f32' (every
+        other precision, said once on stderr), on the first device of a device list (said once on stderr)."""
         X = atleast2d_or_csr(X)
         check_non_negative(X, "NMF.fit")
-        return self._fit_blocks([X], [1.], _fit=_fit, return_errors=return_errors)
+        return self._fit_blocks([X], [1.], _fit=_fit, return_errors=return_errors, weights=[weights])
 
-    def _fit_blocks(self, blocks, coefs, _fit=True, return_errors=False):
+    def _fit_blocks(self, blocks, coefs, _fit=True, return_errors=False, weights=None):
         """fit_transform of hstack([c * b for b, c in zip(blocks, coefs)])
         without building the stacked matrix on the host: each modality block is
-        scaled, cast and placed by the upload kernel (learner.py:53-56 fused)."""
-        if self._sparse_route(*blocks):
+        scaled, cast and placed by the upload kernel (learner.py:53-56 fused).
+        `weights`: None, or one entry per block -- None / a scalar (that block's weights are 1) or an array broadcastable
+        to the block (`check_weights`), uploaded block by block beside the data; `coefs` scale the data only."""
+        sparse = self._sparse_route(*blocks)
+        if weights is not None:
+            if len(weights) != len(blocks):
+                raise ValueError("weights: one entry per block expected (%d blocks, %d entries)" % (len(blocks), len(weights)))
+            weights = [check_weights(w, b.shape, sparse) for w, b in zip(weights, blocks)]
+            if all(w is None for w in weights):
+                weights = None
+        if sparse:
             X = _csr_of(blocks, coefs)
             return self._fit_uploaded(X.shape[0], X.shape[1], None,
                                       lambda H_init: np.float32 if (X.dtype == np.float32 and H_init.dtype == np.float32)
@@ -336,12 +397,22 @@ class KLdivNMF(object):
         blocks = [_dense(b) for b in blocks]
         n_samples = blocks[0].shape[0]
         n_features = sum(b.shape[1] for b in blocks)
-        return self._fit_uploaded(n_samples, n_features, lambda ctx: ctx.upload_blocks(blocks, coefs),
+        if weights is None:
+            upload = lambda ctx: ctx.upload_blocks(blocks, coefs)
+        else:
+            def upload(ctx):
+                ctx.upload_blocks(blocks, coefs)
+                col = 0
+                for b, w in zip(blocks, weights):
+                    if w is not None:
+                        ctx.upload_weights(w, row0=0, col0=col)
+                    col += b.shape[1]
+        return self._fit_uploaded(n_samples, n_features, upload,
                                   lambda H_init: _out_dtype(H_init, *blocks), _fit=_fit,
-                                  return_errors=return_errors, host_blocks=(blocks, coefs))
+                                  return_errors=return_errors, host_blocks=(blocks, coefs), weighted=weights is not None)
 
     def _fit_uploaded(self, n_samples, n_features, upload, out_dtype_of, _fit=True, return_errors=False,
-                      sparse_X=None, host_blocks=None):
+                      sparse_X=None, host_blocks=None, weighted=False):
         """The loop of nmf.py:159-230 on a matrix that `upload(ctx)` places in the context: host blocks
         (`_fit_blocks`, which also passes them as `host_blocks` = (blocks, coefs): with two or more devices the loop runs over
         row shards, `_fit_group`) or rows gathered from device-resident data (`device_data.DeviceDataset`: first device)."""
@@ -352,7 +423,11 @@ class KLdivNMF(object):
         max_iter = int(self.max_iter)
         out_dtype = out_dtype_of(H_init)
 
-        if len(self.devices) > 1:
+        if len(self.devices) > 1 and weighted:
+            # (the group's exchange carries the H numerator alone: a weighted fit stays in one context)
+            _note_once(('weights-group',), "KLdivNMF: a weighted fit runs on one device (%d), not over the row shards of devices %s\n"
+                       % (self.device, list(self.devices)))
+        elif len(self.devices) > 1:
             if sparse_X is not None:
                 X = sp.csr_matrix(sparse_X, copy=True)      # (what set_problem_sparse uploads: no explicit zeros, sorted rows)
                 X.eliminate_zeros()
@@ -370,7 +445,7 @@ class KLdivNMF(object):
                                            return_errors)
 
         with self._context(shape=None if sparse_X is not None else (n_samples, n_features, k),
-                           sparse=sparse_X is not None) as ctx:
+                           sparse=sparse_X is not None, weighted=weighted) as ctx:
             if sparse_X is not None:
                 ctx.set_problem_sparse(sparse_X, k, max_iter)
             else:
@@ -504,9 +579,9 @@ class KLdivNMF(object):
         params['_fit'] = False
         return self.fit_transform(X, **params)
 
-    def _transform_blocks(self, blocks, coefs, return_errors=False):
+    def _transform_blocks(self, blocks, coefs, return_errors=False, weights=None):
         self._init_dictionary = self.components_
-        return self._fit_blocks(blocks, coefs, _fit=False, return_errors=return_errors)
+        return self._fit_blocks(blocks, coefs, _fit=False, return_errors=return_errors, weights=weights)
 
     # -------------------------------------------------------- single steps ---
     def _update(self, X, W, _fit=True, scale_W=False, eps=1.e-8):
@@ -544,18 +619,23 @@ class KLdivNMF(object):
         return Wn
 
     def error(self, X, W, H=None, weights=1., eps=1.e-8):
-        """generalized_KL(X, W.H) (reference nmf.py:297-310; `weights` and `eps`
-        are ignored by the reference's dense branch too)."""
+        """generalized_KL(X, W.H) (reference nmf.py:297-310; `eps` is ignored by the reference's dense branch too, and so
+        are `weights` there).  Array `weights` (np.ndim >= 1, broadcast to X.shape: `check_weights`) give the weighted loss
+        sum(weights * (X log((X + eps) / (W.H + eps)) - X + W.H)) in 'f64' or 'f32' (`weighted_precision`); a scalar is
+        ignored as before."""
         X = atleast2d_or_csr(X)
         if H is None:
             H = self.components_
-        with self._context(sparse=self._sparse_route(X)) as ctx:
+        Om = check_weights(weights, X.shape, self._sparse_route(X))
+        with self._context(sparse=self._sparse_route(X), weighted=Om is not None) as ctx:
             if self._sparse_route(X):
                 ctx.set_problem_sparse(X, np.shape(H)[0], 1)      # nmf.py:301-308
             else:
                 Xd = _dense(X)
                 ctx.set_problem(Xd.shape[0], Xd.shape[1], np.shape(H)[0], 1)
                 ctx.upload_blocks([Xd])
+                if Om is not None:
+                    ctx.upload_weights(Om)
             ctx.set_H(H)
             ctx.set_W(W)
             return ctx.error()
@@ -591,7 +671,8 @@ class KLdivNMF(object):
             return ctx.get_Q(dtype=_out_dtype(Xd, W, H))
 
     @classmethod
-    def _step(cls, X, W, H, Q, eps, which):
+    def _step(cls, X, W, H, Q, eps, which, weights=1.):
+        Om = check_weights(weights, np.shape(X), sp.issparse(X))
         if sp.issparse(X) and Q is None:          # the sparse branch end to end (nmf.py:331-351)
             with cls._exact_context() as ctx:
                 Xc = ctx.set_problem_sparse(X, np.shape(H)[0], 1)
@@ -609,13 +690,15 @@ class KLdivNMF(object):
         with cls._exact_context() as ctx:
             ctx.set_problem(Xd.shape[0], Xd.shape[1], np.shape(H)[0], 1)
             ctx.upload_V(Xd)
+            if Om is not None:
+                ctx.upload_weights(Om)
             ctx.set_H(H)
             ctx.set_W(W)
             if Q is None:
                 ctx.set_ratio_eps(eps)
                 ctx.step_Q()
-            else:
-                ctx.set_Q(_dense(Q))
+            else:                                  # (a weighted rule contracts R = weights * Q)
+                ctx.set_Q(_dense(Q) if Om is None else Om * _dense(Q))
             dt = _out_dtype(Xd, W, H)
             if which == 'W':
                 ctx.step_W()
@@ -625,10 +708,12 @@ class KLdivNMF(object):
 
     @classmethod
     def _updated_W(cls, X, W, H, weights=1., Q=None, eps=1.e-8):
-        """W * (Q.H^T) (reference nmf.py:338-343)."""
-        return cls._step(X, W, H, Q, eps, 'W')
+        """W * (Q.H^T) (reference nmf.py:338-343); array `weights`: W * ((weights * Q).H^T) / (weights.H^T), factor 1 where
+        the denominator is 0 (a scalar is ignored as in the reference)."""
+        return cls._step(X, W, H, Q, eps, 'W', weights)
 
     @classmethod
     def _updated_H(cls, X, W, H, weights=1., Q=None, eps=1.e-8):
-        """normalize_rows(H * (W^T.Q)) (reference nmf.py:345-351)."""
-        return cls._step(X, W, H, Q, eps, 'H')
+        """normalize_rows(H * (W^T.Q)) (reference nmf.py:345-351); array `weights`:
+        normalize_rows(H * (W^T.(weights * Q)) / (W^T.weights)), factor 1 where the denominator is 0."""
+        return cls._step(X, W, H, Q, eps, 'H', weights)
