@@ -137,8 +137,27 @@ int klnmf_upload_V_device_rows(klnmf_ctx *ctx, const float *dsrc, const int64_t 
 int klnmf_upload_weights(klnmf_ctx *ctx, const void *src, int dtype,
                          int64_t rows, int64_t cols, int64_t ld,
                          int64_t row0, int64_t col0);
-/* Drop the weights (nmf.py:159-175: back to the reference's unweighted cost): the problem runs the unweighted kernels again. */
+/* Drop the weights (nmf.py:159-175: back to the reference's unweighted cost) -- or the presence mask of
+ * klnmf_upload_presence: the problem runs the unweighted kernels again. */
 int klnmf_clear_weights(klnmf_ctx *ctx);
+/* Weights of the form Om[i, j] = P[i, m(j)] (a modality absent from some samples: learner.py:53-56 stacks the modalities as
+ * contiguous column ranges; the reference has no counterpart): P is n x n_mod, m(j) the modality whose column range
+ * [col_bounds[m], col_bounds[m + 1]) holds column j.  Sets rows row0 .. row0 + rows - 1 of P from src[rows][n_mod] (leading
+ * dimension ld >= n_mod).  col_bounds has n_mod + 1 entries, 0 = b_0 < b_1 < ... < b_M = f, 1 <= n_mod <=
+ * KLNMF_MAX_MODALITIES.  The first call of a problem fixes the bounds and takes P filled with 1; a later call with other bounds
+ * returns KLNMF_ERR_ARG.  From then on the problem is masked (klnmf_query KLNMF_Q_PRESENCE = n_mod; KLNMF_Q_WEIGHTED stays 0:
+ * there is no n x f buffer): every call that minimises the weighted cost on a weighted problem minimises it on this one, to
+ * the same rules, with the denominators Om.H^T = P.S (S the dictionary's row sums per modality) and W^T.Om = D[., m(j)]
+ * (D = W^T.P) formed in n k n_mod operations each (csrc/presence.hip.h); results agree with the same weights uploaded through
+ * klnmf_upload_weights within the exact modes' rounding, not bit for bit.  P >= 0 is the caller's contract.  Refusals, each
+ * leaving the context and the problem as they were: KLNMF_ERR_UNSUPP on a CSR problem, outside KLNMF_PREC_F64 / F32 and while a
+ * loop over row shards is open; KLNMF_ERR_ARG for bad bounds, n_mod out of range, rows out of range, and on a problem that
+ * holds weights (as klnmf_upload_weights on a problem that holds a mask); a masked context is refused (KLNMF_ERR_UNSUPP)
+ * wherever a weighted one is.  klnmf_clear_weights, klnmf_set_problem* and klnmf_release_problem drop the mask. */
+#define KLNMF_MAX_MODALITIES 16
+int klnmf_upload_presence(klnmf_ctx *ctx, const void *src, int dtype,
+                          int64_t rows, int64_t ld, int64_t row0,
+                          const int64_t *col_bounds, int n_mod);
 /* Dictionary [k,f], C order (nmf.py:149-155 `_init_dictionary`, learner.py:13
  * `components_ = dictionary`). */
 int klnmf_set_H(klnmf_ctx *ctx, const void *src, int dtype);
@@ -414,6 +433,8 @@ int klnmf_all_distances_device(int device, int dtype, int metric, int64_t na, in
 #define KLNMF_Q_EX_H_FROM_SLABS   19
 /*   KLNMF_Q_WEIGHTED         1 if the current problem holds weights (klnmf_upload_weights), 0 otherwise or with no problem */
 #define KLNMF_Q_WEIGHTED          20
+/*   KLNMF_Q_PRESENCE         modalities of the current problem's presence mask (klnmf_upload_presence), 0 without one or with no problem */
+#define KLNMF_Q_PRESENCE          21
 int klnmf_query(klnmf_ctx *ctx, int what, int64_t *value);
 /* The launch plan of a problem without a context or a device (replaces nothing of the reference): what klnmf_query would answer
  * right after klnmf_set_problem(n, f, k) -- with nnz >= 0 after klnmf_set_problem_sparse(n, f, k, nnz) -- on a context of `precision`

@@ -52,6 +52,7 @@ SIGNATURES = {
                                   _i64, _i64, _c.c_double]),
     'klnmf_upload_weights': (_c.c_int, [_ctx_p, _c.c_void_p, _c.c_int, _i64, _i64, _i64, _i64, _i64]),
     'klnmf_clear_weights': (_c.c_int, [_ctx_p]),
+    'klnmf_upload_presence': (_c.c_int, [_ctx_p, _c.c_void_p, _c.c_int, _i64, _i64, _i64, _c.POINTER(_i64), _c.c_int]),
     'klnmf_upload_V_device_rows': (_c.c_int, [_ctx_p, _c.c_void_p, _c.c_void_p, _i64, _i64, _i64, _i64, _i64,
                                               _c.c_double]),
     'klnmf_upload_V_device': (_c.c_int, [_ctx_p, _c.c_void_p, _i64, _i64, _i64, _i64,
@@ -257,6 +258,8 @@ Q_FP8_POLL_DUE = 13
 Q_SP_COL_BLOCKS, Q_SP_ROW_BLOCKS = 14, 15
 Q_EX_ROW_CHUNKS, Q_EX_W_CHUNKS, Q_EX_H_SEGMENTS, Q_EX_H_FROM_SLABS = 16, 17, 18, 19
 Q_WEIGHTED = 20
+Q_PRESENCE = 21
+MAX_MODALITIES = 16
 QF_SUM_V, QF_NNZ_V, QF_MON_STAT, QF_MON_THRESHOLD = 0, 1, 2, 3
 QF_KL_OVER_SUM_V = 9
 
@@ -374,9 +377,14 @@ class Context(object):
                                         a.shape[0], a.shape[1], ld, row0, col0,
                                         float(scale)))
 
-    def upload_weights(self, block, row0=0, col0=0):
+    def upload_weights(self, block, row0=0, col0=0, col_bounds=None):
         """Om[row0:, col0:] block = block (klnmf_upload_weights): weights on the cost function, >= 0.  The first call of a
-        problem makes it weighted, with every weight not uploaded equal to 1; dense problems in 'f64' / 'f32' only."""
+        problem makes it weighted, with every weight not uploaded equal to 1; dense problems in 'f64' / 'f32' only.
+        `col_bounds`: the weights in their row x modality form -- `block` is the presence matrix of `upload_presence`."""
+        if col_bounds is not None:
+            if col0 != 0:
+                raise ValueError("a presence matrix spans every column: col0 must be 0")
+            return self.upload_presence(block, col_bounds, row0=row0)
         a = np.asarray(block)
         if a.dtype not in (np.float32, np.float64):
             a = a.astype(np.float64)
@@ -386,6 +394,28 @@ class Context(object):
             a = np.ascontiguousarray(a)
         ld = a.strides[0] // a.itemsize
         _check(self._lib.klnmf_upload_weights(self._h, a.ctypes.data, _np_dtype_code(a), a.shape[0], a.shape[1], ld, row0, col0))
+
+    def upload_presence(self, P, col_bounds, row0=0):
+        """P[row0:row0 + rows, :] = P (klnmf_upload_presence): the weight of modality m -- columns col_bounds[m] .. col_bounds[m + 1] - 1
+        -- in each of the rows, >= 0.  The first call of a problem fixes `col_bounds` (0 = b_0 < ... < b_M = f, M <= MAX_MODALITIES)
+        and makes the problem masked, with every entry not uploaded equal to 1; dense problems in 'f64' / 'f32' only."""
+        a = np.asarray(P)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.ndim != 2:
+            raise ValueError("2-D presence matrix expected")
+        bounds = [int(b) for b in col_bounds]
+        if a.shape[1] != len(bounds) - 1:
+            raise ValueError("presence matrix of %d columns for %d modalities" % (a.shape[1], len(bounds) - 1))
+        if a.strides[1] != a.itemsize or a.strides[0] % a.itemsize or a.strides[0] < a.shape[1] * a.itemsize:
+            a = np.ascontiguousarray(a)
+        ld = a.strides[0] // a.itemsize
+        cb = (_i64 * len(bounds))(*bounds)
+        _check(self._lib.klnmf_upload_presence(self._h, a.ctypes.data, _np_dtype_code(a), a.shape[0], ld, row0, cb, len(bounds) - 1))
+
+    def presence(self):
+        """Modalities of the current problem's presence mask (klnmf_query KLNMF_Q_PRESENCE); 0 without one."""
+        return int(self.query(Q_PRESENCE))
 
     def clear_weights(self):
         _check(self._lib.klnmf_clear_weights(self._h))

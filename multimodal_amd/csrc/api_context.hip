@@ -645,6 +645,8 @@ int klnmf_upload_weights(klnmf_ctx *c, const void *src, int dtype, int64_t rows,
             fail(KLNMF_ERR_UNSUPP, "klnmf_upload_weights: a loop over row shards is open on this context (klnmf_loop_begin on a communicator, "
                                    "klnmf_loop_begin_sharded / _agreed) and its exchange carries no denominator; klnmf_loop_end first");
         check_block(c, rows, cols, ld, row0, col0);
+        if (c->presence())
+            fail(KLNMF_ERR_ARG, "klnmf_upload_weights: the problem holds a presence mask (klnmf_upload_presence); klnmf_clear_weights first");
         const size_t es = c->esize(), n = (size_t)c->n, f = (size_t)c->f, k = (size_t)c->k;
         if (!c->weighted()) {
             HIPCHK(hipStreamSynchronize(c->stream));
@@ -672,9 +674,110 @@ int klnmf_upload_weights(klnmf_ctx *c, const void *src, int dtype, int64_t rows,
     });
 }
 
+// P[row0 + i, m] = src[i, m] for the M = n_mod modalities whose columns are [col_bounds[m], col_bounds[m + 1]) (presence.hip.h).  The
+// first upload of a problem fixes the bounds, builds the per-column modality index and takes P filled with 1, with S, D and D's
+// slabs beside it; klnmf_set_problem* / klnmf_release_problem drop them with the problem (ProblemState).
+int klnmf_upload_presence(klnmf_ctx *c, const void *src, int dtype, int64_t rows, int64_t ld, int64_t row0,
+                          const int64_t *col_bounds, int n_mod) {
+    return guarded([&] {
+        need_problem(c);
+        if (c->sparse) fail(KLNMF_ERR_UNSUPP, "klnmf_upload_presence: CSR problems have no masked kernels (the ratio lives on the stored entries only)");
+        if (c->prec != KLNMF_PREC_F64 && c->prec != KLNMF_PREC_F32)
+            fail(KLNMF_ERR_UNSUPP, "klnmf_upload_presence: the masked kernels exist in KLNMF_PREC_F64 and KLNMF_PREC_F32 only");
+        if (c->sharded_loop)
+            fail(KLNMF_ERR_UNSUPP, "klnmf_upload_presence: a loop over row shards is open on this context (klnmf_loop_begin on a communicator, "
+                                   "klnmf_loop_begin_sharded / _agreed) and its exchange carries no W^T.P; klnmf_loop_end first");
+        if (!src && rows > 0) fail(KLNMF_ERR_ARG, "null source");
+        if (dtype != KLNMF_DT_F64 && dtype != KLNMF_DT_F32) fail(KLNMF_ERR_ARG, "unknown dtype");
+        if (n_mod < 1 || n_mod > KLNMF_MAX_MODALITIES)
+            fail(KLNMF_ERR_ARG, "klnmf_upload_presence: 1 <= n_mod <= KLNMF_MAX_MODALITIES (" + std::to_string(KLNMF_MAX_MODALITIES) + ")");
+        if (!col_bounds) fail(KLNMF_ERR_ARG, "klnmf_upload_presence: null column bounds");
+        if (col_bounds[0] != 0 || col_bounds[n_mod] != c->f)
+            fail(KLNMF_ERR_ARG, "klnmf_upload_presence: the column bounds must run from 0 to f");
+        for (int m = 0; m < n_mod; ++m)
+            if (col_bounds[m] >= col_bounds[m + 1]) fail(KLNMF_ERR_ARG, "klnmf_upload_presence: the column bounds must increase strictly");
+        if (rows < 0 || row0 < 0 || row0 + rows > c->n || ld < n_mod) fail(KLNMF_ERR_ARG, "klnmf_upload_presence: rows out of range");
+        if (c->weighted())
+            fail(KLNMF_ERR_ARG, "klnmf_upload_presence: the problem holds weights (klnmf_upload_weights); klnmf_clear_weights first");
+        if (c->presence() && (n_mod != c->pres_M || !std::equal(col_bounds, col_bounds + n_mod + 1, c->pres_bounds)))
+            fail(KLNMF_ERR_ARG, "klnmf_upload_presence: the column bounds differ from the ones the problem's first upload fixed");
+        const size_t es = c->esize();
+        const int64_t M = n_mod;
+        if (!c->presence()) {
+            HIPCHK(hipStreamSynchronize(c->stream));
+            void *pm = nullptr;
+            try {
+                const int dch = presence_d_chunks(c->n);
+                pm = c->dalloc((size_t)(c->n * M) * es, false);
+                c->pres_S = c->dalloc((size_t)(M * c->k) * es);
+                c->pres_D = c->dalloc((size_t)(c->k * M) * es);
+                c->pres_Dslab = c->dalloc((size_t)dch * (size_t)(c->k * M) * sizeof(double));
+                c->pres_dbounds = c->dalloc((size_t)(M + 1) * sizeof(int64_t));
+                c->pres_mod = c->dalloc((size_t)c->f);
+                std::vector<unsigned char> mod((size_t)c->f);
+                for (int m = 0; m < n_mod; ++m) std::fill(mod.begin() + col_bounds[m], mod.begin() + col_bounds[m + 1], (unsigned char)m);
+                HIPCHK(hipMemcpyAsync(c->pres_mod, mod.data(), mod.size(), hipMemcpyHostToDevice, c->stream));
+                HIPCHK(hipMemcpyAsync(c->pres_dbounds, col_bounds, (size_t)(M + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+                const int64_t count = c->n * M;
+                if (c->prec == KLNMF_PREC_F64)
+                    hipLaunchKernelGGL((k_fill<double>), dim3(grid_for(count, 256, 8192)), dim3(256), 0, c->stream, (double *)pm, count, 1.0);
+                else
+                    hipLaunchKernelGGL((k_fill<float>), dim3(grid_for(count, 256, 8192)), dim3(256), 0, c->stream, (float *)pm, count, 1.0f);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipStreamSynchronize(c->stream));      // (the host images above are read by the copies until here)
+                c->pres_dchunks = dch;
+            } catch (...) {                     // all or nothing: a failed first upload leaves the problem without a mask
+                (void)hipStreamSynchronize(c->stream);
+                c->dfree(c->pres_S); c->dfree(c->pres_D); c->dfree(c->pres_Dslab); c->dfree(c->pres_dbounds); c->dfree(c->pres_mod);
+                c->dfree(pm);
+                throw;
+            }
+            c->Pm = pm;
+            std::copy(col_bounds, col_bounds + n_mod + 1, c->pres_bounds);
+            c->pres_M = n_mod;
+        }
+        if (rows == 0) return;
+        // the rows through a bounded staging buffer (upload_block's scheme), cast and placed by k_place_V on an n x M matrix
+        const size_t ses = dt_size(dtype);
+        int64_t rows_per = (int64_t)((256ull << 20) / (ses * (size_t)ld));
+        rows_per = std::max<int64_t>(1, std::min(rows_per, rows));
+        void *d = nullptr;
+        HIPCHK(hipMalloc(&d, (size_t)rows_per * ld * ses + 16));
+        try {
+            for (int64_t r0 = 0; r0 < rows; r0 += rows_per) {
+                const int64_t rr = std::min(rows_per, rows - r0);
+                HIPCHK(hipMemcpyAsync(d, (const char *)src + (size_t)r0 * ld * ses, ((size_t)(rr - 1) * ld + M) * ses,
+                                      hipMemcpyHostToDevice, c->stream));
+                const int grid = grid_for(rr * M, 256, 8192);
+                const int64_t *no_idx = nullptr;
+#define KL_PLACE_P(T, S) hipLaunchKernelGGL((k_place_V<T, S>), dim3(grid), dim3(256), 0, c->stream, (T *)c->Pm, M, (const S *)d, rr, M, ld, \
+                                            row0 + r0, (int64_t)0, 1.0, no_idx)
+                if (c->prec == KLNMF_PREC_F64) { if (dtype == KLNMF_DT_F64) KL_PLACE_P(double, double); else KL_PLACE_P(double, float); }
+                else { if (dtype == KLNMF_DT_F64) KL_PLACE_P(float, double); else KL_PLACE_P(float, float); }
+#undef KL_PLACE_P
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipStreamSynchronize(c->stream));
+            }
+        } catch (...) {
+            (void)hipFree(d);
+            throw;
+        }
+        (void)hipFree(d);
+    });
+}
+
+// weights and a presence mask alike: the problem runs the unweighted kernels again
 int klnmf_clear_weights(klnmf_ctx *c) {
     return guarded([&] {
         need_problem(c);
+        if (c->presence()) {
+            HIPCHK(hipStreamSynchronize(c->stream));
+            c->dfree(c->Pm); c->dfree(c->pres_S); c->dfree(c->pres_D); c->dfree(c->pres_Dslab); c->dfree(c->pres_dbounds);
+            c->dfree(c->pres_mod);
+            c->pres_M = 0; c->pres_dchunks = 0;
+            std::fill(c->pres_bounds, c->pres_bounds + kMaxMod + 1, (int64_t)0);
+            return;
+        }
         if (!c->weighted()) return;
         HIPCHK(hipStreamSynchronize(c->stream));
         c->dfree(c->Om); c->dfree(c->Dpart); c->dfree(c->denom); c->dfree(c->WDpart);

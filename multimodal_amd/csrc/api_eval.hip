@@ -188,6 +188,7 @@ int klnmf_query(klnmf_ctx *c, int what, int64_t *value) {
             case KLNMF_Q_MON_TRIPS: *value = c->stat_mon_trips; break;
             case KLNMF_Q_MON_GAVE_UP: *value = c->stat_mon_gave_up ? 1 : 0; break;
             case KLNMF_Q_WEIGHTED: *value = (c->have_problem && c->weighted()) ? 1 : 0; break;
+            case KLNMF_Q_PRESENCE: *value = (c->have_problem && c->presence()) ? c->pres_M : 0; break;
             case KLNMF_Q_FP8_POLL_DUE: *value = (c->have_problem && fp8_poll_due(c)) ? 1 : 0; break;
             case KLNMF_Q_COMM_RANKS: {
                 int cnt = 1;

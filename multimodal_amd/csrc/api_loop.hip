@@ -274,11 +274,90 @@ void weighted_H(klnmf_ctx *c, bool from_slabs) {
     HIPCHK(hipGetLastError());
 }
 
+// ------------------------------------------------------- presence pieces ---
+// A masked problem (c->presence(): klnmf_upload_presence; dense, KLNMF_PREC_F64 / F32) takes the kernels of presence.hip.h on the
+// unweighted plan's routes: the ratio pass and the two rules carry the mask, the H numerator is the unweighted one.
+template <typename T>
+void presence_Q(klnmf_ctx *c, int write_q, double eps, const DecideArgs &dec) {
+    EpiQp<T> epi{(const T *)c->V, (const T *)c->Pm, (const unsigned char *)c->pres_mod, (T *)c->Q, c->f, c->pres_M, c->loss_part,
+                 write_q, 0.0, (T)eps};
+    dim3 grid((unsigned)((c->f + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), 1);
+    EventPair ev{};
+    if (c->prof_now) ev = begin_event(c, c->ev_row);
+    hipLaunchKernelGGL((k_gemm<T, EpiQp<T>, 4, true>), grid, dim3(256), 0, c->stream, (int)c->n, (int)c->f, (int)c->k,
+                       (const T *)c->W[c->cur], (int64_t)c->k, (int64_t)1, (const T *)c->H, (int64_t)c->f, (int64_t)1,
+                       (int)c->k + GK, (const DevState *)c->st, epi);
+    HIPCHK(hipGetLastError());
+    if (c->prof_now) HIPCHK(hipEventRecord(ev.b, c->stream));
+    hipLaunchKernelGGL(k_sum_doubles, dim3(1), dim3(1024), 0, c->stream, (const double *)c->loss_part, (int64_t)grid.x * grid.y,
+                       c->loss_xchg, (const DevState *)c->st, dec);
+    HIPCHK(hipGetLastError());
+}
+
+// S from the current H, then W_new = W * (R.H^T) / (P.S) (few rows: feature chunks, the numerator's slabs alone)
+template <typename T>
+void presence_W(klnmf_ctx *c) {
+    hipLaunchKernelGGL((k_presence_S<T>), dim3((unsigned)c->k, (unsigned)c->pres_M), dim3(256), 0, c->stream, (const T *)c->H,
+                       (const int64_t *)c->pres_dbounds, (T *)c->pres_S, c->f, c->k, (const DevState *)c->st);
+    HIPCHK(hipGetLastError());
+    dim3 grid((unsigned)((c->k + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), (unsigned)c->wsplit);
+    if (c->wsplit > 1) {
+        EpiWpart<T> epip{(T *)c->Wpart, c->k, c->n * c->k};
+        hipLaunchKernelGGL((k_gemm<T, EpiWpart<T>, 4, true>), grid, dim3(256), 0, c->stream, (int)c->n, (int)c->k, (int)c->f,
+                           (const T *)c->Q, (int64_t)c->f, (int64_t)1, (const T *)c->H, (int64_t)1, (int64_t)c->f, c->wchunk,
+                           (const DevState *)c->st, epip);
+        HIPCHK(hipGetLastError());
+        const int64_t count = c->n * c->k;
+        hipLaunchKernelGGL((k_wrule_exact_p<T>), dim3(grid_for(count)), dim3(256), 0, c->stream, (const T *)c->Wpart, c->wsplit, count,
+                           (const T *)c->W[c->cur], (T *)c->W[c->cur ^ 1], (const T *)c->Pm, (const T *)c->pres_S, c->k, c->pres_M,
+                           (const DevState *)c->st);
+        HIPCHK(hipGetLastError());
+        return;
+    }
+    EpiWp<T> epi{(const T *)c->W[c->cur], (T *)c->W[c->cur ^ 1], c->k, (const T *)c->Pm, (const T *)c->pres_S, c->pres_M};
+    hipLaunchKernelGGL((k_gemm<T, EpiWp<T>, 4, true>), grid, dim3(256), 0, c->stream, (int)c->n, (int)c->k, (int)c->f,
+                       (const T *)c->Q, (int64_t)c->f, (int64_t)1, (const T *)c->H, (int64_t)1, (int64_t)c->f, (int)c->f + GK,
+                       (const DevState *)c->st, epi);
+    HIPCHK(hipGetLastError());
+}
+
+// D = W[widx]^T.P: the row chunks' slabs in double, then their fixed-order sum (the H numerator beside it is exact_N's own)
+template <typename T>
+void presence_D(klnmf_ctx *c, int widx) {
+    const int64_t chunk = (c->n + c->pres_dchunks - 1) / c->pres_dchunks;
+    hipLaunchKernelGGL((k_presence_D_part<T>), dim3((unsigned)((c->k + 63) / 64), (unsigned)c->pres_dchunks), dim3(256), 0, c->stream,
+                       (const T *)c->W[widx], (const T *)c->Pm, (double *)c->pres_Dslab, c->n, c->k, c->pres_M, chunk, (const DevState *)c->st);
+    HIPCHK(hipGetLastError());
+    const int64_t count = c->k * c->pres_M;
+    hipLaunchKernelGGL((k_presence_D_sum<T>), dim3(grid_for(count)), dim3(256), 0, c->stream, (const double *)c->pres_Dslab,
+                       c->pres_dchunks, count, (T *)c->pres_D, (const DevState *)c->st);
+    HIPCHK(hipGetLastError());
+}
+
+template <typename T>
+void presence_H(klnmf_ctx *c, bool from_slabs) {
+    const unsigned char *mod = (const unsigned char *)c->pres_mod;
+    if (from_slabs) {
+        hipLaunchKernelGGL((k_update_H_slabs_p<T>), dim3((unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H, (const T *)c->Npart,
+                           c->nsplit, c->k * c->f, (const T *)c->pres_D, mod, c->pres_M, c->f, (const DevState *)c->st);
+    } else if (c->hseg_n > 1) {
+        hipLaunchKernelGGL((k_update_H_part_p<T>), dim3((unsigned)c->hseg_n, (unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
+                           (const T *)c->numer, (const T *)c->pres_D, mod, c->pres_M, c->f, c->hseg, c->hpart, (const DevState *)c->st);
+        hipLaunchKernelGGL((k_update_H_norm<T>), dim3((unsigned)c->hseg_n, (unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
+                           c->f, c->hseg, (const double *)c->hpart, (const DevState *)c->st);
+    } else {
+        hipLaunchKernelGGL((k_update_H_p<T>), dim3((unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H, (const T *)c->numer,
+                           (const T *)c->pres_D, mod, c->pres_M, c->f, (const DevState *)c->st);
+    }
+    HIPCHK(hipGetLastError());
+}
+
 // dec.on: the stop rule rides in the one-block loss reduction (single-context loops: no k_decide launch)
 template <typename T>
 void exact_Q(klnmf_ctx *c, int write_q, double eps = kEpsRatio, DecideArgs dec = DecideArgs{0, nullptr, 0.0, nullptr, 0}) {
     if (c->sparse) { sparse_Q<T>(c, write_q, eps, dec); return; }
     if (c->weighted()) { weighted_Q<T>(c, write_q, eps, dec); return; }
+    if (c->presence()) { presence_Q<T>(c, write_q, eps, dec); return; }
     if (write_q) c->x3_ready = false;
     EpiQ<T> epi{(const T *)c->V, (T *)c->Q, c->f, c->loss_part, write_q, 0.0, (T)eps};
     dim3 grid((unsigned)((c->f + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), 1);
@@ -360,6 +439,7 @@ void exact_W(klnmf_ctx *c, const void *qsrc, int multiply) {
         return;
     }
     if (c->weighted() && multiply) { weighted_W<T>(c); return; }      // (the start W0 = V.H0^T is unweighted)
+    if (c->presence() && multiply) { presence_W<T>(c); return; }
     if (c->wsplit > 1) {     // few rows: contraction over f split into chunks (blockIdx.z), W rule from the slabs
         EpiWpart<T> epip{(T *)c->Wpart, c->k, c->n * c->k};
         dim3 gridp((unsigned)((c->k + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), (unsigned)c->wsplit);
@@ -412,6 +492,7 @@ void exact_N(klnmf_ctx *c, int widx, bool sum_slabs = true) {
         return;
     }
     if (c->weighted()) { weighted_N<T>(c, widx, sum_slabs); return; }
+    if (c->presence()) presence_D<T>(c, widx);      // (the numerator below is the unweighted one, on R)
     EpiN<T> epi{(T *)c->Npart, c->f, c->k * c->f};
     dim3 grid((unsigned)((c->f + GT - 1) / GT), (unsigned)((c->k + GT - 1) / GT), (unsigned)c->nsplit);
     EventPair ev{};
@@ -434,6 +515,7 @@ void exact_N(klnmf_ctx *c, int widx, bool sum_slabs = true) {
 template <typename T>
 void exact_H(klnmf_ctx *c, bool from_slabs = false) {
     if (c->weighted()) { weighted_H<T>(c, from_slabs); return; }
+    if (c->presence()) { presence_H<T>(c, from_slabs); return; }
     if (from_slabs) {             // (dense, short rows: the rule sums the row chunks' slabs itself -- the same bits, one launch less)
         hipLaunchKernelGGL((k_update_H_slabs<T>), dim3((unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H, (const T *)c->Npart,
                            c->nsplit, c->k * c->f, c->f, (const DevState *)c->st);
@@ -737,6 +819,10 @@ void piece_rowpass(klnmf_ctx *c, int fit, const double *fused_tol, bool defer_to
 
 // loops whose exchange carries the H numerator alone (communicator, group): a weighted context is refused at their entries
 void refuse_weighted(const klnmf_ctx *c, const char *who) {
+    if (c->presence())
+        fail(KLNMF_ERR_UNSUPP, std::string(who) + ": the context holds a presence mask (klnmf_upload_presence) and the exchange between "
+                                   "row shards carries no W^T.P of the masked H rule; run the masked problem in one context or "
+                                   "klnmf_clear_weights first");
     if (c->weighted())
         fail(KLNMF_ERR_UNSUPP, std::string(who) + ": the context holds weights (klnmf_upload_weights) and the exchange between row "
                                    "shards carries no denominator of the weighted H rule; run the weighted problem in one context "

@@ -33,6 +33,7 @@
 #include "common.hip.h"
 #include "exact.hip.h"
 #include "weighted.hip.h"
+#include "presence.hip.h"
 #include "split3.hip.h"
 #include "f16x3.hip.h"
 #include "sparseb.hip.h"
@@ -295,6 +296,14 @@ struct ProblemState : ProblemPlan {
     // by the first klnmf_upload_weights, dropped by klnmf_clear_weights -- and the denominators' slabs and sums, laid out as
     // Npart / numer / Wpart are.  Om != nullptr IS "the current problem is weighted" (klnmf_query KLNMF_Q_WEIGHTED).
     void *Om = nullptr, *Dpart = nullptr, *denom = nullptr, *WDpart = nullptr;
+    // a masked problem (presence.hip.h; dense, KLNMF_PREC_F64 / F32): the n x M presence matrix P -- allocated filled with 1 by the
+    // first klnmf_upload_presence, dropped by klnmf_clear_weights -- the modalities' column bounds (host and device) and the
+    // per-column modality index, S [M][k] and D [k][M] of the two collapsed denominators and D's row-chunk slabs.  pres_M > 0 IS
+    // "the current problem holds a mask" (klnmf_query KLNMF_Q_PRESENCE); a problem holds Om or P, never both.
+    int pres_M = 0, pres_dchunks = 0;
+    int64_t pres_bounds[kMaxMod + 1] = {};
+    void *Pm = nullptr, *pres_S = nullptr, *pres_D = nullptr;
+    void *pres_dbounds = nullptr, *pres_mod = nullptr, *pres_Dslab = nullptr;      // int64 [M + 1]; bytes [f]; double [chunks][k][M]
     float *x3_hs = nullptr, *x3_qr = nullptr;     // per-component H scales; per-row ratio scales of the column pass
     unsigned *x3_xmax = nullptr;                  // per-component maxima of W_new qr (bit patterns of non-negative floats)
     double *x3_loss = nullptr;                    // one loss partial per 64 rows
@@ -412,6 +421,7 @@ struct klnmf_ctx : ContextState, ProblemState, LoopState, LoopRecord {
     bool x3_fused() const { return x3; }
     size_t esize() const { return prec_esize(prec); }
     bool weighted() const { return Om != nullptr; }
+    bool presence() const { return pres_M > 0; }
 
     void *dalloc(size_t bytes, bool zero = true) {
         if (bytes == 0) bytes = 16;

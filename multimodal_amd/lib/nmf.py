@@ -183,6 +183,23 @@ def check_weights(weights, shape, sparse=False):
     return wb
 
 
+def weights_route(weights, blocks):
+    """How `_fit_blocks` carries per-block `weights` (None, or one entry per block) to the device: None (no array among them:
+    the unweighted loop), 'presence' or 'array'.  'presence' -- a row x modality mask, klnmf_upload_presence, no n x f weight
+    buffer (csrc/presence.hip.h) -- where every entry is None, a scalar or an array of shape exactly (n, 1), at least one is
+    an array, and there are at most `_native.MAX_MODALITIES` blocks: M = the number of blocks, the bounds are the block widths, the
+    column of a block without weights is 1.  Every other case is 'array' (klnmf_upload_weights, csrc/weighted.hip.h)."""
+    if weights is None:
+        return None
+    arrays = [w for w in weights if not (w is None or np.ndim(w) == 0)]
+    if not arrays:
+        return None
+    n = blocks[0].shape[0]
+    if len(blocks) <= _native.MAX_MODALITIES and all(np.shape(w) == (n, 1) for w in arrays):
+        return 'presence'
+    return 'array'
+
+
 def _devices_of(device):
     """`device` as a tuple of GPU indices: an int is a one-entry list; a sequence of ints is a list (entries may repeat)."""
     if isinstance(device, (int, np.integer)) and not isinstance(device, bool):
@@ -319,6 +336,7 @@ class KLdivNMF(object):
         self.devices = _devices_of(device) if device is not None else _default_devices()
         self.device = self.devices[0]
         self.last_fp8_report = None         # set by every loop: what it ran on e4m3 operands (klnmf_query)
+        self.last_weights_route = None      # set by every loop: how it carried array `weights` -- None, 'array' or 'presence' (`weights_route`)
 
     # ------------------------------------------------------------ helpers ---
     def _sparse_route(self, *blocks):
@@ -381,11 +399,15 @@ class KLdivNMF(object):
         without building the stacked matrix on the host: each modality block is
         scaled, cast and placed by the upload kernel (learner.py:53-56 fused).
         `weights`: None, or one entry per block -- None / a scalar (that block's weights are 1) or an array broadcastable
-        to the block (`check_weights`), uploaded block by block beside the data; `coefs` scale the data only."""
+        to the block (`check_weights`), uploaded block by block beside the data; `coefs` scale the data only.  Where every
+        array among them is an (n, 1) presence column (`weights_route`), one n x M presence matrix is uploaded instead and the
+        loop runs the masked kernels (csrc/presence.hip.h); `last_weights_route` names the path the loop took."""
         sparse = self._sparse_route(*blocks)
+        route = None
         if weights is not None:
             if len(weights) != len(blocks):
                 raise ValueError("weights: one entry per block expected (%d blocks, %d entries)" % (len(blocks), len(weights)))
+            route = weights_route(weights, blocks)      # (from the shapes as given: check_weights broadcasts them)
             weights = [check_weights(w, b.shape, sparse) for w, b in zip(weights, blocks)]
             if all(w is None for w in weights):
                 weights = None
@@ -399,6 +421,17 @@ class KLdivNMF(object):
         n_features = sum(b.shape[1] for b in blocks)
         if weights is None:
             upload = lambda ctx: ctx.upload_blocks(blocks, coefs)
+        elif route == 'presence':
+            # one presence column per block (1 for a block without weights), the blocks' widths as the modalities' bounds
+            P = np.ones((n_samples, len(blocks)), dtype=np.float64)
+            for m, w in enumerate(weights):
+                if w is not None:
+                    P[:, m] = w[:, 0]
+            bounds = np.concatenate([[0], np.cumsum([b.shape[1] for b in blocks])])
+
+            def upload(ctx):
+                ctx.upload_blocks(blocks, coefs)
+                ctx.upload_weights(P, col_bounds=bounds)      # (the factored form: klnmf_upload_presence)
         else:
             def upload(ctx):
                 ctx.upload_blocks(blocks, coefs)
@@ -407,15 +440,18 @@ class KLdivNMF(object):
                     if w is not None:
                         ctx.upload_weights(w, row0=0, col0=col)
                     col += b.shape[1]
-        return self._fit_uploaded(n_samples, n_features, upload,
-                                  lambda H_init: _out_dtype(H_init, *blocks), _fit=_fit,
-                                  return_errors=return_errors, host_blocks=(blocks, coefs), weighted=weights is not None)
+        out = self._fit_uploaded(n_samples, n_features, upload,
+                                 lambda H_init: _out_dtype(H_init, *blocks), _fit=_fit,
+                                 return_errors=return_errors, host_blocks=(blocks, coefs), weighted=weights is not None)
+        self.last_weights_route = route if weights is not None else None
+        return out
 
     def _fit_uploaded(self, n_samples, n_features, upload, out_dtype_of, _fit=True, return_errors=False,
                       sparse_X=None, host_blocks=None, weighted=False):
         """The loop of nmf.py:159-230 on a matrix that `upload(ctx)` places in the context: host blocks
         (`_fit_blocks`, which also passes them as `host_blocks` = (blocks, coefs): with two or more devices the loop runs over
         row shards, `_fit_group`) or rows gathered from device-resident data (`device_data.DeviceDataset`: first device)."""
+        self.last_weights_route = None      # (`_fit_blocks` names the route of a weighted loop behind it)
         if not self.n_components:
             self.n_components = n_features
         H_init = self._init_H(n_features)
