@@ -357,6 +357,7 @@ int klnmf_get_Q(klnmf_ctx *ctx, void *dst, int dtype);   /* [n,f], F64/F32 modes
  *                                learner.py:43-51) from a device-resident dictionary: H[:, col0 : col0 + ncols] <- src
  *                                ([k, ncols], rows `ld` apart); `last` != 0 on the block that completes the dictionary
  *   klnmf_get_W_device           the coefficients of the last loop (what transform returns, nmf.py:291) -> [n, k], rows `ld` apart
+ *                                (both on dense and on CSR problems)
  *   klnmf_upload_V_device_rows_dt klnmf_upload_V_device_rows for float32 or float64 device-resident modalities
  *   klnmf_matmul_device          reconstruct_modalit{y,ies} (learner.py:80-84): C[m,n] = A[m,kk] . B[kk,n]
  *   klnmf_all_distances_device   all_distances (metrics.py:80-86) of two device matrices -> [na, nb] on the device */
@@ -496,6 +497,35 @@ int klnmf_upload_csr(klnmf_ctx *ctx, int dtype, const int64_t *indptr, const int
  * (KLNMF_ERR_ARG) before anything is reordered, and leave the problem with no stored entry until the next upload. */
 int klnmf_upload_csr_rows(klnmf_ctx *ctx, int dtype, const int64_t *indptr, const int64_t *indices, const void *data);
 int klnmf_get_Q_values(klnmf_ctx *ctx, void *dst, int dtype);
+/* klnmf_upload_csr_device_rows  X = hstack([scale[m] * X_m[rows] for m in 0 .. n_mod)]) in CSR, gathered ON THE DEVICE from
+ * device-resident CSR modalities: replaces the per-run host slices `x[train, :]` / `x[test, :]` of experiment.py:163-164 and the
+ * sparse stack of learner.py:53-56 (`safe_hstack` keeps the stack sparse if any block is) for data that stays on the GPU across
+ * runs; nothing of nnz length is sliced on the host or crosses the bus.  Called on a problem set by
+ * klnmf_set_problem_sparse(n = rows, f, k, cap, nnz) with nnz the stored entries of the selected rows (the caller knows it from
+ * the sources' row pointers).  Source m (device memory of the context's device): indptr[m] int64 [src_rows + 1], indices[m] INT32
+ * [nnz_m] sorted within every row and in [0, col_bounds[m + 1] - col_bounds[m]) (a modality has fewer than 2^31 columns; half the
+ * resident bytes of int64 -- the problem's own indices stay int64), data[m] [nnz_m] float32 / float64 (dtype[m] = KLNMF_DT_*), no
+ * explicit zeros.  col_bounds has n_mod + 1 entries, 0 = b_0 <= b_1 <= ... <= b_M = f: modality m takes the columns
+ * [b_m, b_(m+1)), 1 <= n_mod <= KLNMF_MAX_MODALITIES.  drow_idx: `rows` int64 row indices in device memory, any order, repeats
+ * allowed.  The product x * scale[m] is formed in the SOURCE's element type with scale[m] rounded to it (scipy's `csr * float(c)`),
+ * then cast to the context's type: the problem is bit for bit the one klnmf_upload_csr_rows uploads from the host's slices.  The
+ * caller keeps products that round to zero out (a scale of 0, or one that underflows the smallest stored value: the reference
+ * drops such entries, nmf.py:66, and a device gather cannot after nnz is fixed).  Then the device tail of klnmf_upload_csr_rows
+ * (structure check, CSC order).  KLNMF_ERR_ARG, the problem as it was: a dense problem, rows != n, n_mod out of range, a null
+ * pointer, bounds that do not run from 0 to f or decrease, an unknown dtype.  KLNMF_ERR_ARG, the problem left with no stored
+ * entry until the next upload (as a refused klnmf_upload_csr_rows leaves it): a row index outside [0, src_rows) -- found on the
+ * device, reported through a flag, never dereferenced -- and a gathered total that differs from the problem's nnz (read back
+ * with the flag, before anything is copied).  Synchronous. */
+int klnmf_upload_csr_device_rows(klnmf_ctx *ctx, int n_mod, const int64_t *const *indptr, const int32_t *const *indices,
+                                 const void *const *data, const int *dtype, const int64_t *col_bounds, const double *scale,
+                                 int64_t src_rows, const int64_t *drow_idx, int64_t rows);
+/* klnmf_csr_rows_to_dense_device  rows drow_idx[0 .. rows) of ONE device-resident CSR matrix (arrays as a source above, d columns)
+ * as a dense float64 device matrix dout [rows, d], rows `ld` apart, zero where nothing is stored: the raw rows `x[test, :]` of a
+ * sparse modality (experiment.py:163-164) that the evaluation compares reconstructions with (experiment.py:266), for
+ * klnmf_all_distances_device; learner.py:53-56 has no part in it (no scale, no stacking).  A row index outside [0, src_rows)
+ * leaves its row zero.  On `device`'s null stream, synchronous (the pattern of klnmf_matmul_device). */
+int klnmf_csr_rows_to_dense_device(int device, int dtype, const int64_t *indptr, const int32_t *indices, const void *data,
+                                   int64_t src_rows, const int64_t *drow_idx, int64_t rows, int64_t d, void *dout, int64_t ld);
 
 /* ---- reconstruction (next-row K7) ---------------------------------------- */
 /* C[m x n] = A[m x kk] . B[kk x n], row-major host arrays of `dtype`, computed on `device` in that

@@ -129,6 +129,11 @@ SIGNATURES = {
                                     _c.c_void_p, _c.c_void_p]),
     'klnmf_upload_csr_rows': (_c.c_int, [_ctx_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     'klnmf_get_Q_values': (_c.c_int, [_ctx_p, _c.c_void_p, _c.c_int]),
+    'klnmf_upload_csr_device_rows': (_c.c_int, [_ctx_p, _c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p),
+                                                _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_int), _c.POINTER(_i64),
+                                                _c.POINTER(_c.c_double), _i64, _c.c_void_p, _i64]),
+    'klnmf_csr_rows_to_dense_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _i64, _c.c_void_p,
+                                                  _i64, _i64, _c.c_void_p, _i64]),
     'klnmf_matmul': (_c.c_int, [_c.c_int, _c.c_int, _i64, _i64, _i64, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     'klnmf_all_distances': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _i64, _i64, _i64, _c.c_void_p, _c.c_void_p,
                                        _c.c_void_p]),
@@ -248,6 +253,14 @@ def all_distances_device(dA, lda, dB, ldb, dout, na, nb, d, metric, f64=True, de
     """out[na, nb] = metric(A[i], B[j]) between DEVICE matrices: klnmf_all_distances_device."""
     _check(load().klnmf_all_distances_device(device, DT_F64 if f64 else DT_F32, int(metric), int(na), int(nb), int(d),
                                              _c.c_void_p(dA), int(lda), _c.c_void_p(dB), int(ldb), _c.c_void_p(dout)))
+
+
+def csr_rows_to_dense_device(d_indptr, d_indices, d_data, f64, src_rows, d_row_idx, rows, d, d_out, ld, device=0):
+    """Rows row_idx[0 .. rows) of one DEVICE-resident CSR matrix (int64 row pointers, int32 column indices, float32 / float64
+    values; pointers) as a dense float64 device matrix [rows, d], rows `ld` apart: klnmf_csr_rows_to_dense_device."""
+    _check(load().klnmf_csr_rows_to_dense_device(device, DT_F64 if f64 else DT_F32, _c.c_void_p(d_indptr), _c.c_void_p(d_indices),
+                                                 _c.c_void_p(d_data), int(src_rows), _c.c_void_p(d_row_idx), int(rows), int(d),
+                                                 _c.c_void_p(d_out), int(ld)))
 
 
 Q_FP8_LOOP, Q_FP8_TILE_ITERS, Q_FP8_COL_ITERS, Q_RATIO_TILE_BYTES, Q_COMM_RANKS = 0, 1, 2, 3, 4
@@ -464,6 +477,28 @@ class Context(object):
         _check(self._lib.klnmf_upload_csr_rows(self._h, DT_F32 if dt == np.float32 else DT_F64, p(indptr), p(indices), p(data)))
         self._csr = (indptr, indices)
         return X
+
+    def set_problem_sparse_shape(self, n, f, k, max_iter_capacity, nnz):
+        """A CSR problem of n x f with nnz stored entries whose arrays an upload fills later (klnmf_set_problem_sparse alone):
+        `upload_csr_device_rows` gathers them from device-resident modalities."""
+        _check(self._lib.klnmf_set_problem_sparse(self._h, int(n), int(f), int(k), int(max_iter_capacity), int(nnz)))
+        self.n, self.f, self.k, self.cap = int(n), int(f), int(k), int(max_iter_capacity)
+        self.nnz = int(nnz)
+
+    def upload_csr_device_rows(self, sources, col_bounds, scales, src_rows, row_idx_ptr, rows):
+        """The CSR of hstack([scale * X[rows] ...]) gathered on the device (klnmf_upload_csr_device_rows).  `sources`: one
+        (indptr pointer, indices pointer, data pointer, values are float64) per modality -- DEVICE arrays: int64 row pointers,
+        int32 column indices, float32 / float64 values; `col_bounds`: the modalities' column bounds, 0 .. f; `row_idx_ptr`: `rows`
+        int64 row indices in device memory.  Only pointers and per-modality scalars cross the boundary."""
+        M = len(sources)
+        if len(col_bounds) != M + 1 or len(scales) != M:
+            raise ValueError("%d sources need %d column bounds and %d scales" % (M, M + 1, M))
+        ptrs = lambda j: (_c.c_void_p * M)(*[int(s[j]) or None for s in sources])
+        dts = (_c.c_int * M)(*[DT_F64 if s[3] else DT_F32 for s in sources])
+        cb = (_i64 * (M + 1))(*[int(b) for b in col_bounds])
+        sc = (_c.c_double * M)(*[float(v) for v in scales])
+        _check(self._lib.klnmf_upload_csr_device_rows(self._h, M, ptrs(0), ptrs(1), ptrs(2), dts, cb, sc, int(src_rows),
+                                                      _c.c_void_p(row_idx_ptr), int(rows)))
 
     def get_Q_values(self, dtype=np.float64):
         out = np.empty(self.nnz, dtype=dtype)

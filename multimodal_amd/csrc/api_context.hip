@@ -1,6 +1,7 @@
 // libklnmf.so, unit 1 of 5: contexts, problems, uploads and downloads (ctx.hip.h lists the units).
 #include "ctx.hip.h"
 #include "csc.hip.h"
+#include "csrgather.hip.h"
 
 DevBlockCache g_block_cache;
 
@@ -463,6 +464,17 @@ static void csr_blocked_setup(klnmf_ctx *c, const char *msg) {
     if (bad) fail(KLNMF_ERR_ARG, msg);
 }
 
+// A refused upload leaves every row and column of the problem empty: no kernel reads the refused indices.
+static void csr_leave_empty(klnmf_ctx *c) {
+    HIPCHK(hipMemsetAsync(c->sp_indptr, 0, sizeof(int64_t) * (c->n + 1), c->stream));
+    HIPCHK(hipMemsetAsync(c->csc_indptr, 0, sizeof(int64_t) * (c->f + 1), c->stream));
+    if (c->sp_blocked) {
+        HIPCHK(hipMemsetAsync(c->sp_blkptr, 0, sizeof(int64_t) * c->n * (c->sp_cb + 1), c->stream));
+        HIPCHK(hipMemsetAsync(c->csc_blkptr, 0, sizeof(int64_t) * c->f * (c->sp_rb + 1), c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+}
+
 // csc_indptr / csc_rows / csc_perm from the CSR structure already on the device (csc.hip.h), after checking it there.  Bad input is
 // refused before any pass runs, and leaves every row and column of the problem empty (no kernel reads the refused indices).
 static void csc_build(klnmf_ctx *c) {
@@ -476,13 +488,7 @@ static void csc_build(klnmf_ctx *c) {
     HIPCHK(hipMemcpyAsync(&bad, flag, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (bad) {
-        HIPCHK(hipMemsetAsync(c->sp_indptr, 0, sizeof(int64_t) * (c->n + 1), c->stream));
-        HIPCHK(hipMemsetAsync(c->csc_indptr, 0, sizeof(int64_t) * (c->f + 1), c->stream));
-        if (c->sp_blocked) {
-            HIPCHK(hipMemsetAsync(c->sp_blkptr, 0, sizeof(int64_t) * c->n * (c->sp_cb + 1), c->stream));
-            HIPCHK(hipMemsetAsync(c->csc_blkptr, 0, sizeof(int64_t) * c->f * (c->sp_rb + 1), c->stream));
-        }
-        HIPCHK(hipStreamSynchronize(c->stream));
+        csr_leave_empty(c);
         fail(KLNMF_ERR_ARG, "klnmf_upload_csr_rows: the row pointers must not decrease, and the column indices of every row must be "
                             "sorted and lie in [0, f)");
     }
@@ -569,6 +575,107 @@ int klnmf_upload_csr_rows(klnmf_ctx *c, int dtype, const int64_t *indptr, const 
         HIPCHK(hipStreamSynchronize(c->stream));
         c->v_uploaded = true;
         c->refusals_dirty = true;
+    });
+}
+
+// The CSR of hstack([scale[m] * X_m[rows] ...]) gathered on the device from device-resident CSR modalities (csrgather.hip.h), then
+// the device tail of klnmf_upload_csr_rows.  Nothing of nnz length crosses the bus: the host reads back two words (the gathered
+// total and the flag) -- before the copy kernel runs, because its stores are in range only if the total is the problem's nnz.
+int klnmf_upload_csr_device_rows(klnmf_ctx *c, int n_mod, const int64_t *const *indptr, const int32_t *const *indices,
+                                 const void *const *data, const int *dtype, const int64_t *col_bounds, const double *scale,
+                                 int64_t src_rows, const int64_t *drow_idx, int64_t rows) {
+    return guarded([&] {
+        need_problem(c);
+        if (!c->sparse) fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows needs klnmf_set_problem_sparse");
+        if (n_mod < 1 || n_mod > KLNMF_MAX_MODALITIES)
+            fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: 1 <= n_mod <= KLNMF_MAX_MODALITIES (" + std::to_string(KLNMF_MAX_MODALITIES) + ")");
+        if (rows != c->n) fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: `rows` must be the problem's n");
+        if (src_rows < 0) fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: src_rows < 0");
+        if (!indptr || !indices || !data || !dtype || !col_bounds || !scale || !drow_idx)
+            fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: null pointer");
+        if (col_bounds[0] != 0 || col_bounds[n_mod] != c->f)
+            fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: the column bounds must run from 0 to f");
+        CsrSources S{};
+        S.src_rows = src_rows;
+        S.n_mod = n_mod;
+        for (int m = 0; m < n_mod; ++m) {
+            if (col_bounds[m] > col_bounds[m + 1]) fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: the column bounds must not decrease");
+            if (col_bounds[m + 1] - col_bounds[m] > (int64_t)std::numeric_limits<int32_t>::max())
+                fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: a modality of 2^31 columns or more (int32 source indices)");
+            if (dtype[m] != KLNMF_DT_F32 && dtype[m] != KLNMF_DT_F64)
+                fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: dtype must be KLNMF_DT_F32 or KLNMF_DT_F64");
+            if (!indptr[m] || (c->nnz > 0 && (!indices[m] || !data[m]))) fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: null pointer");
+            S.indptr[m] = indptr[m];
+            S.indices[m] = indices[m];
+            S.data[m] = data[m];
+            S.col0[m] = col_bounds[m];
+            S.scale[m] = scale[m];
+            if (dtype[m] == KLNMF_DT_F64) S.f64_mask |= 1u << m;
+        }
+        c->v_uploaded = false;
+        // row lengths -> exclusive scan in place (csc.hip.h's scan: fixed order, exact integers) -> sp_indptr
+        const int64_t m1 = c->n + 1, nparts = (m1 + kCscScanTile - 1) / kCscScanTile;
+        void *tmp = c->dalloc(sizeof(int64_t) * (size_t)(nparts + 1));      // the scan's tile sums, then the flag (zero-filled)
+        int64_t *parts = (int64_t *)tmp, *flag = parts + nparts;
+        hipLaunchKernelGGL(k_csrg_len, dim3(grid_for(m1, kCsrgThreads, 8192)), dim3(kCsrgThreads), 0, c->stream, S, drow_idx, rows,
+                           c->sp_indptr, flag);
+        hipLaunchKernelGGL(k_csc_scan_tiles, dim3((unsigned)nparts), dim3(kCscThreads), 0, c->stream, c->sp_indptr, m1, parts);
+        hipLaunchKernelGGL(k_csc_scan_part, dim3(1), dim3(kCscThreads), 0, c->stream, parts, nparts);
+        hipLaunchKernelGGL(k_csc_scan_add, dim3(grid_for(m1, 256, 8192)), dim3(256), 0, c->stream, c->sp_indptr, m1, (const int64_t *)parts);
+        HIPCHK(hipGetLastError());
+        int64_t bad = 0, total = -1;
+        HIPCHK(hipMemcpyAsync(&bad, flag, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(&total, c->sp_indptr + c->n, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->dfree(tmp);
+        if (bad || total != c->nnz) {
+            csr_leave_empty(c);
+            if (bad) fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: a row index outside [0, src_rows), or source row pointers that decrease");
+            fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: the rows hold " + std::to_string(total) + " stored entries, the problem was set for " +
+                                std::to_string(c->nnz));
+        }
+        if (c->nnz > 0) {
+            const int grid = grid_for(rows * kCsrgTrip, kCsrgThreads, 1 << 16);
+            if (c->prec == KLNMF_PREC_F64)
+                hipLaunchKernelGGL((k_csrg_copy<double>), dim3(grid), dim3(kCsrgThreads), 0, c->stream, S, drow_idx, rows,
+                                   (const int64_t *)c->sp_indptr, c->sp_indices, (double *)c->sp_data);
+            else
+                hipLaunchKernelGGL((k_csrg_copy<float>), dim3(grid), dim3(kCsrgThreads), 0, c->stream, S, drow_idx, rows,
+                                   (const int64_t *)c->sp_indptr, c->sp_indices, (float *)c->sp_data);
+            HIPCHK(hipGetLastError());
+        }
+        csc_build(c);
+        csr_blocked_setup(c, "klnmf_upload_csr_device_rows: the column indices of every source row must be sorted");
+        HIPCHK(hipStreamSynchronize(c->stream));      // (drow_idx and the sources are the caller's: free to go from here)
+        c->v_uploaded = true;
+        c->refusals_dirty = true;
+    });
+}
+
+// Rows drow_idx[0 .. rows) of one device-resident CSR matrix as a dense float64 device matrix (the pattern of klnmf_matmul_device:
+// the device's null stream, synchronous)
+int klnmf_csr_rows_to_dense_device(int device, int dtype, const int64_t *indptr, const int32_t *indices, const void *data,
+                                   int64_t src_rows, const int64_t *drow_idx, int64_t rows, int64_t d, void *dout, int64_t ld) {
+    return guarded([&] {
+        if (rows < 0 || d < 0 || src_rows < 0 || rows > (1LL << 40) || d > (int64_t)std::numeric_limits<int32_t>::max())
+            fail(KLNMF_ERR_ARG, "klnmf_csr_rows_to_dense_device: bad shape");
+        if (dtype != KLNMF_DT_F32 && dtype != KLNMF_DT_F64)
+            fail(KLNMF_ERR_ARG, "klnmf_csr_rows_to_dense_device: dtype must be KLNMF_DT_F32 or KLNMF_DT_F64");
+        if (rows == 0 || d == 0) return;
+        if (!indptr || !drow_idx || !dout || ld < d) fail(KLNMF_ERR_ARG, "klnmf_csr_rows_to_dense_device: null pointer or short stride");
+        HIPCHK(hipSetDevice(device));
+        HIPCHK(hipMemset2DAsync(dout, (size_t)ld * sizeof(double), 0, (size_t)d * sizeof(double), (size_t)rows, 0));
+        if (indices && data) {      // (a matrix without stored entries may come without them: the zeros are the answer)
+            const int grid = grid_for(rows * kCsrgTrip, kCsrgThreads, 1 << 16);
+            if (dtype == KLNMF_DT_F64)
+                hipLaunchKernelGGL((k_csrg_dense<double>), dim3(grid), dim3(kCsrgThreads), 0, 0, indptr, indices, (const double *)data, src_rows,
+                                   drow_idx, rows, d, (double *)dout, ld);
+            else
+                hipLaunchKernelGGL((k_csrg_dense<float>), dim3(grid), dim3(kCsrgThreads), 0, 0, indptr, indices, (const float *)data, src_rows,
+                                   drow_idx, rows, d, (double *)dout, ld);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipStreamSynchronize(0));
     });
 }
 
@@ -828,7 +935,6 @@ int klnmf_set_H_device(klnmf_ctx *c, const void *dsrc, int dtype, int64_t ld, in
         if (!dsrc) fail(KLNMF_ERR_ARG, "null source");
         if (dtype != KLNMF_DT_F32 && dtype != KLNMF_DT_F64) fail(KLNMF_ERR_ARG, "dtype must be KLNMF_DT_F32 or KLNMF_DT_F64");
         if (col0 < 0 || ncols < 0 || col0 + ncols > c->f || ld < ncols) fail(KLNMF_ERR_ARG, "klnmf_set_H_device: column block out of range");
-        if (c->sparse) fail(KLNMF_ERR_UNSUPP, "klnmf_set_H_device: dense problems");
         const bool f64 = dtype == KLNMF_DT_F64;
         // the first block of a dictionary (col0 = 0) starts from zeros, as klnmf_set_H does: a pooled or re-used context
         // must not keep padding rows / columns of the previous dictionary in its images

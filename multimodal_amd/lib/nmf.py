@@ -447,10 +447,13 @@ class KLdivNMF(object):
         return out
 
     def _fit_uploaded(self, n_samples, n_features, upload, out_dtype_of, _fit=True, return_errors=False,
-                      sparse_X=None, host_blocks=None, weighted=False):
+                      sparse_X=None, host_blocks=None, weighted=False, sparse_nnz=None):
         """The loop of nmf.py:159-230 on a matrix that `upload(ctx)` places in the context: host blocks
         (`_fit_blocks`, which also passes them as `host_blocks` = (blocks, coefs): with two or more devices the loop runs over
-        row shards, `_fit_group`) or rows gathered from device-resident data (`device_data.DeviceDataset`: first device)."""
+        row shards, `_fit_group`) or rows gathered from device-resident data (`device_data.DeviceDataset`: first device).
+        `sparse_nnz`: the matrix is a CSR problem of (n_samples, n_features, sparse_nnz) whose arrays `upload(ctx)` fills (rows
+        gathered from device-resident CSR modalities): the reference's sparse branch in the arithmetic `sparse_precision` names,
+        as with `sparse_X`, on the first device."""
         self.last_weights_route = None      # (`_fit_blocks` names the route of a weighted loop behind it)
         if not self.n_components:
             self.n_components = n_features
@@ -480,10 +483,13 @@ class KLdivNMF(object):
                     return self._fit_group(plan, host_blocks[0], host_blocks[1], n_samples, n_features, H_init, out_dtype, _fit,
                                            return_errors)
 
-        with self._context(shape=None if sparse_X is not None else (n_samples, n_features, k),
-                           sparse=sparse_X is not None, weighted=weighted) as ctx:
+        sparse = sparse_X is not None or sparse_nnz is not None
+        with self._context(shape=None if sparse else (n_samples, n_features, k), sparse=sparse, weighted=weighted) as ctx:
             if sparse_X is not None:
                 ctx.set_problem_sparse(sparse_X, k, max_iter)
+            elif sparse_nnz is not None:
+                ctx.set_problem_sparse_shape(n_samples, n_features, k, max_iter, sparse_nnz)
+                upload(ctx)
             else:
                 ctx.set_problem(n_samples, n_features, k, max_iter)
                 upload(ctx)
