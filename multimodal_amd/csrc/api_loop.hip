@@ -195,133 +195,21 @@ void sparse_Q(klnmf_ctx *c, int write_q, double eps, const DecideArgs &dec) {
         hipLaunchKernelGGL((k_gemm<T, EPI, 4, true>), grid, dim3(256), 0, stream, __VA_ARGS__);                     \
     } while (0)
 
-// ------------------------------------------------------- weighted pieces ---
-// A weighted problem (c->weighted(): klnmf_upload_weights; dense, KLNMF_PREC_F64 / F32) takes the kernels of weighted.hip.h on
-// the unweighted plan's routes; the branch is here, on the host, and no unweighted kernel knows of it.
-template <typename T>
-void weighted_Q(klnmf_ctx *c, int write_q, double eps, const DecideArgs &dec) {
-    EpiQw<T> epi{(const T *)c->V, (const T *)c->Om, (T *)c->Q, c->f, c->loss_part, write_q, 0.0, (T)eps};
-    dim3 grid((unsigned)((c->f + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), 1);
-    EventPair ev{};
-    if (c->prof_now) ev = begin_event(c, c->ev_row);
-    hipLaunchKernelGGL((k_gemm<T, EpiQw<T>, 4, true>), grid, dim3(256), 0, c->stream, (int)c->n, (int)c->f, (int)c->k,
-                       (const T *)c->W[c->cur], (int64_t)c->k, (int64_t)1, (const T *)c->H, (int64_t)c->f, (int64_t)1,
-                       (int)c->k + GK, (const DevState *)c->st, epi);
-    HIPCHK(hipGetLastError());
-    if (c->prof_now) HIPCHK(hipEventRecord(ev.b, c->stream));
-    hipLaunchKernelGGL(k_sum_doubles, dim3(1), dim3(1024), 0, c->stream, (const double *)c->loss_part, (int64_t)grid.x * grid.y,
-                       c->loss_xchg, (const DevState *)c->st, dec);
-    HIPCHK(hipGetLastError());
-}
+// ------------------------------------------- weighted and masked problems ---
+// A weighted (c->weighted(): klnmf_upload_weights) or masked (c->presence(): klnmf_upload_presence) problem -- dense, KLNMF_PREC_F64 /
+// F32 -- takes the unweighted plan's routes and the same kernel family (exact.hip.h) under its own policies; the branch is here, on
+// the host, and no unweighted instantiation knows of it.  The split-operand modes (KL_GEMM_TT's k_gemm_x3 arm) exist for the
+// unweighted policy only: the uploads refuse every other precision.
 
-// W_new = W * (R.H^T) / (Om.H^T): form A of k_gemm_dual, the tile of H^T shared (few rows: feature chunks, two slab sets)
+// S of the masked W rule's denominator P.S, from the current H
 template <typename T>
-void weighted_W(klnmf_ctx *c) {
-    dim3 grid((unsigned)((c->k + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), (unsigned)c->wsplit);
-    if (c->wsplit > 1) {
-        EpiW2part<T> epip{(T *)c->Wpart, (T *)c->WDpart, c->k, c->n * c->k};
-        hipLaunchKernelGGL((k_gemm_dual<T, EpiW2part<T>, true>), grid, dim3(256), 0, c->stream, (int)c->n, (int)c->k, (int)c->f,
-                           (const T *)c->Q, (int64_t)c->f, (int64_t)1, (const T *)c->H, (int64_t)1, (int64_t)c->f,
-                           (const T *)c->Om, c->wchunk, (const DevState *)c->st, epip);
-        HIPCHK(hipGetLastError());
-        const int64_t count = c->n * c->k;
-        hipLaunchKernelGGL((k_wrule_exact_w<T>), dim3(grid_for(count)), dim3(256), 0, c->stream, (const T *)c->Wpart,
-                           (const T *)c->WDpart, c->wsplit, count, (const T *)c->W[c->cur], (T *)c->W[c->cur ^ 1],
-                           (const DevState *)c->st);
-        HIPCHK(hipGetLastError());
-        return;
-    }
-    EpiW2<T> epi{(const T *)c->W[c->cur], (T *)c->W[c->cur ^ 1], c->k};
-    hipLaunchKernelGGL((k_gemm_dual<T, EpiW2<T>, true>), grid, dim3(256), 0, c->stream, (int)c->n, (int)c->k, (int)c->f,
-                       (const T *)c->Q, (int64_t)c->f, (int64_t)1, (const T *)c->H, (int64_t)1, (int64_t)c->f,
-                       (const T *)c->Om, (int)c->f + GK, (const DevState *)c->st, epi);
-    HIPCHK(hipGetLastError());
-}
-
-// (W[widx]^T.R, W[widx]^T.Om) per row chunk: form B of k_gemm_dual, the tile of W^T shared
-template <typename T>
-void weighted_N(klnmf_ctx *c, int widx, bool sum_slabs) {
-    EpiN2<T> epi{(T *)c->Npart, (T *)c->Dpart, c->f, c->k * c->f};
-    dim3 grid((unsigned)((c->f + GT - 1) / GT), (unsigned)((c->k + GT - 1) / GT), (unsigned)c->nsplit);
-    EventPair ev{};
-    if (c->prof_now) ev = begin_event(c, c->ev_col);
-    hipLaunchKernelGGL((k_gemm_dual<T, EpiN2<T>, false>), grid, dim3(256), 0, c->stream, (int)c->k, (int)c->f, (int)c->n,
-                       (const T *)c->W[widx], (int64_t)1, (int64_t)c->k, (const T *)c->Q, (int64_t)c->f, (int64_t)1,
-                       (const T *)c->Om, c->kchunk, (const DevState *)c->st, epi);
-    HIPCHK(hipGetLastError());
-    if (c->prof_now) HIPCHK(hipEventRecord(ev.b, c->stream));
-    if (!sum_slabs) return;
-    const int64_t count = c->k * c->f;
-    hipLaunchKernelGGL((k_sum_partials_w<T>), dim3(grid_for(count)), dim3(256), 0, c->stream, (const T *)c->Npart,
-                       (const T *)c->Dpart, (T *)c->numer, (T *)c->denom, count, c->nsplit, (const DevState *)c->st);
-    HIPCHK(hipGetLastError());
-}
-
-template <typename T>
-void weighted_H(klnmf_ctx *c, bool from_slabs) {
-    if (from_slabs) {
-        hipLaunchKernelGGL((k_update_H_slabs_w<T>), dim3((unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H, (const T *)c->Npart,
-                           (const T *)c->Dpart, c->nsplit, c->k * c->f, c->f, (const DevState *)c->st);
-    } else if (c->hseg_n > 1) {
-        hipLaunchKernelGGL((k_update_H_part_w<T>), dim3((unsigned)c->hseg_n, (unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
-                           (const T *)c->numer, (const T *)c->denom, c->f, c->hseg, c->hpart, (const DevState *)c->st);
-        hipLaunchKernelGGL((k_update_H_norm<T>), dim3((unsigned)c->hseg_n, (unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
-                           c->f, c->hseg, (const double *)c->hpart, (const DevState *)c->st);
-    } else {
-        hipLaunchKernelGGL((k_update_H_w<T>), dim3((unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H, (const T *)c->numer,
-                           (const T *)c->denom, c->f, (const DevState *)c->st);
-    }
-    HIPCHK(hipGetLastError());
-}
-
-// ------------------------------------------------------- presence pieces ---
-// A masked problem (c->presence(): klnmf_upload_presence; dense, KLNMF_PREC_F64 / F32) takes the kernels of presence.hip.h on the
-// unweighted plan's routes: the ratio pass and the two rules carry the mask, the H numerator is the unweighted one.
-template <typename T>
-void presence_Q(klnmf_ctx *c, int write_q, double eps, const DecideArgs &dec) {
-    EpiQp<T> epi{(const T *)c->V, (const T *)c->Pm, (const unsigned char *)c->pres_mod, (T *)c->Q, c->f, c->pres_M, c->loss_part,
-                 write_q, 0.0, (T)eps};
-    dim3 grid((unsigned)((c->f + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), 1);
-    EventPair ev{};
-    if (c->prof_now) ev = begin_event(c, c->ev_row);
-    hipLaunchKernelGGL((k_gemm<T, EpiQp<T>, 4, true>), grid, dim3(256), 0, c->stream, (int)c->n, (int)c->f, (int)c->k,
-                       (const T *)c->W[c->cur], (int64_t)c->k, (int64_t)1, (const T *)c->H, (int64_t)c->f, (int64_t)1,
-                       (int)c->k + GK, (const DevState *)c->st, epi);
-    HIPCHK(hipGetLastError());
-    if (c->prof_now) HIPCHK(hipEventRecord(ev.b, c->stream));
-    hipLaunchKernelGGL(k_sum_doubles, dim3(1), dim3(1024), 0, c->stream, (const double *)c->loss_part, (int64_t)grid.x * grid.y,
-                       c->loss_xchg, (const DevState *)c->st, dec);
-    HIPCHK(hipGetLastError());
-}
-
-// S from the current H, then W_new = W * (R.H^T) / (P.S) (few rows: feature chunks, the numerator's slabs alone)
-template <typename T>
-void presence_W(klnmf_ctx *c) {
+void presence_S(klnmf_ctx *c) {
     hipLaunchKernelGGL((k_presence_S<T>), dim3((unsigned)c->k, (unsigned)c->pres_M), dim3(256), 0, c->stream, (const T *)c->H,
                        (const int64_t *)c->pres_dbounds, (T *)c->pres_S, c->f, c->k, (const DevState *)c->st);
     HIPCHK(hipGetLastError());
-    dim3 grid((unsigned)((c->k + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), (unsigned)c->wsplit);
-    if (c->wsplit > 1) {
-        EpiWpart<T> epip{(T *)c->Wpart, c->k, c->n * c->k};
-        hipLaunchKernelGGL((k_gemm<T, EpiWpart<T>, 4, true>), grid, dim3(256), 0, c->stream, (int)c->n, (int)c->k, (int)c->f,
-                           (const T *)c->Q, (int64_t)c->f, (int64_t)1, (const T *)c->H, (int64_t)1, (int64_t)c->f, c->wchunk,
-                           (const DevState *)c->st, epip);
-        HIPCHK(hipGetLastError());
-        const int64_t count = c->n * c->k;
-        hipLaunchKernelGGL((k_wrule_exact_p<T>), dim3(grid_for(count)), dim3(256), 0, c->stream, (const T *)c->Wpart, c->wsplit, count,
-                           (const T *)c->W[c->cur], (T *)c->W[c->cur ^ 1], (const T *)c->Pm, (const T *)c->pres_S, c->k, c->pres_M,
-                           (const DevState *)c->st);
-        HIPCHK(hipGetLastError());
-        return;
-    }
-    EpiWp<T> epi{(const T *)c->W[c->cur], (T *)c->W[c->cur ^ 1], c->k, (const T *)c->Pm, (const T *)c->pres_S, c->pres_M};
-    hipLaunchKernelGGL((k_gemm<T, EpiWp<T>, 4, true>), grid, dim3(256), 0, c->stream, (int)c->n, (int)c->k, (int)c->f,
-                       (const T *)c->Q, (int64_t)c->f, (int64_t)1, (const T *)c->H, (int64_t)1, (int64_t)c->f, (int)c->f + GK,
-                       (const DevState *)c->st, epi);
-    HIPCHK(hipGetLastError());
 }
 
-// D = W[widx]^T.P: the row chunks' slabs in double, then their fixed-order sum (the H numerator beside it is exact_N's own)
+// D = W[widx]^T.P: the row chunks' slabs in double, then their fixed-order sum (the H numerator beside it is the unweighted one)
 template <typename T>
 void presence_D(klnmf_ctx *c, int widx) {
     const int64_t chunk = (c->n + c->pres_dchunks - 1) / c->pres_dchunks;
@@ -334,39 +222,30 @@ void presence_D(klnmf_ctx *c, int widx) {
     HIPCHK(hipGetLastError());
 }
 
-template <typename T>
-void presence_H(klnmf_ctx *c, bool from_slabs) {
-    const unsigned char *mod = (const unsigned char *)c->pres_mod;
-    if (from_slabs) {
-        hipLaunchKernelGGL((k_update_H_slabs_p<T>), dim3((unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H, (const T *)c->Npart,
-                           c->nsplit, c->k * c->f, (const T *)c->pres_D, mod, c->pres_M, c->f, (const DevState *)c->st);
-    } else if (c->hseg_n > 1) {
-        hipLaunchKernelGGL((k_update_H_part_p<T>), dim3((unsigned)c->hseg_n, (unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
-                           (const T *)c->numer, (const T *)c->pres_D, mod, c->pres_M, c->f, c->hseg, c->hpart, (const DevState *)c->st);
-        hipLaunchKernelGGL((k_update_H_norm<T>), dim3((unsigned)c->hseg_n, (unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
-                           c->f, c->hseg, (const double *)c->hpart, (const DevState *)c->st);
-    } else {
-        hipLaunchKernelGGL((k_update_H_p<T>), dim3((unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H, (const T *)c->numer,
-                           (const T *)c->pres_D, mod, c->pres_M, c->f, (const DevState *)c->st);
-    }
-    HIPCHK(hipGetLastError());
-}
-
 // dec.on: the stop rule rides in the one-block loss reduction (single-context loops: no k_decide launch)
 template <typename T>
 void exact_Q(klnmf_ctx *c, int write_q, double eps = kEpsRatio, DecideArgs dec = DecideArgs{0, nullptr, 0.0, nullptr, 0}) {
     if (c->sparse) { sparse_Q<T>(c, write_q, eps, dec); return; }
-    if (c->weighted()) { weighted_Q<T>(c, write_q, eps, dec); return; }
-    if (c->presence()) { presence_Q<T>(c, write_q, eps, dec); return; }
     if (write_q) c->x3_ready = false;
-    EpiQ<T> epi{(const T *)c->V, (T *)c->Q, c->f, c->loss_part, write_q, 0.0, (T)eps};
+    const T *V = (const T *)c->V;
+    T *Q = (T *)c->Q;      // (a weight: R = w * Q in its place)
     dim3 grid((unsigned)((c->f + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), 1);
     EventPair ev{};
     if (c->prof_now) ev = begin_event(c, c->ev_row);
-    KL_GEMM_TT(T, EpiQ<T>, grid, c->stream, (int)c->n, (int)c->f,
-               (int)c->k, (const T *)c->W[c->cur], (int64_t)c->k, (int64_t)1,
-               (const T *)c->H, (int64_t)c->f, (int64_t)1, (int)c->k + GK,
-               (const DevState *)c->st, epi);
+#define KL_Q_ARGS (int)c->n, (int)c->f, (int)c->k, (const T *)c->W[c->cur], (int64_t)c->k, (int64_t)1, (const T *)c->H, (int64_t)c->f, \
+                  (int64_t)1, (int)c->k + GK, (const DevState *)c->st
+    if (c->weighted()) {
+        typedef EpiQ<T, ElemWeight<T>> Epi;
+        hipLaunchKernelGGL((k_gemm<T, Epi, 4, true>), grid, dim3(256), 0, c->stream, KL_Q_ARGS,
+                           Epi{V, {(const T *)c->Om}, Q, c->f, c->loss_part, write_q, 0.0, (T)eps});
+    } else if (c->presence()) {
+        typedef EpiQ<T, PresenceWeight<T>> Epi;
+        hipLaunchKernelGGL((k_gemm<T, Epi, 4, true>), grid, dim3(256), 0, c->stream, KL_Q_ARGS,
+                           Epi{V, {(const T *)c->Pm, (const unsigned char *)c->pres_mod, c->pres_M}, Q, c->f, c->loss_part, write_q, 0.0, (T)eps});
+    } else {
+        KL_GEMM_TT(T, EpiQ<T>, grid, c->stream, KL_Q_ARGS, EpiQ<T>{V, {}, Q, c->f, c->loss_part, write_q, 0.0, (T)eps});
+    }
+#undef KL_Q_ARGS
     HIPCHK(hipGetLastError());
     if (c->prof_now) HIPCHK(hipEventRecord(ev.b, c->stream));
     hipLaunchKernelGGL(k_sum_doubles, dim3(1), dim3(1024), 0, c->stream,
@@ -438,28 +317,43 @@ void exact_W(klnmf_ctx *c, const void *qsrc, int multiply) {
         HIPCHK(hipGetLastError());
         return;
     }
-    if (c->weighted() && multiply) { weighted_W<T>(c); return; }      // (the start W0 = V.H0^T is unweighted)
-    if (c->presence() && multiply) { presence_W<T>(c); return; }
-    if (c->wsplit > 1) {     // few rows: contraction over f split into chunks (blockIdx.z), W rule from the slabs
-        EpiWpart<T> epip{(T *)c->Wpart, c->k, c->n * c->k};
-        dim3 gridp((unsigned)((c->k + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), (unsigned)c->wsplit);
-        KL_GEMM_TT(T, EpiWpart<T>, gridp, c->stream, (int)c->n, (int)c->k,
-                   (int)c->f, (const T *)qsrc, (int64_t)c->f, (int64_t)1, (const T *)c->H,
-                   (int64_t)1, (int64_t)c->f, c->wchunk, (const DevState *)c->st, epip);
+    // dense: the whole contraction with the rule in its epilogue, or (few rows) the contraction over f split into chunks
+    // (blockIdx.z), slabs, and the rule from the slabs -- under the policy `fac`
+    const bool split = c->wsplit > 1;
+    dim3 grid((unsigned)((c->k + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), (unsigned)(split ? c->wsplit : 1));
+    const int chunk = split ? c->wchunk : (int)c->f + GK;
+    // x3: std::true_type for the unweighted policy alone -- KL_GEMM_TT's split-operand arm (k_gemm_x3) exists for no other
+    auto contract = [&](auto epi, auto x3) {
+        typedef decltype(epi) Epi;
+#define KL_W_ARGS (int)c->n, (int)c->k, (int)c->f, (const T *)qsrc, (int64_t)c->f, (int64_t)1, (const T *)c->H, (int64_t)1, (int64_t)c->f
+        if constexpr (Epi::sets == 2)      // numerator and denominator: form A of k_gemm_dual (R.H^T, Om.H^T), the tile of H^T shared
+            hipLaunchKernelGGL((k_gemm_dual<T, Epi, true>), grid, dim3(256), 0, c->stream, KL_W_ARGS, (const T *)c->Om, chunk,
+                               (const DevState *)c->st, epi);
+        else if constexpr (decltype(x3)::value)
+            KL_GEMM_TT(T, Epi, grid, c->stream, KL_W_ARGS, chunk, (const DevState *)c->st, epi);
+        else
+            hipLaunchKernelGGL((k_gemm<T, Epi, 4, true>), grid, dim3(256), 0, c->stream, KL_W_ARGS, chunk, (const DevState *)c->st, epi);
+#undef KL_W_ARGS
         HIPCHK(hipGetLastError());
+    };
+    auto rule = [&](auto fac, auto x3) {
+        typedef decltype(fac) Fac;
+        EpiW<T, Fac> epi{(const T *)c->W[c->cur], (T *)c->W[c->cur ^ 1], c->k, fac};
+        if (!split) { contract(epi, x3); return; }
         const int64_t count = c->n * c->k;
-        hipLaunchKernelGGL((k_wrule_exact<T>), dim3(grid_for(count)), dim3(256), 0, c->stream, (const T *)c->Wpart,
-                           c->wsplit, count, (const T *)c->W[c->cur], (T *)c->W[c->cur ^ 1], multiply,
-                           (const DevState *)c->st);
+        T *const sets[2] = {(T *)c->Wpart, (T *)c->WDpart};      // numerator (and denominator) slabs
+        EpiWpart<T, Fac::S> epip{{}, c->k, count};
+        NumSlabs<T, Fac::S> part{{}, c->wsplit, count};
+        for (int s = 0; s < Fac::S; ++s) { epip.P[s] = sets[s]; part.first.p[s] = sets[s]; }
+        contract(epip, x3);
+        hipLaunchKernelGGL((k_wrule_exact<T, Fac>), dim3(grid_for(count)), dim3(256), 0, c->stream, part, (const DevState *)c->st, epi);
         HIPCHK(hipGetLastError());
-        return;
-    }
-    EpiW<T> epi{(const T *)c->W[c->cur], (T *)c->W[c->cur ^ 1], c->k, multiply};
-    dim3 grid((unsigned)((c->k + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), 1);
-    KL_GEMM_TT(T, EpiW<T>, grid, c->stream, (int)c->n, (int)c->k,
-               (int)c->f, (const T *)qsrc, (int64_t)c->f, (int64_t)1, (const T *)c->H,
-               (int64_t)1, (int64_t)c->f, (int)c->f + GK, (const DevState *)c->st, epi);
-    HIPCHK(hipGetLastError());
+    };
+    if (c->weighted() && multiply) rule(FacDen{}, std::false_type{});      // (the start W0 = V.H0^T is unweighted under every policy)
+    else if (c->presence() && multiply) {
+        presence_S<T>(c);
+        rule(FacPresW<T>{(const T *)c->Pm, (const T *)c->pres_S, c->k, c->pres_M}, std::false_type{});
+    } else rule(FacW0{{}, multiply}, std::true_type{});
 }
 
 // numer = W[widx]^T . Q   (sum_slabs = false: the dense row chunks' slabs are left for exact_H to sum: single-context loops)
@@ -491,47 +385,59 @@ void exact_N(klnmf_ctx *c, int widx, bool sum_slabs = true) {
         if (c->prof_now) HIPCHK(hipEventRecord(evs.b, c->stream));
         return;
     }
-    if (c->weighted()) { weighted_N<T>(c, widx, sum_slabs); return; }
     if (c->presence()) presence_D<T>(c, widx);      // (the numerator below is the unweighted one, on R)
-    EpiN<T> epi{(T *)c->Npart, c->f, c->k * c->f};
     dim3 grid((unsigned)((c->f + GT - 1) / GT), (unsigned)((c->k + GT - 1) / GT), (unsigned)c->nsplit);
+    const int64_t count = c->k * c->f;
     EventPair ev{};
     if (c->prof_now) ev = begin_event(c, c->ev_col);
-    if (c->x3_fused() && c->x3_ready && widx == (c->cur ^ 1)) x3_colpass(c);
-    else KL_GEMM_TT(T, EpiN<T>, grid, c->stream, (int)c->k, (int)c->f,
-               (int)c->n, (const T *)c->W[widx], (int64_t)1, (int64_t)c->k,
-               (const T *)c->Q, (int64_t)c->f, (int64_t)1, c->kchunk,
-               (const DevState *)c->st, epi);
+#define KL_N_ARGS (int)c->k, (int)c->f, (int)c->n, (const T *)c->W[widx], (int64_t)1, (int64_t)c->k, (const T *)c->Q, (int64_t)c->f, (int64_t)1
+    if (c->weighted())         // (W^T.R, W^T.Om): form B of k_gemm_dual, the tile of W^T shared
+        hipLaunchKernelGGL((k_gemm_dual<T, EpiN<T, 2>, false>), grid, dim3(256), 0, c->stream, KL_N_ARGS, (const T *)c->Om, c->kchunk,
+                           (const DevState *)c->st, EpiN<T, 2>{{(T *)c->Npart, (T *)c->Dpart}, c->f, count});
+    else if (c->x3_fused() && c->x3_ready && widx == (c->cur ^ 1)) x3_colpass(c);
+    else KL_GEMM_TT(T, EpiN<T>, grid, c->stream, KL_N_ARGS, c->kchunk, (const DevState *)c->st, EpiN<T>{{(T *)c->Npart}, c->f, count});
+#undef KL_N_ARGS
     HIPCHK(hipGetLastError());
     if (c->prof_now) HIPCHK(hipEventRecord(ev.b, c->stream));
     if (!sum_slabs) return;
-    const int64_t count = c->k * c->f;
-    hipLaunchKernelGGL((k_sum_partials<T>), dim3(grid_for(count)), dim3(256), 0, c->stream,
-                       (const T *)c->Npart, (T *)c->numer, count, c->nsplit,
-                       (const DevState *)c->st);
+    if (c->weighted())
+        hipLaunchKernelGGL((k_sum_partials<T, 2>), dim3(grid_for(count)), dim3(256), 0, c->stream,
+                           NumArray<T, 2>{{(const T *)c->Npart, (const T *)c->Dpart}}, OutSets<T, 2>{{(T *)c->numer, (T *)c->denom}},
+                           count, c->nsplit, (const DevState *)c->st);
+    else
+        hipLaunchKernelGGL((k_sum_partials<T, 1>), dim3(grid_for(count)), dim3(256), 0, c->stream,
+                           NumArray<T, 1>{{(const T *)c->Npart}}, OutSets<T, 1>{{(T *)c->numer}}, count, c->nsplit, (const DevState *)c->st);
     HIPCHK(hipGetLastError());
 }
 
+// from_slabs (dense, short rows): the rule sums the row chunks' slabs itself -- the same bits, one launch less; else from their
+// sums: one block per row, or (long rows) S segments per row in two launches (exact.hip.h)
 template <typename T>
 void exact_H(klnmf_ctx *c, bool from_slabs = false) {
-    if (c->weighted()) { weighted_H<T>(c, from_slabs); return; }
-    if (c->presence()) { presence_H<T>(c, from_slabs); return; }
-    if (from_slabs) {             // (dense, short rows: the rule sums the row chunks' slabs itself -- the same bits, one launch less)
-        hipLaunchKernelGGL((k_update_H_slabs<T>), dim3((unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H, (const T *)c->Npart,
-                           c->nsplit, c->k * c->f, c->f, (const DevState *)c->st);
+    auto rule = [&](auto fac) {
+        typedef decltype(fac) Fac;
+        typedef NumArray<T, Fac::S> Arr;
+        typedef NumSlabs<T, Fac::S> Slabs;
+        Arr sums{}, slab0{};      // numerator (and denominator): summed, and slab 0 of the row chunks' sets
+        const T *const psums[2] = {(const T *)c->numer, (const T *)c->denom}, *const pslabs[2] = {(const T *)c->Npart, (const T *)c->Dpart};
+        for (int s = 0; s < Fac::S; ++s) { sums.p[s] = psums[s]; slab0.p[s] = pslabs[s]; }
+        if (from_slabs) {
+            hipLaunchKernelGGL((k_update_H<T, Slabs, Fac>), dim3((unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
+                               RuleIn<Slabs, Fac>{Slabs{slab0, c->nsplit, c->k * c->f}, fac}, c->f, (const DevState *)c->st);
+        } else if (c->hseg_n > 1) {
+            hipLaunchKernelGGL((k_update_H_part<T, Fac>), dim3((unsigned)c->hseg_n, (unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
+                               RuleIn<Arr, Fac>{sums, fac}, c->f, c->hseg, c->hpart, (const DevState *)c->st);
+            hipLaunchKernelGGL((k_update_H_norm<T>), dim3((unsigned)c->hseg_n, (unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
+                               c->f, c->hseg, (const double *)c->hpart, (const DevState *)c->st);
+        } else {
+            hipLaunchKernelGGL((k_update_H<T, Arr, Fac>), dim3((unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H, RuleIn<Arr, Fac>{sums, fac},
+                               c->f, (const DevState *)c->st);
+        }
         HIPCHK(hipGetLastError());
-        return;
-    }
-    if (c->hseg_n > 1) {          // long rows: S segments per row, two launches (exact.hip.h)
-        hipLaunchKernelGGL((k_update_H_part<T>), dim3((unsigned)c->hseg_n, (unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
-                           (const T *)c->numer, c->f, c->hseg, c->hpart, (const DevState *)c->st);
-        hipLaunchKernelGGL((k_update_H_norm<T>), dim3((unsigned)c->hseg_n, (unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
-                           c->f, c->hseg, (const double *)c->hpart, (const DevState *)c->st);
-    } else {
-        hipLaunchKernelGGL((k_update_H<T>), dim3((unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
-                           (const T *)c->numer, c->f, (const DevState *)c->st);
-    }
-    HIPCHK(hipGetLastError());
+    };
+    if (c->weighted()) rule(FacDen{});
+    else if (c->presence()) rule(FacPresH<T>{(const T *)c->pres_D, (const unsigned char *)c->pres_mod, c->pres_M});
+    else rule(FacNum{});
 }
 
 #define EXACT_CALL(c, fn, ...)                                         \

@@ -3,11 +3,15 @@
 // with the element-wise work fused into their epilogues.  This is the mode the
 // tight parity tests run; the throughput path is mfma.hip.h.
 //
-//   k_gemm<.., EpiQ>  W.H -> Q=(V+eps)/(WH+eps), loss partials   nmf.py:325-336, 297-310
-//   k_gemm<.., EpiW>  Q.H^T -> W*(.)                              nmf.py:338-343 (and :156 for W0)
-//   k_gemm<.., EpiN>  W^T.Q split over row chunks -> partials     nmf.py:349
-//   k_sum_partials / k_update_H                                   nmf.py:349-350, array_utils.py:19-22
+//   k_gemm<.., EpiQ<T, Weight>>   W.H -> Q=(V+eps)/(WH+eps) [* weight], loss partials   nmf.py:325-336, 297-310
+//   k_gemm<.., EpiW<T, Fac>>      Q.H^T -> W*factor                                     nmf.py:338-343 (and :156 for W0)
+//   k_gemm<.., EpiWpart<T, S>> + k_wrule_exact<T, Fac>   the same over feature chunks: slabs, then the rule from them
+//   k_gemm<.., EpiN<T, S>>        W^T.Q split over row chunks -> partials               nmf.py:349
+//   k_sum_partials<T, S> / k_update_H<T, Num, Fac> / k_update_H_part<T, Fac> + k_update_H_norm   nmf.py:349-350, array_utils.py:19-22
+// ONE family for the unweighted cost function and for the two others, whose policies the headers that include this one bring: see
+// "policies" below.
 #pragma once
+#include <type_traits>
 #include "common.hip.h"
 
 namespace klnmf {
@@ -15,28 +19,41 @@ namespace klnmf {
 constexpr int GT = 64;   // output tile edge
 constexpr int GK = 16;   // contraction step
 
+// MFMA accumulators and the 16 x 16 x 4 product in fp64 / fp32 (same operand layout: A[i][k] in lane i + 16 k, B[k][j] in lane
+// j + 16 k; probed, experiments/micro/mfma_f64_probe.hip)
+template <typename T> struct Acc4;
+template <> struct Acc4<double> { typedef __attribute__((ext_vector_type(4))) double type; };
+template <> struct Acc4<float> { typedef __attribute__((ext_vector_type(4))) float type; };
+__device__ __forceinline__ Acc4<double>::type mfma_16x16x4(double a, double b, Acc4<double>::type c) {
+    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ Acc4<float>::type mfma_16x16x4(float a, float b, Acc4<float>::type c) {
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+// row of the 16 x 16 result held in register rr of lane l (its column is l & 15): kLane (l >> 4) + kReg rr -- fp64 (l >> 4) + 4 rr,
+// fp32 4 (l >> 4) + rr
+template <typename T>
+struct MfmaRow { static constexpr int kLane = sizeof(T) == 8 ? 1 : 4, kReg = sizeof(T) == 8 ? 4 : 1; };
+
 // C[M,N] = A[M,K] . B[K,N]; element (r,c) of A is A[r*ars + c*acs] (so a
-// transposed operand is a stride swap).  256 threads, TT x TT outputs each: tiles of 64 x 64 (TT = 4) or 128 x 128 (TT = 8).
+// transposed operand is a stride swap).  256 threads, TT x TT outputs each: tiles of 64 x 64 (TT = 4).
 // blockIdx.z selects a contraction chunk [z*kchunk, (z+1)*kchunk).
 // Round 4: with 4 x 4 outputs per thread every contraction step reads 8 operands from LDS for 16 multiply-adds -- in fp64
 // that is 128 LDS cycles for 64 VALU cycles per step and workgroup: LDS-bound at a quarter of the fp64 peak (18 TFLOP/s
-// measured), with element-wise bounds-checked staging on top.  8 x 8 outputs per thread read 16 operands for 64
-// multiply-adds (LDS and VALU time balanced) and stage a quarter of the elements per flop; tiles that do not touch a matrix
-// edge load without bounds checks; the next step's operands are prefetched into registers under the current step's
-// arithmetic.  The summation order of one output element is unchanged (k ascending within its chunk): for the same chunking
-// the results are bit-identical to the 64 x 64 tiles.  128 x 128 tiles are used where their grid still fills the chip
-// (klnmf_set_problem); measured (scripts/small_problem_timing.py): see DESIGN.md.
+// measured), with element-wise bounds-checked staging on top.  Since: tiles that do not touch a matrix edge load without bounds
+// checks; the next step's operands are prefetched into registers under the current step's arithmetic.  (8 x 8 outputs per thread,
+// 128 x 128 tiles, balanced LDS and VALU time in that form; tried in round 4, instantiated nowhere since MF, and removed.)
 // MF (64 x 64 tiles): the inner product on v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32 -- wave w owns rows 16 w .. 16 w + 15 of the tile and
 // its four 16-column blocks; per 4 contraction steps one double of A and four of B per lane from the SAME LDS images (A[i][k]
-// in lane i + 16 k, B[k][j] in lane j + 16 k; result register r of lane l = D[(l >> 4) + 4 r][l & 15]: probed,
-// experiments/micro/mfma_f64_probe.hip).  Same fp64 peak as the vector pipe on this part, a sixth of the LDS reads and a
-// sixteenth of the instructions: the VALU form is LDS-bound at a quarter of that peak.  Round 1 had tried it and found no
+// in lane i + 16 k, B[k][j] in lane j + 16 k; result register r of lane l: MfmaRow).  Same fp64 peak as the vector pipe on this
+// part, a sixth of the LDS reads and a sixteenth of the instructions: the VALU form is LDS-bound at a quarter of that peak.  Round 1 had tried it and found no
 // gain (526 vs 540 us at 2000 x 4096, k = 200) because the bounds-checked synchronous staging bound the kernel then.
 template <typename T, typename Epi, int TT = 4, bool MF = false>
-__global__ __launch_bounds__(256, (TT == 4 ? 3 : 2)) void k_gemm(int M, int N, int K, const T *A, int64_t ars,
+__global__ __launch_bounds__(256, 3) void k_gemm(int M, int N, int K, const T *A, int64_t ars,
                                               int64_t acs, const T *B, int64_t brs, int64_t bcs,
                                               int kchunk, const DevState *st, Epi epi) {
     if (st && st->stop) return;
+    static_assert(TT == 4, "64 x 64 tiles");
     constexpr int TL = 16 * TT;             // tile edge
     __shared__ T As[GK][TL + 4];
     __shared__ T Bs[GK][TL + 4];
@@ -51,12 +68,10 @@ __global__ __launch_bounds__(256, (TT == 4 ? 3 : 2)) void k_gemm(int M, int N, i
     for (int i = 0; i < TT; ++i)
 #pragma unroll
         for (int j = 0; j < TT; ++j) acc[i][j] = T(0);
-    typedef __attribute__((ext_vector_type(4))) double d4_t;
-    typedef __attribute__((ext_vector_type(4))) float f4_t;
-    d4_t accm[4];
-    f4_t accf[4];
+    typedef typename Acc4<T>::type acc_t;
+    acc_t accm[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) { accm[t] = d4_t{0.0, 0.0, 0.0, 0.0}; accf[t] = f4_t{0.f, 0.f, 0.f, 0.f}; }
+    for (int t = 0; t < 4; ++t) accm[t] = acc_t{T(0), T(0), T(0), T(0)};
 
     const bool a_k_contig = (acs == 1);   // consecutive threads walk the contiguous axis
     const bool b_n_contig = (bcs == 1);
@@ -107,10 +122,8 @@ __global__ __launch_bounds__(256, (TT == 4 ? 3 : 2)) void k_gemm(int M, int N, i
     __syncthreads();
     for (int k0 = kbeg; k0 < kend; k0 += GK) {
         const bool more = k0 + GK < kend;
-        constexpr bool PREF = !(sizeof(T) == 8 && TT == 8);      // (fp64 with 8 x 8 outputs: 128 accumulator registers leave no room for the prefetch)
-        if (PREF && more) fetch(k0 + GK);
+        if (more) fetch(k0 + GK);
         if constexpr (MF) {
-            static_assert(!MF || TT == 4, "MFMA inner product: 64 x 64 tiles");
             const int lane = tid & 63, wv = tid >> 6;
 #pragma unroll
             for (int k4 = 0; k4 < GK / 4; ++k4) {
@@ -118,13 +131,11 @@ __global__ __launch_bounds__(256, (TT == 4 ? 3 : 2)) void k_gemm(int M, int N, i
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const T bv = Bs[4 * k4 + (lane >> 4)][16 * t + (lane & 15)];
-                    if constexpr (sizeof(T) == 8) accm[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, accm[t], 0, 0, 0);
-                    else accf[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, accf[t], 0, 0, 0);      // (same operand / result layout)
+                    accm[t] = mfma_16x16x4(av, bv, accm[t]);
                 }
             }
         } else {
-        constexpr int UNR = TT == 8 ? 2 : 4;
-#pragma unroll UNR
+#pragma unroll 4
         for (int kk = 0; kk < GK; ++kk) {
             T a[TT], b[TT];
 #pragma unroll
@@ -139,7 +150,6 @@ __global__ __launch_bounds__(256, (TT == 4 ? 3 : 2)) void k_gemm(int M, int N, i
         }
         __syncthreads();
         if (more) {
-            if (!PREF) fetch(k0 + GK);
             commit();
             __syncthreads();
         }
@@ -150,9 +160,8 @@ __global__ __launch_bounds__(256, (TT == 4 ? 3 : 2)) void k_gemm(int M, int N, i
         for (int t = 0; t < 4; ++t)
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
-                // result register rr of lane l: fp64 D[(l >> 4) + 4 rr][l & 15] (probed); fp32 D[4 (l >> 4) + rr][l & 15]
-                const int r = m0 + 16 * wv + (sizeof(T) == 8 ? (lane >> 4) + 4 * rr : 4 * (lane >> 4) + rr), c = n0 + 16 * t + (lane & 15);
-                if (r < M && c < N) epi.apply(r, c, sizeof(T) == 8 ? (T)accm[t][rr] : (T)accf[t][rr]);
+                const int r = m0 + 16 * wv + (MfmaRow<T>::kLane * (lane >> 4) + MfmaRow<T>::kReg * rr), c = n0 + 16 * t + (lane & 15);
+                if (r < M && c < N) epi.apply(r, c, (T)accm[t][rr]);
             }
     } else {
 #pragma unroll
@@ -166,15 +175,85 @@ __global__ __launch_bounds__(256, (TT == 4 ? 3 : 2)) void k_gemm(int M, int N, i
     epi.finish(red);
 }
 
-// Q = (V+eps)/(WH+eps) and the loss terms x*log(q) - x + y (metrics.py:18-20).
-template <typename T>
+// ---- the policies of the one family ---------------------------------------------------------------------------------------
+// The unweighted, the weighted (an n x f buffer of weights: ElemWeight, FacDen) and the masked (weights of the form P[i][m(j)]:
+// PresenceWeight, FacPresW, FacPresH) cost functions run the SAME kernels; what differs is named by three small policies, and the
+// policies of the last two are defined beside the kernels only they run, not here.
+//   element weight   of the ratio epilogue: NoWeight | ElemWeight (one per element) | PresenceWeight (one per row and column range)
+//   numerator source of a rule: NumArray (summed before) | NumSlabs (summed here: T(0) + slab 0 + slab 1 ..., z ascending);
+//                    either holds Fac::S buffer sets side by side -- the numerator, and the denominator where the factor wants one
+//   rule factor      what multiplies the old value: FacNum / FacW0 (num) | FacDen (num / den) | FacPresW, FacPresH (num / the
+//                    mask's collapsed denominator); den = 0 gives the factor 1 (w_factor)
+// An unweighted instantiation holds no weight load, no multiplication by 1 and no test the others need.
+struct NoWeight {
+    __device__ NoWeight at(int, int, int64_t) const { return NoWeight{}; }
+};
+
+template <typename T, int S>
+struct NumArray {
+    const T *p[S];
+    __device__ NumArray at(int64_t o) const {
+        NumArray r;
+#pragma unroll
+        for (int s = 0; s < S; ++s) r.p[s] = p[s] + o;
+        return r;
+    }
+    struct At {      // element j of each set, read where the factor uses it
+        const NumArray &a; int64_t j;
+        __device__ T operator[](int s) const { return a.p[s][j]; }
+    };
+    __device__ At get(int64_t j) const { return At{*this, j}; }
+};
+template <typename T, int S>
+struct Sums {
+    T v[S];
+    __device__ T operator[](int s) const { return v[s]; }
+};
+template <typename T, int S>
+struct NumSlabs {
+    NumArray<T, S> first; int nslab; int64_t slab;      // slab 0 of each set, the number of slabs, elements per slab
+    __device__ NumSlabs at(int64_t o) const { return NumSlabs{first.at(o), nslab, slab}; }
+    __device__ Sums<T, S> get(int64_t j) const {
+        static_assert(S <= 2, "numerator, denominator");
+        T g = T(0), d = T(0);
+        for (int z = 0; z < nslab; ++z) {
+            g += first.p[0][z * slab + j];
+            if constexpr (S == 2) d += first.p[1][z * slab + j];
+        }
+        if constexpr (S == 2) return Sums<T, 2>{{g, d}};
+        else return Sums<T, 1>{{g}};
+    }
+};
+// a rule's inputs as ONE kernel argument: an empty factor takes no room in it
+template <typename Num, typename Fac>
+struct RuleIn { Num num; [[no_unique_address]] Fac fac; };
+
+// of(v, r, c): the factor of element (r, c) -- (sample, component) in the W rule, (component, column) in the H rule -- from its S sums
+struct FacNum {
+    static constexpr int S = 1;
+    template <typename V> __device__ auto of(const V &v, int64_t, int64_t) const { return v[0]; }
+};
+struct FacW0 : FacNum {      // the unweighted W rule, which is also the start W0 = V.H0^T (multiply = 0: the numerator itself)
+    int multiply;
+    __device__ bool on() const { return multiply != 0; }
+};
+
+// Q = w * (V+eps)/(WH+eps) and the loss terms w * (x*log(q) - x + y) (metrics.py:18-20); NoWeight: no w at all.
+template <typename T, typename Weight = NoWeight>
 struct EpiQ {
-    const T *V; T *Q; int64_t f; double *loss_part; int write_q; double local; T eps;
+    const T *V; [[no_unique_address]] Weight wt; T *Q; int64_t f; double *loss_part; int write_q; double local; T eps;
     __device__ void apply(int r, int c, T y) {
-        const T x = V[(int64_t)r * f + c];
+        const int64_t o = (int64_t)r * f + c;
+        const T x = V[o];
+        const auto w = wt.at(r, c, o);      // (NoWeight: nothing is read)
         const T q = (x + eps) / (y + eps);
-        if (write_q) Q[(int64_t)r * f + c] = q;
-        local += (double)(x * log(q) - x + y);
+        if constexpr (std::is_same<Weight, NoWeight>::value) {
+            if (write_q) Q[o] = q;
+            local += (double)(x * log(q) - x + y);
+        } else {
+            if (write_q) Q[o] = w * q;
+            if (w != T(0)) local += (double)(w * (x * log(q) - x + y));      // (w = 0: a loss term of exactly 0)
+        }
     }
     __device__ void finish(double *red) {
         const double t = block_sum(local, red);
@@ -182,33 +261,41 @@ struct EpiQ {
     }
 };
 
-// W_new = W_old * acc (update) or acc (W0 = V.H^T).
-template <typename T>
+// W_new = W_old * factor (fac.on(); FacW0 with multiply = 0: W_new = the numerator).  Epilogue of the whole contraction -- one
+// accumulator, or two from k_gemm_dual -- and the rule of k_wrule_exact behind a split one.
+template <typename T, typename Fac>
 struct EpiW {
-    const T *Wold; T *Wnew; int64_t k; int multiply;
-    __device__ void apply(int r, int c, T g) {
-        const int64_t o = (int64_t)r * k + c;
-        Wnew[o] = multiply ? Wold[o] * g : g;
+    static constexpr int sets = Fac::S;
+    const T *Wold; T *Wnew; int64_t k; [[no_unique_address]] Fac fac;
+    template <typename V>
+    __device__ void rule(int64_t o, int64_t r, int64_t c, const V &v) {
+        Wnew[o] = fac.on() ? Wold[o] * fac.of(v, r, c) : fac.of(v, r, c);
     }
+    __device__ void apply(int r, int c, T g) { rule((int64_t)r * k + c, r, c, Sums<T, 1>{{g}}); }
+    __device__ void apply(int r, int c, T num, T den) { rule((int64_t)r * k + c, r, c, Sums<T, 2>{{num, den}}); }
     __device__ void finish(double *) {}
 };
 
 // Split contraction of the W rule (few rows: n*k/4096 output tiles would leave the chip idle while each walks all of
-// f): blockIdx.z = chunk of the feature axis, partial Q.H^T into slab z; k_wrule_exact sums the slabs in a fixed order.
-template <typename T>
+// f): blockIdx.z = chunk of the feature axis, partial Q.H^T into slab z of each of the S sets; k_wrule_exact sums the slabs
+// in a fixed order.
+template <typename T, int S = 1>
 struct EpiWpart {
-    T *P; int64_t k; int64_t slab;      // slab = n*k
-    __device__ void apply(int r, int c, T g) { P[blockIdx.z * slab + (int64_t)r * k + c] = g; }
+    static constexpr int sets = S;
+    T *P[S]; int64_t k; int64_t slab;      // slab = n*k
+    __device__ void apply(int r, int c, T g) { P[0][blockIdx.z * slab + (int64_t)r * k + c] = g; }
+    __device__ void apply(int r, int c, T num, T den) {
+        const int64_t o = blockIdx.z * slab + (int64_t)r * k + c;
+        P[0][o] = num; P[1][o] = den;
+    }
     __device__ void finish(double *) {}
 };
-template <typename T>
-__global__ void k_wrule_exact(const T *part, int nslab, int64_t count, const T *Wold, T *Wnew, int multiply,
-                              const DevState *st) {
+template <typename T, typename Fac>
+__global__ void k_wrule_exact(NumSlabs<T, Fac::S> part, const DevState *st, EpiW<T, Fac> epi) {
     if (st && st->stop) return;
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < count; e += (int64_t)gridDim.x * blockDim.x) {
-        T g = T(0);
-        for (int z = 0; z < nslab; ++z) g += part[z * count + e];
-        Wnew[e] = multiply ? Wold[e] * g : g;
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < part.slab; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = e / epi.k;
+        epi.rule(e, r, e - r * epi.k, part.get(e));
     }
 }
 
@@ -220,41 +307,55 @@ struct EpiStore {
     __device__ void finish(double *) {}
 };
 
-// Partial numerator of the H rule for one row chunk.
-template <typename T>
+// Partial numerator (S = 2: and denominator) of the H rule for one row chunk.
+template <typename T, int S = 1>
 struct EpiN {
-    T *Npart; int64_t f; int64_t slab;   // slab = k*f
-    __device__ void apply(int r, int c, T v) { Npart[blockIdx.z * slab + (int64_t)r * f + c] = v; }
+    T *Npart[S]; int64_t f; int64_t slab;   // slab = k*f
+    __device__ void apply(int r, int c, T v) { Npart[0][blockIdx.z * slab + (int64_t)r * f + c] = v; }
+    __device__ void apply(int r, int c, T num, T den) {
+        const int64_t o = blockIdx.z * slab + (int64_t)r * f + c;
+        Npart[0][o] = num; Npart[1][o] = den;
+    }
     __device__ void finish(double *) {}
 };
 
-template <typename T>
-__global__ void k_sum_partials(const T *part, T *out, int64_t count, int nslab,
-                               const DevState *st) {
+template <typename T, int S>
+struct OutSets { T *p[S]; };
+template <typename T, int S>
+__global__ void k_sum_partials(NumArray<T, S> part, OutSets<T, S> out, int64_t count, int nslab, const DevState *st) {
     if (st && st->stop) return;
+    const NumSlabs<T, S> slabs{part, nslab, count};
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < count;
          e += (int64_t)gridDim.x * blockDim.x) {
-        T s = T(0);
-        for (int z = 0; z < nslab; ++z) s += part[z * count + e];
-        out[e] = s;
+        const Sums<T, S> v = slabs.get(e);
+#pragma unroll
+        for (int s = 0; s < S; ++s) out.p[s][e] = v[s];
     }
 }
 
-// H <- H*num, rows divided by (1e-16 + row sum).  One block per component row.
-template <typename T>
-__global__ __launch_bounds__(256) void k_update_H(T *H, const T *num, int64_t f,
-                                                  const DevState *st) {
+// The product of the H rule, written once: row[j] <- row[j] * factor over j0 + tid, + 256, ... < j1; returns the thread's fp64
+// sum of the products.
+template <typename T, typename Num, typename Fac>
+__device__ __forceinline__ double h_product(T *row, const Num &num, const Fac &fac, int64_t a, int64_t j0, int64_t j1) {
+    double s = 0;
+    for (int64_t j = j0 + threadIdx.x; j < j1; j += blockDim.x) {
+        const auto nv = num.get(j);      // (slabs: summed here, in front of the read of row[j])
+        const T v = row[j] * fac.of(nv, a, j);
+        row[j] = v;
+        s += (double)v;
+    }
+    return s;
+}
+
+// H <- H*factor, rows divided by (1e-16 + row sum).  One block per component row.  Num = NumSlabs (single-context loops): the
+// rule straight from the row chunks' slabs, summed in k_sum_partials' order -- one launch instead of two, the same bits.
+template <typename T, typename Num, typename Fac>
+__global__ __launch_bounds__(256) void k_update_H(T *H, RuleIn<Num, Fac> in, int64_t f, const DevState *st) {
     if (st && st->stop) return;
     __shared__ double red[16];
     __shared__ double total;
     T *row = H + blockIdx.x * f;
-    const T *nrow = num + blockIdx.x * f;
-    double s = 0;
-    for (int64_t j = threadIdx.x; j < f; j += blockDim.x) {
-        const T v = row[j] * nrow[j];
-        row[j] = v;
-        s += (double)v;
-    }
+    const double s = h_product(row, in.num.at(blockIdx.x * f), in.fac, (int64_t)blockIdx.x, 0, f);
     const double t = block_sum(s, red);
     if (threadIdx.x == 0) total = t;
     __syncthreads();
@@ -264,21 +365,15 @@ __global__ __launch_bounds__(256) void k_update_H(T *H, const T *num, int64_t f,
 
 // The same rule for long rows (round 4: the CSR problems have f = 110 000 columns and k = 50 components -- 50 blocks walked
 // 880 KB each, three dependent passes: 0.33 ms of a 3.3 ms iteration): the row in S segments, two launches, no communication
-// inside a launch.  k_update_H_part: H * num written back + the segment's fp64 partial sum; k_update_H_norm: every block adds
+// inside a launch.  k_update_H_part: H * factor written back + the segment's fp64 partial sum; k_update_H_norm: every block adds
 // the row's S partial sums in the same fixed order and divides its segment.
-template <typename T>
-__global__ __launch_bounds__(256) void k_update_H_part(T *H, const T *num, int64_t f, int64_t seg, double *part, const DevState *st) {
+template <typename T, typename Fac>
+__global__ __launch_bounds__(256) void k_update_H_part(T *H, RuleIn<NumArray<T, Fac::S>, Fac> in, int64_t f, int64_t seg,
+                                                       double *part, const DevState *st) {
     if (st && st->stop) return;
     __shared__ double red[16];
     const int64_t a = blockIdx.y, j0 = blockIdx.x * seg, j1 = min(f, j0 + seg);
-    T *row = H + a * f;
-    const T *nrow = num + a * f;
-    double s = 0;
-    for (int64_t j = j0 + threadIdx.x; j < j1; j += blockDim.x) {
-        const T v = row[j] * nrow[j];
-        row[j] = v;
-        s += (double)v;
-    }
+    const double s = h_product(H + a * f, in.num.at(a * f), in.fac, a, j0, j1);
     const double t = block_sum(s, red);
     if (threadIdx.x == 0) part[a * gridDim.x + blockIdx.x] = t;
 }
@@ -324,30 +419,6 @@ KL_GLOBAL __launch_bounds__(1024) void k_sum_doubles(const double *part, int64_t
     for (int64_t e = threadIdx.x; e < count; e += blockDim.x) s += part[e];
     const double t = block_sum(s, red);
     if (threadIdx.x == 0) { out[0] = t; out[1] = 0; decide_here(dec, t); }
-}
-
-// The H rule straight from the row chunks' slabs (single-context loops): num[j] = sum_z part[z][a][j] in k_sum_partials'
-// order, then exactly k_update_H -- one launch instead of two, the same bits.
-template <typename T>
-__global__ __launch_bounds__(256) void k_update_H_slabs(T *H, const T *part, int nslab, int64_t slab, int64_t f, const DevState *st) {
-    if (st && st->stop) return;
-    __shared__ double red[16];
-    __shared__ double total;
-    T *row = H + blockIdx.x * f;
-    const T *prow = part + blockIdx.x * f;
-    double s = 0;
-    for (int64_t j = threadIdx.x; j < f; j += blockDim.x) {
-        T nj = T(0);
-        for (int z = 0; z < nslab; ++z) nj += prow[z * slab + j];
-        const T v = row[j] * nj;
-        row[j] = v;
-        s += (double)v;
-    }
-    const double t = block_sum(s, red);
-    if (threadIdx.x == 0) total = t;
-    __syncthreads();
-    const T d = (T)(kEpsNorm + total);
-    for (int64_t j = threadIdx.x; j < f; j += blockDim.x) row[j] = row[j] / d;
 }
 
 // V[row0+i, col0+j] = scale * src[i, j]  (learner.py:53-56 fused into the upload).

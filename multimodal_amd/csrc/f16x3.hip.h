@@ -20,7 +20,7 @@
 // LDS, MFMA-2 (Q.H^T into 64 x KP fp32 accumulators held in registers across the tiles).  Behind the last tile: the W rule
 // W_new = W (Q.H^T) (EpiW), qr, xmax.  LDS: 151 KiB at KP = 256 (one workgroup per CU; static_assert below).
 // k_colpass_x3: W^T.Q of one row chunk into a fixed-order fp32 slab per chunk ([z][k][f], EpiN's layout) -- k_sum_partials /
-// k_update_H_slabs, the H rule and the exchange of the numerator are the fp32 mode's.
+// k_update_H on the slabs, the H rule and the exchange of the numerator are the fp32 mode's.
 #pragma once
 #include "common.hip.h"
 

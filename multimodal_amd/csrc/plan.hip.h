@@ -70,7 +70,7 @@ struct ProblemPlan {
     static bool row_chunks_possible_q8(int64_t n, bool big_k) { return big_k ? n >= 65536 : n > 32768; }
 };
 
-// A single-context fit loop (piece_fit_tail) applies the H rule straight from the row chunks' slabs (k_update_H_slabs) where that
+// A single-context fit loop (piece_fit_tail) applies the H rule straight from the row chunks' slabs (k_update_H on NumSlabs) where that
 // is a few thousand loads per row; beyond, and in segments, the slabs are summed first (k_sum_partials).  KLNMF_Q_EX_H_FROM_SLABS.
 inline bool h_from_slabs(const ProblemPlan *p) {
     return !p->sparse && p->hseg_n == 1 && (int64_t)p->nsplit * p->f <= 8192;

@@ -5,12 +5,14 @@
 //   Om.H^T      = P.S    S[m][a] = sum of H[a][j] over the columns j of modality m   (M x k; n M k work)
 //   (W^T.Om)[a][j] = D[a][m(j)]    D = W^T.P                                         (k x M; n k M work)
 // so an iteration is the unweighted loop's three contractions of n f k plus these, and V and R are its only n x f streams:
-//   k_gemm<.., EpiQp>   W.H -> R = p * Q, loss partials of p * (V log Q - V + Y)      (p = 0: R = 0, a loss term of exactly 0)
-//   k_presence_S        S from the current H, once per W rule
-//   k_gemm<.., EpiWp>   R.H^T -> W * num / (P.S)   (feature chunks: EpiWpart's slabs, summed by k_wrule_exact_p)
-//   k_gemm<.., EpiN>    W_new^T.R: the unweighted H numerator, unchanged
-//   k_presence_D_part / k_presence_D_sum      D = W_new^T.P over row chunks, slabs in double summed in a fixed order
-//   k_update_H_p / _part_p / _slabs_p         the H rule: factor = D > 0 ? num / D : 1
+//   k_gemm<.., EpiQ<T, PresenceWeight>>   W.H -> R = p * Q, loss partials of p * (V log Q - V + Y)   (p = 0: R = 0, a loss term of exactly 0)
+//   k_presence_S                           S from the current H, once per W rule
+//   k_gemm<.., EpiW<T, FacPresW>>          R.H^T -> W * num / (P.S)   (feature chunks: EpiWpart's slabs, summed by k_wrule_exact<T, FacPresW>)
+//   k_gemm<.., EpiN<T>>                    W_new^T.R: the unweighted H numerator, unchanged
+//   k_presence_D_part / k_presence_D_sum   D = W_new^T.P over row chunks, slabs in double summed in a fixed order
+//   k_update_H / k_update_H_part under FacPresH   the H rule: factor = D > 0 ? num / D : 1
+// The ratio epilogue and the rules are the one family of exact.hip.h under the policies PresenceWeight, FacPresW and FacPresH; this
+// file holds them and what only a masked problem runs: k_presence_S, k_presence_D_part, k_presence_D_sum.
 // S and D are accumulated in double in a fixed order and rounded once to T (as the H rule's row sums are): two runs give the
 // same bits.  The routes (row chunks, feature chunks, segments, rule from the slabs) are the unweighted plan's.
 #pragma once
@@ -28,22 +30,11 @@ inline int presence_d_chunks(int64_t n) {
     return (int)(c < 1 ? 1 : (c > kPresDMaxChunks ? kPresDMaxChunks : c));
 }
 
-// R = p * (V+eps)/(WH+eps) and the loss terms p * (x*log(q) - x + y), p = P[r][m(c)]: EpiQw with the weight looked up per
-// element (a 64-column tile may hold several modalities).
+// the weight of element (r, c): p = P[r][m(c)], looked up per element (a 64-column tile may hold several modalities)
 template <typename T>
-struct EpiQp {
-    const T *V; const T *P; const unsigned char *mod; T *R; int64_t f; int nmod; double *loss_part; int write_q; double local; T eps;
-    __device__ void apply(int r, int c, T y) {
-        const int64_t o = (int64_t)r * f + c;
-        const T x = V[o], p = P[(int64_t)r * nmod + mod[c]];
-        const T q = (x + eps) / (y + eps);
-        if (write_q) R[o] = p * q;
-        if (p != T(0)) local += (double)(p * (x * log(q) - x + y));
-    }
-    __device__ void finish(double *red) {
-        const double t = block_sum(local, red);
-        if (threadIdx.x == 0) loss_part[blockIdx.y * gridDim.x + blockIdx.x] = t;
-    }
+struct PresenceWeight {
+    const T *P; const unsigned char *mod; int nmod;
+    __device__ T at(int r, int c, int64_t) const { return P[(int64_t)r * nmod + mod[c]]; }
 };
 
 // S[m][a] = sum over modality m's columns of H[a][j]: one block per (a, m), fp64 partial sums per thread (stride 256), the
@@ -69,29 +60,23 @@ __device__ __forceinline__ T presence_den(const T *prow, const T *S, int64_t k, 
     return den;
 }
 
-// W_new = W_old * (R.H^T) / (P.S); a sample with no present modality (denominator 0) keeps its coefficients.
+// W rule: num / (P.S)[r][c]; a sample with no present modality (denominator 0) keeps its coefficients.  No denominator slabs.
 template <typename T>
-struct EpiWp {
-    const T *Wold; T *Wnew; int64_t k; const T *P; const T *S; int nmod;
-    __device__ void apply(int r, int c, T num) {
-        const int64_t o = (int64_t)r * k + c;
-        Wnew[o] = Wold[o] * w_factor(num, presence_den(P + (int64_t)r * nmod, S, k, c, nmod));
-    }
-    __device__ void finish(double *) {}
+struct FacPresW {
+    static constexpr int S = 1;
+    const T *P; const T *Sm; int64_t k; int nmod;
+    __device__ bool on() const { return true; }
+    template <typename V>
+    __device__ T of(const V &v, int64_t r, int64_t c) const { return w_factor(v[0], presence_den(P + r * nmod, Sm, k, (int)c, nmod)); }
 };
-
-// ... from the feature chunks' numerator slabs (EpiWpart): k_wrule_exact with the same denominator; no denominator slabs.
+// H rule: num / D[a][m(j)]
 template <typename T>
-__global__ void k_wrule_exact_p(const T *part, int nslab, int64_t count, const T *Wold, T *Wnew, const T *P, const T *S, int64_t k,
-                                int nmod, const DevState *st) {
-    if (st && st->stop) return;
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < count; e += (int64_t)gridDim.x * blockDim.x) {
-        T g = T(0);
-        for (int z = 0; z < nslab; ++z) g += part[z * count + e];
-        const int64_t r = e / k;
-        Wnew[e] = Wold[e] * w_factor(g, presence_den(P + r * nmod, S, k, (int)(e - r * k), nmod));
-    }
-}
+struct FacPresH {
+    static constexpr int S = 1;
+    const T *D; const unsigned char *mod; int nmod;
+    template <typename V>
+    __device__ T of(const V &v, int64_t a, int64_t j) const { return w_factor(v[0], (D + a * nmod)[mod[j]]); }
+};
 
 // D = W^T.P over one row chunk: block (x, z) takes components 64 x .. 64 x + 63 and rows [z * chunk, (z + 1) * chunk); wave w
 // walks the chunk's rows w, w + 4, ... (64 consecutive components of a row of W per load), every lane holds M fp64 sums; the
@@ -138,71 +123,6 @@ __global__ void k_presence_D_sum(const double *slab, int nslab, int64_t count, T
         for (int z = 0; z < nslab; ++z) s += slab[z * count + e];
         D[e] = (T)s;
     }
-}
-
-// H <- H * num / D[a][m(j)] (factor 1 where D = 0), rows divided by (1e-16 + row sum): k_update_H with the mask's factor.
-template <typename T>
-__global__ __launch_bounds__(256) void k_update_H_p(T *H, const T *num, const T *D, const unsigned char *mod, int nmod, int64_t f,
-                                                    const DevState *st) {
-    if (st && st->stop) return;
-    __shared__ double red[16];
-    __shared__ double total;
-    T *row = H + blockIdx.x * f;
-    const T *nrow = num + blockIdx.x * f, *drow = D + (int64_t)blockIdx.x * nmod;
-    double s = 0;
-    for (int64_t j = threadIdx.x; j < f; j += blockDim.x) {
-        const T v = row[j] * w_factor(nrow[j], drow[mod[j]]);
-        row[j] = v;
-        s += (double)v;
-    }
-    const double t = block_sum(s, red);
-    if (threadIdx.x == 0) total = t;
-    __syncthreads();
-    const T d = (T)(kEpsNorm + total);
-    for (int64_t j = threadIdx.x; j < f; j += blockDim.x) row[j] = row[j] / d;
-}
-
-// ... for long rows: the segment's product and partial sum (k_update_H_part); k_update_H_norm follows unchanged.
-template <typename T>
-__global__ __launch_bounds__(256) void k_update_H_part_p(T *H, const T *num, const T *D, const unsigned char *mod, int nmod, int64_t f,
-                                                         int64_t seg, double *part, const DevState *st) {
-    if (st && st->stop) return;
-    __shared__ double red[16];
-    const int64_t a = blockIdx.y, j0 = blockIdx.x * seg, j1 = min(f, j0 + seg);
-    T *row = H + a * f;
-    const T *nrow = num + a * f, *drow = D + a * nmod;
-    double s = 0;
-    for (int64_t j = j0 + threadIdx.x; j < j1; j += blockDim.x) {
-        const T v = row[j] * w_factor(nrow[j], drow[mod[j]]);
-        row[j] = v;
-        s += (double)v;
-    }
-    const double t = block_sum(s, red);
-    if (threadIdx.x == 0) part[a * gridDim.x + blockIdx.x] = t;
-}
-
-// ... straight from the row chunks' numerator slabs (k_update_H_slabs): the bits of k_sum_partials + k_update_H_p.
-template <typename T>
-__global__ __launch_bounds__(256) void k_update_H_slabs_p(T *H, const T *part, int nslab, int64_t slab, const T *D,
-                                                          const unsigned char *mod, int nmod, int64_t f, const DevState *st) {
-    if (st && st->stop) return;
-    __shared__ double red[16];
-    __shared__ double total;
-    T *row = H + blockIdx.x * f;
-    const T *prow = part + blockIdx.x * f, *drow = D + (int64_t)blockIdx.x * nmod;
-    double s = 0;
-    for (int64_t j = threadIdx.x; j < f; j += blockDim.x) {
-        T nj = T(0);
-        for (int z = 0; z < nslab; ++z) nj += prow[z * slab + j];
-        const T v = row[j] * w_factor(nj, drow[mod[j]]);
-        row[j] = v;
-        s += (double)v;
-    }
-    const double t = block_sum(s, red);
-    if (threadIdx.x == 0) total = t;
-    __syncthreads();
-    const T d = (T)(kEpsNorm + total);
-    for (int64_t j = threadIdx.x; j < f; j += blockDim.x) row[j] = row[j] / d;
 }
 
 }  // namespace klnmf

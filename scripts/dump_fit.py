@@ -26,6 +26,14 @@ CASES = [(3000, 520, 200, 4, 'f16', None, None), (70000, 256, 200, 5, 'f16', Non
          (700, 900, 200, 4, 'f16x3', None, None), (600, 800, 300, 3, 'f16x3', None, None),
          (90000, 6144, 200, 2, 'f16', None, None),
          (4000, 30000, 32, 4, 'f32', None, 0.02), (300, 700, 513, 3, 'f64', None, 0.1)]
+# weighted and masked fits of the exact modes (n, f, k, iterations, precision, 'weights' | 'presence', route), built the way
+# tests/test_weighted_gpu.py and tests/test_presence_gpu.py build theirs (weighted_cases.general; presence_cases.mask / bounds with
+# three modalities).  route: what (W chunks, H segments, H rule from the slabs) of the context's plan must be (cost_fit asserts
+# it; None: any) -- the whole W rule with the H rule from the slabs, the issue's 3000 x 520 (W chunks, H rule from the summed
+# slabs on a 256-CU device), and several W chunks with H segments
+COST_SHAPES = ((4111, 63, 200, 4, (1, 1, 1)), (3000, 520, 20, 4, None), (100, 16385, 33, 3, ('>1', '>1', 0)))
+COST_CASES = [(n, f, k, it, prec, cost, route) for (n, f, k, it, route) in COST_SHAPES for prec in ('f64', 'f32')
+              for cost in ('weights', 'presence')]
 POOLED_SEQUENCES = {
     'pool_f32': [(500, 300, 20, 5, 'f32', None, None), (2000, 3000, 16, 4, 'f32', None, 0.02), (1200, 700, 40, 5, 'f32', None, None)],
     'pool_f16': [(70000, 256, 200, 5, 'f16', None, None), (520, 1030, 200, 5, 'f16', None, None), (40000, 512, 50, 6, 'f16', None, None)],
@@ -54,6 +62,32 @@ def fit(case):
     return W, m.components_, np.array(e), m.last_fp8_report
 
 
+def cost_fit(case):
+    """(W, H, losses, route) of one seeded weighted or masked fit on a context of its own."""
+    from multimodal_amd import _native
+    from oracle import klnmf_oracle as orc
+    from tests import presence_cases as pc
+    from tests import weighted_cases as wc
+    n, f, k, iters, prec, cost, want = case
+    dt = np.float64 if prec == 'f64' else np.float32
+    V, H0 = orc.synthetic_V(5, n, f, min(k, 32)), orc.synthetic_H0(5, f, k)
+    with _native.Context(prec) as ctx:
+        ctx.set_problem(n, f, k, iters)
+        ctx.upload_V(V.astype(dt))
+        if cost == 'weights':
+            ctx.upload_weights(wc.general(n, f, seed=3 * n + 5 * f + k).astype(dt))
+        else:
+            ctx.upload_presence(pc.mask(n, 3, seed=3 * n + 5 * f + k).astype(dt), pc.bounds(f, 3))
+        route = list(ctx.exact_regime())
+        for got, w in zip(route[1:], want or ()):
+            assert (got > 1) if w == '>1' else (got == w), (case, route)
+        ctx.set_H(H0.astype(dt))
+        ctx.init_W()
+        errors, n_done, _ = ctx.run(iters, True, -1e300)
+        assert n_done == iters
+        return ctx.get_W(), ctx.get_H(), np.array(errors), route
+
+
 def main():
     if sys.argv[1] == '--cmp':
         a, b = np.load(sys.argv[2]), np.load(sys.argv[3])
@@ -61,13 +95,13 @@ def main():
         for key in a.files:
             same = key in b.files and np.array_equal(a[key], b[key])
             d = np.abs(a[key].astype(np.float64) - b[key].astype(np.float64)).max() / max(1e-300, np.abs(a[key]).max()) if key in b.files else np.nan
-            print('%-28s %s  (max rel diff %.2e)' % (key, 'identical' if same else 'DIFFERENT', d))
+            print('%-36s %s  (max rel diff %.2e)' % (key, 'identical' if same else 'DIFFERENT', d))
             bad += 0 if same else 1
         for name, z in ((sys.argv[2], a), (sys.argv[3], b)):
             for key in z.files:
                 if '_third_' in key:
                     same = np.array_equal(z[key], z[key.replace('_third_', '_fresh_')])
-                    print('%-28s %s its fresh-context twin in %s' % (key, 'identical to' if same else 'DIFFERENT from', name))
+                    print('%-36s %s its fresh-context twin in %s' % (key, 'identical to' if same else 'DIFFERENT from', name))
                     bad += 0 if same else 1
         sys.exit(1 if bad else 0)
     out = {}
@@ -83,6 +117,11 @@ def main():
 
     for case in CASES:
         record(tag_of(case), case)
+    for case in COST_CASES:
+        tag = '%dx%dk%d_%s_%s' % (case[0], case[1], case[2], case[4], case[5])
+        W, H, e, route = cost_fit(case)
+        out[tag + '_W'], out[tag + '_H'], out[tag + '_e'] = W, H, e
+        print(tag, 'loss', e[-1], 'route', route, flush=True)
     for name, seq in POOLED_SEQUENCES.items():
         for i, case in enumerate(seq):
             record('%s_%s_%s' % (name, ('first', 'second', 'third')[i], tag_of(case)), case)

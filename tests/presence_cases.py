@@ -1,4 +1,5 @@
-"""The masked KL-NMF update in its factored form (multimodal_amd/csrc/presence.hip.h) restated in fp64, and the masks and column
+"""The masked KL-NMF update in its factored form (the exact kernel family of multimodal_amd/csrc/exact.hip.h under
+presence.hip.h's policies) restated in fp64, and the masks and column
 bounds the tests use.
 
 The weights are Om[i, j] = P[i, m(j)]: P is n x M, m(j) the modality whose column range [bounds[m], bounds[m + 1]) holds j.

@@ -229,13 +229,16 @@ def test_the_new_export_is_declared_bound_and_exported():
 
 
 def test_the_masked_route_is_a_host_branch():
-    """No kernel of exact.hip.h or weighted.hip.h knows of the mask; the masked kernels live in presence.hip.h."""
+    """No code of exact.hip.h or weighted.hip.h knows of the mask; its policies and its own kernels live in presence.hip.h."""
     csrc = os.path.join(ROOT, 'multimodal_amd', 'csrc')
     for name in ('exact.hip.h', 'weighted.hip.h'):
-        assert not re.search(r'presence|modalit', open(os.path.join(csrc, name)).read()), name
-    text = open(os.path.join(csrc, 'presence.hip.h')).read()
-    for kernel in ('EpiQp', 'k_presence_S', 'EpiWp', 'k_wrule_exact_p', 'k_presence_D_part', 'k_presence_D_sum', 'k_update_H_p',
-                   'k_update_H_part_p', 'k_update_H_slabs_p'):
-        assert kernel in text, kernel
+        whole = open(os.path.join(csrc, name)).read()
+        assert not re.search(r'presence|modalit', whole), name                        # (comments included)
+        assert 'Pres' not in re.sub(r'//[^\n]*', '', whole), name                     # the mask's policies: named in comments at most
+    text = re.sub(r'//[^\n]*', '', open(os.path.join(csrc, 'presence.hip.h')).read())
+    for name in ('PresenceWeight', 'k_presence_S', 'presence_den', 'FacPresW', 'k_presence_D_part', 'k_presence_D_sum', 'FacPresH',
+                 'presence_d_chunks'):
+        assert name in text, name
+    assert not re.search(r'k_update_H|k_wrule_exact|struct Epi', text)        # the rules and epilogues are the family's
     loop = open(os.path.join(csrc, 'api_loop.hip')).read()
-    assert all(('presence_%s<T>' % p) in loop for p in 'QWDH')
+    assert all(('presence_%s<T>' % p) in loop for p in 'SD')

@@ -251,16 +251,28 @@ def test_the_new_exports_are_declared_bound_and_exported():
     assert callable(_native.Context.upload_weights) and callable(_native.Context.clear_weights)
 
 
+def _code(path):
+    """The file without its // comments."""
+    return re.sub(r'//[^\n]*', '', open(path).read())
+
+
 def test_the_weighted_route_is_a_host_branch():
-    """No kernel of exact.hip.h knows of weights, the weighted kernels live in weighted.hip.h and every new buffer is problem
-    state sized by the unweighted plan's counts."""
+    """One kernel family (exact.hip.h) under policies: its own file names no weight buffer and keeps the unweighted epilogue a
+    compile-time branch of its own, every rule kernel exists once, what only a weighted problem runs lives in weighted.hip.h and
+    every new buffer is problem state sized by the unweighted plan's counts."""
     csrc = os.path.join(ROOT, 'multimodal_amd', 'csrc')
-    exact = open(os.path.join(csrc, 'exact.hip.h')).read()
-    assert not re.search(r'weight|\bOm\b', exact)
-    weighted = open(os.path.join(csrc, 'weighted.hip.h')).read()
-    for kernel in ('EpiQw', 'k_gemm_dual', 'k_wrule_exact_w', 'k_update_H_w', 'k_update_H_part_w', 'k_update_H_slabs_w'):
-        assert kernel in weighted, kernel
-    assert 'mfma_f64_16x16x4f64' in weighted and 'mfma_f32_16x16x4f32' in weighted
+    assert not re.search(r'\bOm\b', open(os.path.join(csrc, 'exact.hip.h')).read())        # (comments included)
+    exact = _code(os.path.join(csrc, 'exact.hip.h'))
+    assert 'if constexpr (std::is_same<Weight, NoWeight>::value)' in exact
+    weighted = _code(os.path.join(csrc, 'weighted.hip.h'))
+    for name in ('ElemWeight', 'FacDen', 'w_factor', 'k_gemm_dual', 'k_fill'):
+        assert name in weighted, name
+    family = exact + weighted + _code(os.path.join(csrc, 'presence.hip.h'))
+    for kernel in ('k_update_H', 'k_update_H_part', 'k_update_H_norm', 'k_wrule_exact', 'k_sum_partials', 'h_product'):
+        assert len(re.findall(r'\b%s\(' % kernel, family)) == 1 + (kernel == 'h_product') * 2, kernel      # defined once (h_product: + two calls)
+    for epi in ('EpiQ', 'EpiW', 'EpiWpart', 'EpiN'):
+        assert len(re.findall(r'struct %s\b' % epi, family)) == 1, epi
+    assert 'mfma_f64_16x16x4f64' in exact and 'mfma_f32_16x16x4f32' in exact
     ctx = open(os.path.join(csrc, 'ctx.hip.h')).read()
     state = ctx[ctx.index('struct ProblemState'):ctx.index('struct LoopState')]
     assert re.search(r'\*Om\b', state) and 'Dpart' in state

@@ -1,4 +1,5 @@
-"""The weighted / masked KL-NMF update (multimodal_amd/csrc/weighted.hip.h) restated in fp64, and the weights the tests use.
+"""The weighted / masked KL-NMF update (the exact kernel family of multimodal_amd/csrc/exact.hip.h under weighted.hip.h's policies)
+restated in fp64, and the weights the tests use.
 
 With Om >= 0 (n x f), eps = 1e-8 and Y = W.H one iteration is
     Q = (V + eps) / (Y + eps),  loss = sum Om o (V log Q - V + Y)  (before the update),  R = Om o Q
