@@ -158,6 +158,23 @@ int klnmf_clear_weights(klnmf_ctx *ctx);
 int klnmf_upload_presence(klnmf_ctx *ctx, const void *src, int dtype,
                           int64_t rows, int64_t ld, int64_t row0,
                           const int64_t *col_bounds, int n_mod);
+/* klnmf_upload_presence for a mask that lives in DEVICE memory of the context's device, gathered there by row index and by source
+ * column in one launch (the reference has no counterpart: it has no mask, and experiment.py:163-164 slices every per-sample array
+ * of a run on the host):
+ *     P[row0 + i, m] = src_cols[m] >= 0 ? dP[drow_idx[i] * ld + src_cols[m]] : 1          i < rows, m < n_mod
+ * dP: src_rows rows, ld elements apart, KLNMF_DT_F32 or KLNMF_DT_F64, cast to the context's type as klnmf_upload_presence casts a
+ * host upload (a float64 source in KLNMF_PREC_F64 gives P the bits of the host path).  drow_idx: `rows` int64 indices in device
+ * memory, any order, repeats allowed; null: rows 0 .. rows - 1 of the source (as klnmf_upload_V_device_rows_dt reads it).
+ * src_cols: n_mod source columns, each in [0, ld) or -1 (the modality has no column: its weight is 1).  col_bounds, n_mod, row0:
+ * as in klnmf_upload_presence.  State and refusals are klnmf_upload_presence's -- the first mask upload of a problem fixes the
+ * bounds and takes P filled with 1; KLNMF_ERR_UNSUPP on a CSR problem, outside KLNMF_PREC_F64 / F32 and while a loop over row
+ * shards is open; KLNMF_ERR_ARG for bad bounds, n_mod out of range, rows out of range, a problem that holds weights -- and
+ * KLNMF_ERR_ARG as well for a source column outside [-1, ld) and for a row index outside [0, src_rows): the indices are checked
+ * on the device before anything is read through them, the host reads the flag back, and only then is the mask taken and the
+ * gather launched.  A refused call leaves the problem exactly as it was.  Synchronous: dP and drow_idx are free to go on return. */
+int klnmf_upload_presence_device_rows(klnmf_ctx *ctx, const void *dP, int dtype, int64_t src_rows, int64_t ld,
+                                      const int64_t *drow_idx, int64_t rows, int64_t row0,
+                                      const int *src_cols, const int64_t *col_bounds, int n_mod);
 /* Dictionary [k,f], C order (nmf.py:149-155 `_init_dictionary`, learner.py:13
  * `components_ = dictionary`). */
 int klnmf_set_H(klnmf_ctx *ctx, const void *src, int dtype);

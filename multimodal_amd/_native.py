@@ -53,6 +53,8 @@ SIGNATURES = {
     'klnmf_upload_weights': (_c.c_int, [_ctx_p, _c.c_void_p, _c.c_int, _i64, _i64, _i64, _i64, _i64]),
     'klnmf_clear_weights': (_c.c_int, [_ctx_p]),
     'klnmf_upload_presence': (_c.c_int, [_ctx_p, _c.c_void_p, _c.c_int, _i64, _i64, _i64, _c.POINTER(_i64), _c.c_int]),
+    'klnmf_upload_presence_device_rows': (_c.c_int, [_ctx_p, _c.c_void_p, _c.c_int, _i64, _i64, _c.c_void_p, _i64, _i64,
+                                                     _c.POINTER(_c.c_int), _c.POINTER(_i64), _c.c_int]),
     'klnmf_upload_V_device_rows': (_c.c_int, [_ctx_p, _c.c_void_p, _c.c_void_p, _i64, _i64, _i64, _i64, _i64,
                                               _c.c_double]),
     'klnmf_upload_V_device': (_c.c_int, [_ctx_p, _c.c_void_p, _i64, _i64, _i64, _i64,
@@ -425,6 +427,21 @@ class Context(object):
         ld = a.strides[0] // a.itemsize
         cb = (_i64 * len(bounds))(*bounds)
         _check(self._lib.klnmf_upload_presence(self._h, a.ctypes.data, _np_dtype_code(a), a.shape[0], ld, row0, cb, len(bounds) - 1))
+
+    def upload_presence_device_rows(self, dev_ptr, f64, src_rows, ld, row_idx_ptr, rows, src_cols, col_bounds, row0=0):
+        """P[row0 + i, m] = dP[row_idx[i], src_cols[m]] -- 1 where src_cols[m] is -1 -- for i < rows (klnmf_upload_presence_device_rows):
+        `upload_presence` for a mask that lives in device memory, a float32 / float64 matrix of `src_rows` rows `ld` apart at
+        `dev_ptr`.  `row_idx_ptr`: `rows` int64 row indices in device memory (0: rows 0 .. rows - 1), checked on the device
+        before anything is read through them; `src_cols`: one source column per modality; `col_bounds` as in `upload_presence`."""
+        bounds = [int(b) for b in col_bounds]
+        cols = [int(v) for v in src_cols]
+        if len(cols) != len(bounds) - 1:
+            raise ValueError("%d source columns for %d modalities" % (len(cols), len(bounds) - 1))
+        cb = (_i64 * len(bounds))(*bounds)
+        sc = (_c.c_int * max(1, len(cols)))(*cols)
+        _check(self._lib.klnmf_upload_presence_device_rows(self._h, _c.c_void_p(dev_ptr), DT_F64 if f64 else DT_F32, int(src_rows), int(ld),
+                                                           _c.c_void_p(row_idx_ptr) if row_idx_ptr else None, int(rows), int(row0),
+                                                           sc, cb, len(cols)))
 
     def presence(self):
         """Modalities of the current problem's presence mask (klnmf_query KLNMF_Q_PRESENCE); 0 without one."""

@@ -781,6 +781,71 @@ int klnmf_upload_weights(klnmf_ctx *c, const void *src, int dtype, int64_t rows,
     });
 }
 
+// What klnmf_upload_presence and klnmf_upload_presence_device_rows refuse alike, in this order around their own argument checks, and
+// how the first of them on a problem takes the mask's state.
+static void presence_check_supported(klnmf_ctx *c, const std::string &who) {
+    if (c->sparse) fail(KLNMF_ERR_UNSUPP, who + ": CSR problems have no masked kernels (the ratio lives on the stored entries only)");
+    if (c->prec != KLNMF_PREC_F64 && c->prec != KLNMF_PREC_F32)
+        fail(KLNMF_ERR_UNSUPP, who + ": the masked kernels exist in KLNMF_PREC_F64 and KLNMF_PREC_F32 only");
+    if (c->sharded_loop)
+        fail(KLNMF_ERR_UNSUPP, who + ": a loop over row shards is open on this context (klnmf_loop_begin on a communicator, "
+                                     "klnmf_loop_begin_sharded / _agreed) and its exchange carries no W^T.P; klnmf_loop_end first");
+}
+
+// `rows_ok`: the caller's own part of "rows out of range" (the source's leading dimension)
+static void presence_check_args(klnmf_ctx *c, const std::string &who, int64_t rows, int64_t row0, bool rows_ok, const int64_t *col_bounds,
+                                int n_mod) {
+    if (n_mod < 1 || n_mod > KLNMF_MAX_MODALITIES)
+        fail(KLNMF_ERR_ARG, who + ": 1 <= n_mod <= KLNMF_MAX_MODALITIES (" + std::to_string(KLNMF_MAX_MODALITIES) + ")");
+    if (!col_bounds) fail(KLNMF_ERR_ARG, who + ": null column bounds");
+    if (col_bounds[0] != 0 || col_bounds[n_mod] != c->f) fail(KLNMF_ERR_ARG, who + ": the column bounds must run from 0 to f");
+    for (int m = 0; m < n_mod; ++m)
+        if (col_bounds[m] >= col_bounds[m + 1]) fail(KLNMF_ERR_ARG, who + ": the column bounds must increase strictly");
+    if (rows < 0 || row0 < 0 || row0 + rows > c->n || !rows_ok) fail(KLNMF_ERR_ARG, who + ": rows out of range");
+    if (c->weighted()) fail(KLNMF_ERR_ARG, who + ": the problem holds weights (klnmf_upload_weights); klnmf_clear_weights first");
+    if (c->presence() && (n_mod != c->pres_M || !std::equal(col_bounds, col_bounds + n_mod + 1, c->pres_bounds)))
+        fail(KLNMF_ERR_ARG, who + ": the column bounds differ from the ones the problem's first upload fixed");
+}
+
+// The first mask upload of a problem: P filled with 1, S, D, D's slabs, the bounds and the per-column modality bytes (ProblemState).
+// All or nothing; a problem that holds a mask already is left alone.
+static void presence_take(klnmf_ctx *c, const int64_t *col_bounds, int n_mod) {
+    if (c->presence()) return;
+    const size_t es = c->esize();
+    const int64_t M = n_mod;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    void *pm = nullptr;
+    try {
+        const int dch = presence_d_chunks(c->n);
+        pm = c->dalloc((size_t)(c->n * M) * es, false);
+        c->pres_S = c->dalloc((size_t)(M * c->k) * es);
+        c->pres_D = c->dalloc((size_t)(c->k * M) * es);
+        c->pres_Dslab = c->dalloc((size_t)dch * (size_t)(c->k * M) * sizeof(double));
+        c->pres_dbounds = c->dalloc((size_t)(M + 1) * sizeof(int64_t));
+        c->pres_mod = c->dalloc((size_t)c->f);
+        std::vector<unsigned char> mod((size_t)c->f);
+        for (int m = 0; m < n_mod; ++m) std::fill(mod.begin() + col_bounds[m], mod.begin() + col_bounds[m + 1], (unsigned char)m);
+        HIPCHK(hipMemcpyAsync(c->pres_mod, mod.data(), mod.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->pres_dbounds, col_bounds, (size_t)(M + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        const int64_t count = c->n * M;
+        if (c->prec == KLNMF_PREC_F64)
+            hipLaunchKernelGGL((k_fill<double>), dim3(grid_for(count, 256, 8192)), dim3(256), 0, c->stream, (double *)pm, count, 1.0);
+        else
+            hipLaunchKernelGGL((k_fill<float>), dim3(grid_for(count, 256, 8192)), dim3(256), 0, c->stream, (float *)pm, count, 1.0f);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(c->stream));      // (the host images above are read by the copies until here)
+        c->pres_dchunks = dch;
+    } catch (...) {                     // all or nothing: a failed first upload leaves the problem without a mask
+        (void)hipStreamSynchronize(c->stream);
+        c->dfree(c->pres_S); c->dfree(c->pres_D); c->dfree(c->pres_Dslab); c->dfree(c->pres_dbounds); c->dfree(c->pres_mod);
+        c->dfree(pm);
+        throw;
+    }
+    c->Pm = pm;
+    std::copy(col_bounds, col_bounds + n_mod + 1, c->pres_bounds);
+    c->pres_M = n_mod;
+}
+
 // P[row0 + i, m] = src[i, m] for the M = n_mod modalities whose columns are [col_bounds[m], col_bounds[m + 1]) (presence.hip.h).  The
 // first upload of a problem fixes the bounds, builds the per-column modality index and takes P filled with 1, with S, D and D's
 // slabs beside it; klnmf_set_problem* / klnmf_release_problem drop them with the problem (ProblemState).
@@ -788,61 +853,13 @@ int klnmf_upload_presence(klnmf_ctx *c, const void *src, int dtype, int64_t rows
                           const int64_t *col_bounds, int n_mod) {
     return guarded([&] {
         need_problem(c);
-        if (c->sparse) fail(KLNMF_ERR_UNSUPP, "klnmf_upload_presence: CSR problems have no masked kernels (the ratio lives on the stored entries only)");
-        if (c->prec != KLNMF_PREC_F64 && c->prec != KLNMF_PREC_F32)
-            fail(KLNMF_ERR_UNSUPP, "klnmf_upload_presence: the masked kernels exist in KLNMF_PREC_F64 and KLNMF_PREC_F32 only");
-        if (c->sharded_loop)
-            fail(KLNMF_ERR_UNSUPP, "klnmf_upload_presence: a loop over row shards is open on this context (klnmf_loop_begin on a communicator, "
-                                   "klnmf_loop_begin_sharded / _agreed) and its exchange carries no W^T.P; klnmf_loop_end first");
+        const std::string who = "klnmf_upload_presence";
+        presence_check_supported(c, who);
         if (!src && rows > 0) fail(KLNMF_ERR_ARG, "null source");
         if (dtype != KLNMF_DT_F64 && dtype != KLNMF_DT_F32) fail(KLNMF_ERR_ARG, "unknown dtype");
-        if (n_mod < 1 || n_mod > KLNMF_MAX_MODALITIES)
-            fail(KLNMF_ERR_ARG, "klnmf_upload_presence: 1 <= n_mod <= KLNMF_MAX_MODALITIES (" + std::to_string(KLNMF_MAX_MODALITIES) + ")");
-        if (!col_bounds) fail(KLNMF_ERR_ARG, "klnmf_upload_presence: null column bounds");
-        if (col_bounds[0] != 0 || col_bounds[n_mod] != c->f)
-            fail(KLNMF_ERR_ARG, "klnmf_upload_presence: the column bounds must run from 0 to f");
-        for (int m = 0; m < n_mod; ++m)
-            if (col_bounds[m] >= col_bounds[m + 1]) fail(KLNMF_ERR_ARG, "klnmf_upload_presence: the column bounds must increase strictly");
-        if (rows < 0 || row0 < 0 || row0 + rows > c->n || ld < n_mod) fail(KLNMF_ERR_ARG, "klnmf_upload_presence: rows out of range");
-        if (c->weighted())
-            fail(KLNMF_ERR_ARG, "klnmf_upload_presence: the problem holds weights (klnmf_upload_weights); klnmf_clear_weights first");
-        if (c->presence() && (n_mod != c->pres_M || !std::equal(col_bounds, col_bounds + n_mod + 1, c->pres_bounds)))
-            fail(KLNMF_ERR_ARG, "klnmf_upload_presence: the column bounds differ from the ones the problem's first upload fixed");
-        const size_t es = c->esize();
+        presence_check_args(c, who, rows, row0, ld >= n_mod, col_bounds, n_mod);
         const int64_t M = n_mod;
-        if (!c->presence()) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            void *pm = nullptr;
-            try {
-                const int dch = presence_d_chunks(c->n);
-                pm = c->dalloc((size_t)(c->n * M) * es, false);
-                c->pres_S = c->dalloc((size_t)(M * c->k) * es);
-                c->pres_D = c->dalloc((size_t)(c->k * M) * es);
-                c->pres_Dslab = c->dalloc((size_t)dch * (size_t)(c->k * M) * sizeof(double));
-                c->pres_dbounds = c->dalloc((size_t)(M + 1) * sizeof(int64_t));
-                c->pres_mod = c->dalloc((size_t)c->f);
-                std::vector<unsigned char> mod((size_t)c->f);
-                for (int m = 0; m < n_mod; ++m) std::fill(mod.begin() + col_bounds[m], mod.begin() + col_bounds[m + 1], (unsigned char)m);
-                HIPCHK(hipMemcpyAsync(c->pres_mod, mod.data(), mod.size(), hipMemcpyHostToDevice, c->stream));
-                HIPCHK(hipMemcpyAsync(c->pres_dbounds, col_bounds, (size_t)(M + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-                const int64_t count = c->n * M;
-                if (c->prec == KLNMF_PREC_F64)
-                    hipLaunchKernelGGL((k_fill<double>), dim3(grid_for(count, 256, 8192)), dim3(256), 0, c->stream, (double *)pm, count, 1.0);
-                else
-                    hipLaunchKernelGGL((k_fill<float>), dim3(grid_for(count, 256, 8192)), dim3(256), 0, c->stream, (float *)pm, count, 1.0f);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipStreamSynchronize(c->stream));      // (the host images above are read by the copies until here)
-                c->pres_dchunks = dch;
-            } catch (...) {                     // all or nothing: a failed first upload leaves the problem without a mask
-                (void)hipStreamSynchronize(c->stream);
-                c->dfree(c->pres_S); c->dfree(c->pres_D); c->dfree(c->pres_Dslab); c->dfree(c->pres_dbounds); c->dfree(c->pres_mod);
-                c->dfree(pm);
-                throw;
-            }
-            c->Pm = pm;
-            std::copy(col_bounds, col_bounds + n_mod + 1, c->pres_bounds);
-            c->pres_M = n_mod;
-        }
+        presence_take(c, col_bounds, n_mod);
         if (rows == 0) return;
         // the rows through a bounded staging buffer (upload_block's scheme), cast and placed by k_place_V on an n x M matrix
         const size_t ses = dt_size(dtype);
@@ -870,6 +887,56 @@ int klnmf_upload_presence(klnmf_ctx *c, const void *src, int dtype, int64_t rows
             throw;
         }
         (void)hipFree(d);
+    });
+}
+
+// klnmf_upload_presence for a mask in device memory: P[row0 + i, m] = dP[drow_idx[i], src_cols[m]], 1 where src_cols[m] is -1, gathered by
+// k_presence_gather (presence.hip.h).  The row indices are checked on the device first (k_presence_rows_check; the pattern of
+// k_csrg_len): the host reads the flag back, and only a clean flag takes the mask (a first upload) and launches the gather -- a
+// refused call leaves the problem as it was.
+int klnmf_upload_presence_device_rows(klnmf_ctx *c, const void *dP, int dtype, int64_t src_rows, int64_t ld, const int64_t *drow_idx,
+                                      int64_t rows, int64_t row0, const int *src_cols, const int64_t *col_bounds, int n_mod) {
+    return guarded([&] {
+        need_problem(c);
+        const std::string who = "klnmf_upload_presence_device_rows";
+        presence_check_supported(c, who);
+        if (!dP && rows > 0) fail(KLNMF_ERR_ARG, "null source");
+        if (dtype != KLNMF_DT_F64 && dtype != KLNMF_DT_F32) fail(KLNMF_ERR_ARG, "unknown dtype");
+        presence_check_args(c, who, rows, row0, ld >= 0 && src_rows >= 0 && (drow_idx || rows <= src_rows), col_bounds, n_mod);
+        if (!src_cols) fail(KLNMF_ERR_ARG, who + ": null source columns");
+        PresenceCols cols{};
+        for (int m = 0; m < n_mod; ++m) {
+            if (src_cols[m] < -1 || src_cols[m] >= ld) fail(KLNMF_ERR_ARG, who + ": a source column outside [-1, ld)");
+            cols.col[m] = src_cols[m];
+        }
+        if (rows > 0 && drow_idx) {
+            void *flag = c->dalloc(sizeof(int64_t));      // (zero-filled)
+            int64_t bad = 0;
+            try {
+                hipLaunchKernelGGL(k_presence_rows_check, dim3(grid_for(rows, 256, kPresGatherMaxBlocks)), dim3(256), 0, c->stream, drow_idx,
+                                   rows, src_rows, (int64_t *)flag);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpyAsync(&bad, flag, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipStreamSynchronize(c->stream));
+            } catch (...) {
+                (void)hipStreamSynchronize(c->stream);
+                c->dfree(flag);
+                throw;
+            }
+            c->dfree(flag);
+            if (bad) fail(KLNMF_ERR_ARG, who + ": a row index outside [0, src_rows)");
+        }
+        presence_take(c, col_bounds, n_mod);
+        if (rows == 0) return;
+        // every index is a source row, every column one of its ld, and row0 + rows <= n: the gather reads and writes in range
+        const int grid = grid_for(rows, 256, kPresGatherMaxBlocks);
+#define KL_GATHER_P(T, S) hipLaunchKernelGGL((k_presence_gather<T, S>), dim3(grid), dim3(256), 0, c->stream, (T *)c->Pm, n_mod, (const S *)dP, ld, \
+                                             drow_idx, rows, row0, cols)
+        if (c->prec == KLNMF_PREC_F64) { if (dtype == KLNMF_DT_F64) KL_GATHER_P(double, double); else KL_GATHER_P(double, float); }
+        else { if (dtype == KLNMF_DT_F64) KL_GATHER_P(float, double); else KL_GATHER_P(float, float); }
+#undef KL_GATHER_P
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(c->stream));      // (dP and drow_idx are the caller's: free to go from here)
     });
 }
 

@@ -321,6 +321,7 @@ int klnmf_group_run(klnmf_group *g, int64_t n_total, int64_t max_iter, int fit, 
             int64_t nd = 0;
             int sp = 0;
             fetch_results(c, r == 0 ? errors_out : nullptr, &nd, &sp);
+            c->sharded_loop = false;               // (as klnmf_loop_end: the loop klnmf_loop_begin_agreed opened has ended)
             if (r == 0) { nd0 = nd; st0 = sp; }
             else if (nd != nd0 || sp != st0)
                 fail(KLNMF_ERR_REPLICA, "klnmf_group_run: shard " + std::to_string(r) + " ran " + std::to_string(nd) +

@@ -461,6 +461,7 @@ struct klnmf_ctx : ContextState, ProblemState, LoopState, LoopRecord {
             v->clear();
         }
         static_cast<ProblemState &>(*this) = ProblemState();
+        sharded_loop = false;      // (a loop that was left open went with its problem)
     }
 };
 

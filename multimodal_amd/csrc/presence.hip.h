@@ -13,6 +13,8 @@
 //   k_update_H / k_update_H_part under FacPresH   the H rule: factor = D > 0 ? num / D : 1
 // The ratio epilogue and the rules are the one family of exact.hip.h under the policies PresenceWeight, FacPresW and FacPresH; this
 // file holds them and what only a masked problem runs: k_presence_S, k_presence_D_part, k_presence_D_sum.
+// The mask itself comes from the host (klnmf_upload_presence: k_place_V on the n x M matrix) or from a mask resident in device
+// memory, gathered by row index and source column (klnmf_upload_presence_device_rows: k_presence_rows_check, k_presence_gather).
 // S and D are accumulated in double in a fixed order and rounded once to T (as the H rule's row sums are): two runs give the
 // same bits.  The routes (row chunks, feature chunks, segments, rule from the slabs) are the unweighted plan's.
 #pragma once
@@ -23,6 +25,7 @@ namespace klnmf {
 constexpr int kMaxMod = 16;          // KLNMF_MAX_MODALITIES (klnmf.h)
 constexpr int kPresDRows = 128;      // rows per chunk of D's reduction, at least (presence_d_chunks)
 constexpr int kPresDMaxChunks = 64;
+constexpr int kPresGatherMaxBlocks = 512;      // the gather's grid: 256 rows per block, more rows than 131 072 go round its loop
 
 // row chunks of D = W^T.P: a function of n alone (the bits of D do not depend on the device's size)
 inline int presence_d_chunks(int64_t n) {
@@ -122,6 +125,38 @@ __global__ void k_presence_D_sum(const double *slab, int nslab, int64_t count, T
         double s = 0;
         for (int z = 0; z < nslab; ++z) s += slab[z * count + e];
         D[e] = (T)s;
+    }
+}
+
+// The source column of every modality of one gather, passed by value (read through the kernel-argument segment: uniform loads, no
+// table in device memory); -1: the modality has no column, its weight is 1
+struct PresenceCols {
+    int col[kMaxMod];
+};
+
+// bad[0] = 1 if a row index lies outside [0, src_rows): reads idx alone, nothing through it.  The gather is launched only after the
+// host has read bad[0] == 0.
+KL_GLOBAL __launch_bounds__(256) void k_presence_rows_check(const int64_t *idx, int64_t rows, int64_t src_rows, int64_t *bad) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows; r += stride) {
+        const int64_t i = idx[r];
+        if (i < 0 || i >= src_rows) bad[0] = 1;
+    }
+}
+
+// P[row0 + r, m] = src[idx[r], cols[m]] (idx null: src[r, cols[m]]), 1 where cols[m] < 0, cast to T as k_place_V casts an upload.  One
+// thread per output row: one index load, M gathered loads, M contiguous stores (consecutive threads write consecutive rows of P).
+// In range by the caller's checks: every idx[r] in [0, src_rows), every cols[m] in [-1, ld), row0 + rows <= n.
+template <typename T, typename S>
+__global__ __launch_bounds__(256) void k_presence_gather(T *P, int nmod, const S *src, int64_t ld, const int64_t *idx, int64_t rows,
+                                                         int64_t row0, PresenceCols cols) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows; r += stride) {
+        const S *srow = src + (idx ? idx[r] : r) * ld;
+        T *prow = P + (row0 + r) * nmod;
+#pragma unroll
+        for (int m = 0; m < kMaxMod; ++m)
+            if (m < nmod) prow[m] = cols.col[m] >= 0 ? (T)(double)srow[cols.col[m]] : T(1);
     }
 }
 

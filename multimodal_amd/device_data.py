@@ -11,12 +11,16 @@ The reference's datasets are sparse (db/objects.py:79-81 builds CSR histograms) 
 an experiment on them runs the reference's sparse branch (nmf.py:52-70, 301-308, 331-334).  `DeviceDataset(keep_sparse=True)`
 does the same on the device: sparse modalities stay CSR in device memory, and a run's stacked CSR of the selected rows is
 gathered there (`klnmf_upload_csr_device_rows`, csrc/csrgather.hip.h) -- nothing of nnz length is sliced on the host.
+
+`DeviceDataset(presence=[...])` keeps a row x modality presence mask (a modality absent from some samples) resident beside the
+modalities: a call whose modalities carry a mask column gathers its rows of the mask on the device
+(`klnmf_upload_presence_device_rows`) and runs the masked loop of csrc/presence.hip.h -- the reference has no counterpart.
 """
 import numpy as np
 import scipy.sparse as sp
 
 from . import _native
-from .lib.nmf import KLdivNMF, check_non_negative, _default_precision, resolve_precision, _csr_of, _note_once
+from .lib.nmf import KLdivNMF, check_non_negative, check_weights, _default_precision, resolve_precision, _csr_of, _note_once
 from .lib.sklearn_utils import atleast2d_or_csr
 
 
@@ -43,6 +47,34 @@ def csr_rows_plan(indptrs, rows, coefs, minima):
                 if least * type(least)(float(c)) == 0:
                     use_device = False
     return nnz, use_device
+
+
+def check_presence(presence, n_samples, n_modalities):
+    """`presence` of `DeviceDataset` as it is kept: (P, masked) -- P the float64 [n_samples, n_modalities] mask, the column of a
+    modality without an array all 1, and masked[m] whether modality m came with an array; (None, [False ...]) where no entry is
+    an array (None and scalars: weights of 1, as `nmf.check_weights` reads them).  ValueError, before anything is uploaded: not
+    one entry per modality, an array that is not of shape (n_samples,) or (n_samples, 1), negative or non-finite values
+    (`nmf.check_weights`), more than `_native.MAX_MODALITIES` modalities under a mask."""
+    none = [False] * n_modalities
+    if presence is None:
+        return None, none
+    presence = list(presence)
+    if len(presence) != n_modalities:
+        raise ValueError("presence: one entry per modality expected (%d modalities, %d entries)" % (n_modalities, len(presence)))
+    P, masked = np.ones((n_samples, n_modalities), dtype=np.float64), list(none)
+    for m, p in enumerate(presence):
+        if p is None or np.ndim(p) == 0:
+            continue
+        a = np.asarray(p)
+        if a.shape not in ((n_samples,), (n_samples, 1)):
+            raise ValueError("presence[%d] of shape %s: (%d,) or (%d, 1) expected" % (m, a.shape, n_samples, n_samples))
+        P[:, m] = check_weights(a.reshape(n_samples, 1), (n_samples, 1))[:, 0]
+        masked[m] = True
+    if not any(masked):
+        return None, none
+    if n_modalities > _native.MAX_MODALITIES:
+        raise ValueError("presence: a mask holds at most %d modalities, the dataset has %d" % (_native.MAX_MODALITIES, n_modalities))
+    return P, masked
 
 
 class _DeviceCsr(object):
@@ -82,9 +114,20 @@ class DeviceDataset(object):
     subsets of dense modalities).  A fit or transform on modalities of which at least one is sparse runs the reference's sparse
     branch (the rule of `KLdivNMF._sparse_route` for host blocks) on a CSR problem gathered on the device
     (klnmf_upload_csr_device_rows); a subset of dense modalities runs the dense path as ever.  The default keeps every modality
-    dense, as before."""
+    dense, as before.
 
-    def __init__(self, data_matrices, device=None, keep_sparse=False):
+    presence: None (no mask: every call is the unmasked one, as before), or a list with one entry per modality -- None, a scalar
+    (both: that modality is present everywhere, no mask) or an array of shape (n_samples,) / (n_samples, 1) of weights >= 0: the
+    weight of that modality in each sample, 0 where it is absent (`check_presence`: ValueError on the host).  The mask stays on
+    the device as one float64 [n_samples, M] matrix.  A call (`train`, `reconstruct_internal_multi`, `DeviceEvaluation.internal`)
+    whose modalities include one with an array gathers its rows of the mask on the device (klnmf_upload_presence_device_rows) and
+    minimises the masked cost (csrc/presence.hip.h), in the arithmetic `nmf.weighted_precision` names, on the first device;
+    `last_weights_route` then reads 'presence', on the dataset and on the model the call used.  A call on modalities without an
+    array is the unmasked call, bit for bit (`last_weights_route` None).  A row from which every selected modality is absent keeps
+    its W0 (a factor of 1 where the denominator is 0).  Scoring and the choice of rows stay the caller's.  A masked call that
+    selects a modality kept as CSR raises ValueError: CSR problems have no masked kernels."""
+
+    def __init__(self, data_matrices, device=None, keep_sparse=False, presence=None):
         import torch
         self.torch = torch
         self.device = torch.device('cuda', torch.cuda.current_device() if device is None else device)
@@ -100,6 +143,10 @@ class DeviceDataset(object):
         self.keep_sparse = self.keep_sparse_asked and any(sp.issparse(m) for m in mats)
         self.sparse = [self.keep_sparse and sp.issparse(m) for m in mats]
         self.dims = [int(m.shape[1]) for m in mats]
+        self.n_samples = int(mats[0].shape[0])
+        assert all(m.shape[0] == self.n_samples for m in mats)
+        self.presence_host, self.masked = check_presence(presence, self.n_samples, len(mats))      # (before anything is uploaded)
+        self.last_weights_route = None      # set by every call: 'presence' where it ran the masked loop
         self.csr = [_DeviceCsr(m, self._to_device) for m in mats] if self.keep_sparse else [None] * len(mats)
         for m, kept, c in zip(mats, self.sparse, self.csr):
             if kept:             # CSR only: no dense copy on either side
@@ -110,22 +157,52 @@ class DeviceDataset(object):
             if hasattr(m, 'toarray'):
                 m = m.toarray()
             self.host.append(np.asarray(m))
-            t = torch.from_numpy(np.ascontiguousarray(m, dtype=np.float32)).to(self.device)
+            t = self._to_device(np.ascontiguousarray(m, dtype=np.float32))
             self.blocks.append(t)
             self.maxima.append(float(t.max().item()) if t.numel() else 0.0)
-        self.n_samples = int(mats[0].shape[0])
-        assert all(m.shape[0] == self.n_samples for m in mats)
         self._blocks64 = {}
+        self.presence = None if self.presence_host is None else self._to_device(self.presence_host)      # float64 [n_samples, M]
 
     def _to_device(self, array):
-        """A host array of the CSR path as a tensor on `device` (the one place that path touches torch: tests replace it)."""
+        """A host array as a tensor on `device` (the one place the uploads touch torch: tests replace it)."""
         return self.torch.from_numpy(array).to(self.device)
 
+    def _synchronize(self):
+        self.torch.cuda.synchronize(self.device)
+
     def resident_bytes(self):
-        """Device bytes the modalities take as stored now (dense fp32 blocks, fp64 copies made so far, CSR arrays)."""
+        """Device bytes the modalities take as stored now (dense fp32 blocks, fp64 copies made so far, CSR arrays, the mask)."""
         total = sum(b.numel() * b.element_size() for b in self.blocks if b is not None)
         total += sum(b.numel() * b.element_size() for b in self._blocks64.values())
+        total += 0 if self.presence is None else self.presence.numel() * self.presence.element_size()
         return total + sum(c.nbytes() for c in self.csr if c is not None)
+
+    def same_presence(self, presence):
+        """`presence` (as the constructor takes it) is the mask this dataset was built with."""
+        P, masked = check_presence(presence, self.n_samples, len(self.dims))
+        if P is None or self.presence_host is None:
+            return P is None and self.presence_host is None
+        return masked == self.masked and np.array_equal(P, self.presence_host)
+
+    def presence_route(self, which):
+        """The modalities `which` run the masked loop: at least one of them came with a presence array.  ValueError where one
+        of them is kept as CSR as well (the refusal of klnmf_upload_presence on a CSR problem, said on the host)."""
+        if not any(self.masked[w] for w in which):
+            return False
+        if self.sparse_route(which):
+            raise ValueError("a presence mask on modalities of which %s kept as CSR (keep_sparse=True): CSR problems have no masked "
+                             "kernels; select dense modalities, or build the dataset without keep_sparse"
+                             % ', '.join('%d is' % w for w in which if self.sparse[w]))
+        return True
+
+    def upload_presence(self, ctx, which, idx_ptr, n):
+        """The rows of the mask for the modalities `which` into the problem of `ctx`: gathered on the device by the row indices
+        at `idx_ptr` (`n` int64 in device memory), column `w` of the resident mask for a masked modality w, 1 for the others."""
+        bounds = [0]
+        for w in which:
+            bounds.append(bounds[-1] + self.dims[w])
+        ctx.upload_presence_device_rows(self.presence.data_ptr(), True, self.n_samples, self.presence.stride(0), idx_ptr, n,
+                                        [w if self.masked[w] else -1 for w in which], bounds)
 
     def sparse_route(self, which):
         """The modalities `which` run the sparse branch: at least one of them is kept as CSR (`KLdivNMF._sparse_route`)."""
@@ -185,13 +262,15 @@ class DeviceDataset(object):
         if self.sparse[which]:
             raise ValueError("modality %d is kept as CSR (keep_sparse=True): it has no dense device copy" % which)
         if which not in self._blocks64:
-            self._blocks64[which] = self.torch.from_numpy(np.ascontiguousarray(self.host[which], dtype=np.float64)).to(self.device)
+            self._blocks64[which] = self._to_device(np.ascontiguousarray(self.host[which], dtype=np.float64))
         return self._blocks64[which]
 
-    def _uploader(self, which, rows, coefs):
-        torch = self.torch
-        idx = torch.as_tensor(np.asarray(rows, dtype=np.int64), device=self.device)
-        assert idx.numel() == 0 or (int(idx.min()) >= 0 and int(idx.max()) < self.n_samples)
+    def _uploader(self, which, rows, coefs, masked=False):
+        """(upload, n): `upload(ctx)` places the rows of the dense modalities `which` in the problem of `ctx`; masked: and their
+        rows of the presence mask behind them (`upload_presence`)."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        assert rows.size == 0 or (int(rows.min()) >= 0 and int(rows.max()) < self.n_samples)
+        idx = self._to_device(rows)
 
         def upload(ctx):
             # an upper bound of the stacked maximum fixes the 16-bit storage factor (any bound is valid)
@@ -202,8 +281,18 @@ class DeviceDataset(object):
                 ctx.upload_V_device_rows_dt(b.data_ptr(), f64, idx.data_ptr(), idx.numel(), b.shape[1], b.stride(0),
                                             row0=0, col0=col, scale=c)
                 col += b.shape[1]
-            torch.cuda.synchronize(self.device)      # the context runs on its own stream; idx must outlive the kernel
+            if masked:
+                self.upload_presence(ctx, which, idx.data_ptr(), idx.numel())
+            self._synchronize()      # the context runs on its own stream; idx must outlive the kernel
         return upload, idx.numel()
+
+    def _fit_dense(self, nmf, which, rows, coefs, n_features, _fit, return_errors=False):
+        """The loop on the rows of dense modalities: the masked one where `presence_route` says so."""
+        masked = self.presence_route(which)
+        upload, n = self._uploader(which, rows, coefs, masked)
+        out = nmf._fit_uploaded(n, n_features, upload, lambda H: np.float64, _fit=_fit, return_errors=return_errors, weighted=masked)
+        self.last_weights_route = nmf.last_weights_route = 'presence' if masked else None
+        return out
 
     # ---- what experiment.py:_perform_one_run does with the sliced copies ----
     def rows_of(self, which, rows):
@@ -214,7 +303,9 @@ class DeviceDataset(object):
 
     def train(self, learner, rows, iterations, init_dictionary=None):
         """learner.train([x[rows] for x in data], iterations) (learner.py:31-41) without the host slices.
-        `init_dictionary`: the initial dictionary instead of a draw from the global numpy stream (nmf.py:149-155)."""
+        `init_dictionary`: the initial dictionary instead of a draw from the global numpy stream (nmf.py:149-155).
+        With a presence mask on the dataset: learner.train(..., weights=[P_m[rows] ...]), `learner.nmf_train.last_weights_route`
+        'presence'.  A row in which every modality is absent keeps its W0 and gives the dictionary nothing."""
         if learner.sparseness is not None:
             raise NotImplemented
         which = list(range(len(self.blocks)))
@@ -222,27 +313,30 @@ class DeviceDataset(object):
         nmf = KLdivNMF(n_components=learner.k, max_iter=iterations, tol=0)
         if init_dictionary is not None:
             nmf._init_dictionary = np.asarray(init_dictionary)
-        if self.sparse_route(which):
+        if not self.presence_route(which) and self.sparse_route(which):
+            self.last_weights_route = None
             self._fit_sparse(nmf, which, rows, list(learner.coef), True)
         else:
-            upload, n = self._uploader(which, rows, list(learner.coef))
-            nmf._fit_uploaded(n, sum(learner.dim), upload, lambda H: np.float64, _fit=True)
+            self._fit_dense(nmf, which, rows, list(learner.coef), sum(learner.dim), True)
         learner.nmf_train = nmf
         learner.dico = nmf.components_
         return learner
 
     def reconstruct_internal_multi(self, learner, orig_mods, rows, iterations):
-        """learner.reconstruct_internal_multi(orig_mods, [x[rows] ...], iterations) (learner.py:71-78)."""
+        """learner.reconstruct_internal_multi(orig_mods, [x[rows] ...], iterations) (learner.py:71-78).  Where one of `orig_mods`
+        has a presence array: ... with weights=[P_m[rows] ...], the masked transform -- over all modalities it uses in every row
+        whatever that row has; a row from which every selected modality is absent keeps its W0 = x . dico^T (factor 1 where the
+        denominator is 0).  `self.last_weights_route` names the route."""
         which = [learner.get_index(m) for m in orig_mods]
         coefs = [learner.coef[w] for w in which]
         dico = learner.get_stacked_dicos(orig_mods)
         nmf = KLdivNMF(n_components=dico.shape[0], max_iter=iterations, tol=0)
         nmf.components_ = dico
         nmf._init_dictionary = dico
-        if self.sparse_route(which):
+        if not self.presence_route(which) and self.sparse_route(which):
+            self.last_weights_route = None
             return self._fit_sparse(nmf, which, rows, coefs, False)
-        upload, n = self._uploader(which, rows, coefs)
-        return nmf._fit_uploaded(n, dico.shape[1], upload, lambda H: np.float64, _fit=False)
+        return self._fit_dense(nmf, which, rows, coefs, dico.shape[1], False)
 
     def reconstruct_internal(self, learner, orig_mod, rows, iterations):
         return self.reconstruct_internal_multi(learner, [orig_mod], rows, iterations)
@@ -267,6 +361,7 @@ class DeviceEvaluation(object):
         self.dico = torch.from_numpy(np.ascontiguousarray(learner.get_dico(), dtype=np.float64)).to(self.dev)
         self.k, self.F = self.dico.shape
         self.offsets = [sum(learner.dim[:i]) for i in range(len(learner.dim))]
+        self.last_weights_route = None      # set by every `internal`
 
     def _rows(self, rows):
         idx = self.torch.as_tensor(np.asarray(rows, dtype=np.int64), device=self.dev)
@@ -274,18 +369,25 @@ class DeviceEvaluation(object):
         return idx
 
     def internal(self, mods, rows):
-        """learner.reconstruct_internal_multi(mods, [x[rows] ...], iter_test) -> device tensor [len(rows), k]."""
+        """learner.reconstruct_internal_multi(mods, [x[rows] ...], iter_test) -> device tensor [len(rows), k].  Where one of
+        `mods` has a presence array on the dataset, the masked transform (`DeviceDataset.reconstruct_internal_multi`):
+        `self.last_weights_route` reads 'presence', None otherwise."""
         torch, lr = self.torch, self.learner
         which = [lr.get_index(m) for m in mods]
         idx = self._rows(rows)
         n, f = int(idx.numel()), sum(lr.dim[w] for w in which)
         out = torch.empty((n, self.k), dtype=torch.float64, device=self.dev)
         model = KLdivNMF(n_components=self.k, max_iter=self.iter_test, tol=0)
+        masked = self.ds.presence_route(which)
+        self.last_weights_route = model.last_weights_route = 'presence' if masked else None
         if self.ds.sparse_route(which):
             return self._internal_sparse(model, mods, which, rows, out)
+        if masked:
+            model._note_weighted_on_one_device()
         # (the shape decides the arithmetic exactly as the host path's _fit_uploaded does: 'auto' by size, k beyond the MFMA
         # kernels' range on the fp32 kernels)
-        with model._context(shape=(n, f, self.k)) as ctx:
+        # (a masked transform: f64 or f32 as `weighted_precision` names them, first device -- `_fit_uploaded`'s choice)
+        with model._context(shape=(n, f, self.k), weighted=masked) as ctx:
             ctx.set_problem(n, f, self.k, self.iter_test)
             ctx.set_v_max(max([lr.coef[w] * self.ds.maxima[w] for w in which] + [0.0]))
             col = 0
@@ -294,6 +396,8 @@ class DeviceEvaluation(object):
                 ctx.upload_V_device_rows_dt(b.data_ptr(), f64, idx.data_ptr(), n, b.shape[1], b.stride(0), row0=0, col0=col,
                                             scale=lr.coef[w])
                 col += b.shape[1]
+            if masked:
+                self.ds.upload_presence(ctx, which, idx.data_ptr(), n)
             self._set_dictionary(ctx, which)
             ctx.init_W()                                   # W0 = X . H^T with the dictionary itself (nmf.py:156, 283)
             ctx.run(self.iter_test, False, 0.0)

@@ -156,18 +156,25 @@ def evaluate_internal_on_device(dataset, learner, rows_test, rows_ex, labels_tes
 
 
 def perform_one_run(dataset, modalities, coefs, k, iter_train, iter_test, rows_train, rows_test, rows_ex,
-                    labels_test, labels_ex, init_dictionary=None, kind=None, on_device=True, keep_sparse=None):
+                    labels_test, labels_ex, init_dictionary=None, kind=None, on_device=True, keep_sparse=None, presence=None):
     """experiment.py:158-172 on a DeviceDataset: returns (learner, results) with results['dictionary'] as stored there.
     dataset: a `DeviceDataset`, or the modalities' matrices -- uploaded here as DeviceDataset(dataset, keep_sparse=keep_sparse):
     with keep_sparse scipy-sparse modalities stay CSR on the device and the run takes the reference's sparse branch.
     on_device: the evaluation keeps every intermediate on the GPU (default) or goes through host arrays.  kind: 'two' = TwoModalitiesExperiment._evaluate (every comparison space), 'internal' = ThreeModalitiesExperiment's
     (internal space, single and paired modalities); default by the number of modalities, as the reference's scripts pick
-    the class (samples/two_modalities.py, samples/three_modalities.py)."""
+    the class (samples/two_modalities.py, samples/three_modalities.py).
+    presence: a row x modality presence mask for the dataset created here (`DeviceDataset(presence=...)`: one entry per modality,
+    None or the weights of that modality in every sample, 0 where it is absent); the training and every transform of the
+    evaluation that selects a masked modality then run the masked loop on the rows' own part of the mask.  A row from which
+    every selected modality is absent keeps its W0; which rows are scored stays the caller's choice.  With a `DeviceDataset`,
+    `presence` must be the mask it was built with (ValueError otherwise)."""
     from .device_data import DeviceDataset
     if not isinstance(dataset, DeviceDataset):
-        dataset = DeviceDataset(dataset, keep_sparse=bool(keep_sparse))
+        dataset = DeviceDataset(dataset, keep_sparse=bool(keep_sparse), presence=presence)
     elif keep_sparse is not None and bool(keep_sparse) != dataset.keep_sparse_asked:
         raise ValueError("keep_sparse=%r, but the dataset was uploaded with keep_sparse=%r" % (keep_sparse, dataset.keep_sparse_asked))
+    elif presence is not None and not dataset.same_presence(presence):
+        raise ValueError("presence= differs from the mask the dataset was uploaded with")
     learner = MultimodalLearner(list(modalities), list(dataset.dims), list(coefs), k)
     dataset.train(learner, rows_train, iter_train, init_dictionary=init_dictionary)
     results = {'train': list(rows_train), 'test': list(rows_test), 'dictionary': learner.get_dico()}
@@ -202,7 +209,7 @@ def _one_sweep_job(dataset, modalities, coefs, labels, examples, k, run, iter_tr
 def _sweep_worker(job):
     """One process per GPU: uploads the modalities once, runs its share of the (k, run) grid, returns the scores."""
     (device, rank, world, data, modalities, coefs, labels, examples, ks, n_runs, iter_train, iter_test, test_ratio, seed, kind,
-     precision, keep_sparse) = job
+     precision, keep_sparse, presence) = job
     import os
     import torch
     saved = {name: os.environ.get(name) for name in ('KLNMF_PRECISION', 'KLNMF_DEVICE', 'KLNMF_DEVICES')}
@@ -213,7 +220,7 @@ def _sweep_worker(job):
         os.environ.pop('KLNMF_DEVICES', None)      # (a sweep is replica-parallel: every learner of this worker on its one device)
         torch.cuda.set_device(device)
         from .device_data import DeviceDataset
-        ds = DeviceDataset(data, device=device, keep_sparse=keep_sparse)
+        ds = DeviceDataset(data, device=device, keep_sparse=keep_sparse, presence=presence)
         out = []
         for k, run in sweep_assignment(ks, n_runs, rank, world):
             out.append((k, run, _one_sweep_job(ds, modalities, coefs, labels, examples, k, run, iter_train, iter_test,
@@ -228,7 +235,7 @@ def _sweep_worker(job):
 
 
 def run_sweep(data_matrices, labels, modalities, ks, n_runs, iter_train=50, iter_test=50, coefs=None, examples=None,
-              test_ratio=.1, seed=0, devices=None, precision=None, kind=None, keep_sparse=False):
+              test_ratio=.1, seed=0, devices=None, precision=None, kind=None, keep_sparse=False, presence=None):
     """The k sweep of the reference's launcher (samples/launcher.py:68-99, 122-126: Ks x N_RUN independent experiments,
     one OS process each) on the GPUs of this node: ONE process per device, each with the modalities resident on its GPU,
     executing `sweep_assignment`'s share of the (k, run) grid -- replica parallelism, no communication.  Returns
@@ -239,13 +246,20 @@ def run_sweep(data_matrices, labels, modalities, ks, n_runs, iter_train=50, iter
     examples: the row of the example of each label (default: the first sample of every label, evaluation happens on the
     rest); coefs: per-modality coefficients (default 1 / mean row sum, experiment.py:70-72); devices: GPU ordinals
     (default: all visible; the same ordinal may be listed more than once); keep_sparse: scipy-sparse modalities stay CSR on every
-    device and the runs take the reference's sparse branch (`DeviceDataset`; default: densified, as before)."""
+    device and the runs take the reference's sparse branch (`DeviceDataset`; default: densified, as before); presence: a row x
+    modality presence mask kept on every device beside the modalities (`DeviceDataset(presence=...)`, checked here before any
+    process starts): the runs' fits and transforms on masked modalities minimise the masked cost.  The default coefficients
+    stay 1 / the mean row sum over all samples, absent ones included."""
     import torch
     if keep_sparse:
         data = [m.tocsr() if hasattr(m, 'tocsr') else np.asarray(m) for m in data_matrices]
     else:
         data = [np.asarray(m.toarray() if hasattr(m, 'toarray') else m) for m in data_matrices]
     labels = [int(v) for v in labels]
+    if presence is not None:
+        from .device_data import check_presence
+        check_presence(presence, data[0].shape[0], len(data))
+        presence = [None if (p is None or np.ndim(p) == 0) else np.asarray(p) for p in presence]
     if coefs is None:
         coefs = [float(1. / np.average(x.sum(axis=1))) for x in data]
     if examples is None:
@@ -254,7 +268,7 @@ def run_sweep(data_matrices, labels, modalities, ks, n_runs, iter_train=50, iter
         devices = list(range(max(1, torch.cuda.device_count())))
     world = len(devices)
     jobs = [(dev, r, world, data, list(modalities), list(coefs), labels, list(examples), list(ks), int(n_runs), iter_train,
-             iter_test, test_ratio, seed, kind, precision, bool(keep_sparse)) for r, dev in enumerate(devices)]
+             iter_test, test_ratio, seed, kind, precision, bool(keep_sparse), presence) for r, dev in enumerate(devices)]
     if world == 1:
         parts = [_sweep_worker(jobs[0])]
     else:

@@ -446,6 +446,12 @@ class KLdivNMF(object):
         self.last_weights_route = route if weights is not None else None
         return out
 
+    def _note_weighted_on_one_device(self):
+        """(the group's exchange carries the H numerator alone: a weighted fit stays in one context)"""
+        if len(self.devices) > 1:
+            _note_once(('weights-group',), "KLdivNMF: a weighted fit runs on one device (%d), not over the row shards of devices %s\n"
+                       % (self.device, list(self.devices)))
+
     def _fit_uploaded(self, n_samples, n_features, upload, out_dtype_of, _fit=True, return_errors=False,
                       sparse_X=None, host_blocks=None, weighted=False, sparse_nnz=None):
         """The loop of nmf.py:159-230 on a matrix that `upload(ctx)` places in the context: host blocks
@@ -463,9 +469,7 @@ class KLdivNMF(object):
         out_dtype = out_dtype_of(H_init)
 
         if len(self.devices) > 1 and weighted:
-            # (the group's exchange carries the H numerator alone: a weighted fit stays in one context)
-            _note_once(('weights-group',), "KLdivNMF: a weighted fit runs on one device (%d), not over the row shards of devices %s\n"
-                       % (self.device, list(self.devices)))
+            self._note_weighted_on_one_device()
         elif len(self.devices) > 1:
             if sparse_X is not None:
                 X = sp.csr_matrix(sparse_X, copy=True)      # (what set_problem_sparse uploads: no explicit zeros, sorted rows)
