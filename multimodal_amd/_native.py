@@ -142,6 +142,27 @@ SIGNATURES = {
     'klnmf_selftest': (_c.c_int, [_c.c_int, _c.POINTER(_c.c_int)]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/klnmf_batch.h (batches: B problems of one shape in one launch
+# sequence), which the same library exports
+BATCH_SIGNATURES = {
+    'klnmf_batch_create': (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int, _c.c_int, _c.c_int]),
+    'klnmf_batch_destroy': (_c.c_int, [_c.c_void_p]),
+    'klnmf_batch_set_problem': (_c.c_int, [_c.c_void_p, _i64, _i64, _i64, _i64]),
+    'klnmf_batch_upload_V': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _i64, _i64, _i64, _i64, _i64, _c.c_double]),
+    'klnmf_batch_upload_V_device_rows_dt': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _i64, _i64, _i64,
+                                                       _i64, _i64, _c.c_double]),
+    'klnmf_batch_set_H': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int]),
+    'klnmf_batch_set_H_device': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _i64, _i64, _i64, _c.c_int]),
+    'klnmf_batch_set_W': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int]),
+    'klnmf_batch_init_W': (_c.c_int, [_c.c_void_p]),
+    'klnmf_batch_run': (_c.c_int, [_c.c_void_p, _i64, _c.c_int, _c.c_double]),
+    'klnmf_batch_result': (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_i64), _c.POINTER(_c.c_int)]),
+    'klnmf_batch_get_W': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int]),
+    'klnmf_batch_get_H': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int]),
+    'klnmf_batch_get_W_device': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _i64]),
+    'klnmf_batch_query': (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_i64)]),
+}
+
 _lib = None
 
 
@@ -165,7 +186,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()):
         fn = getattr(lib, name)     # AttributeError if a symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -274,6 +295,8 @@ Q_SP_COL_BLOCKS, Q_SP_ROW_BLOCKS = 14, 15
 Q_EX_ROW_CHUNKS, Q_EX_W_CHUNKS, Q_EX_H_SEGMENTS, Q_EX_H_FROM_SLABS = 16, 17, 18, 19
 Q_WEIGHTED = 20
 Q_PRESENCE = 21
+Q_BATCH_COUNT = 22
+BATCH_MAX = 256
 MAX_MODALITIES = 16
 QF_SUM_V, QF_NNZ_V, QF_MON_STAT, QF_MON_THRESHOLD = 0, 1, 2, 3
 QF_KL_OVER_SUM_V = 9
@@ -867,3 +890,119 @@ class Group(object):
 
     def __exit__(self, *a):
         self.close()
+
+
+class Batch(object):
+    """klnmf_batch_*: `count` dense, unweighted problems of one shape (n, f, k) in 'f64' / 'f32' on one device that run the
+    multiplicative-update loop together, every stage of an iteration one launch for all of them.  Each problem `p` keeps its
+    own V, W, H, loss record and stop state; its results are bit for bit those of the same problem alone in a `Context` whose
+    chunk counts equal the batch's (`exact_regime()`).  The methods mirror `Context`'s with the problem index in front."""
+
+    def __init__(self, precision, count, device=0):
+        self._lib = load()
+        self._h = _c.c_void_p()
+        if isinstance(precision, str):
+            precision = PRECISIONS[precision]
+        self.precision = precision
+        self.count = int(count)
+        self.device = int(device)
+        self.n = self.f = self.k = 0
+        self.cap = 0
+        _check(self._lib.klnmf_batch_create(ctypes.byref(self._h), int(device), int(precision), int(count)))
+        self.precision_name = {PREC_F64: 'f64', PREC_F32: 'f32'}[precision]
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h.value:
+            self._lib.klnmf_batch_destroy(self._h)
+            self._h = _c.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_problem(self, n, f, k, max_iter_capacity):
+        _check(self._lib.klnmf_batch_set_problem(self._h, int(n), int(f), int(k), max(1, int(max_iter_capacity))))
+        self.n, self.f, self.k, self.cap = int(n), int(f), int(k), max(1, int(max_iter_capacity))
+
+    def upload_V(self, p, block, row0=0, col0=0, scale=1.0):
+        a = np.asarray(block)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.ndim != 2:
+            raise ValueError("2-D block expected")
+        if a.shape[0] == 0 or a.shape[1] == 0:
+            return
+        if a.strides[1] != a.itemsize or a.strides[0] % a.itemsize or a.strides[0] < a.shape[1] * a.itemsize:
+            a = np.ascontiguousarray(a)
+        ld = a.strides[0] // a.itemsize
+        _check(self._lib.klnmf_batch_upload_V(self._h, int(p), a.ctypes.data, _np_dtype_code(a), a.shape[0], a.shape[1], ld,
+                                              int(row0), int(col0), float(scale)))
+
+    def upload_V_device_rows_dt(self, p, dev_ptr, f64, row_idx_ptr, rows, cols, ld, row0=0, col0=0, scale=1.0):
+        _check(self._lib.klnmf_batch_upload_V_device_rows_dt(self._h, int(p), _c.c_void_p(dev_ptr), DT_F64 if f64 else DT_F32,
+                                                             _c.c_void_p(row_idx_ptr) if row_idx_ptr else None, int(rows), int(cols),
+                                                             int(ld), int(row0), int(col0), float(scale)))
+
+    def set_H(self, p, H):
+        H = _as_float_array(H)
+        assert H.shape == (self.k, self.f)
+        _check(self._lib.klnmf_batch_set_H(self._h, int(p), H.ctypes.data, _np_dtype_code(H)))
+
+    def set_H_device(self, p, dev_ptr, f64, ld, col0, ncols, last=True):
+        _check(self._lib.klnmf_batch_set_H_device(self._h, int(p), _c.c_void_p(dev_ptr), DT_F64 if f64 else DT_F32, int(ld), int(col0),
+                                                  int(ncols), 1 if last else 0))
+
+    def set_W(self, p, W):
+        W = _as_float_array(W)
+        assert W.shape == (self.n, self.k)
+        _check(self._lib.klnmf_batch_set_W(self._h, int(p), W.ctypes.data, _np_dtype_code(W)))
+
+    def init_W(self):
+        _check(self._lib.klnmf_batch_init_W(self._h))
+
+    def run(self, max_iter, fit, tol_abs):
+        """The loop for every problem; returns [(errors list, n_done, stopped)] in problem order."""
+        max_iter = int(max_iter)
+        if max_iter > self.cap:
+            raise ValueError("max_iter exceeds capacity")
+        _check(self._lib.klnmf_batch_run(self._h, max_iter, 1 if fit else 0, float(tol_abs)))
+        return [self.result(p) for p in range(self.count)]
+
+    def result(self, p):
+        errs = np.zeros(max(1, self.cap), dtype=np.float64)
+        nd = _i64(0)
+        stopped = _c.c_int(0)
+        _check(self._lib.klnmf_batch_result(self._h, int(p), errs.ctypes.data_as(_c.POINTER(_c.c_double)), ctypes.byref(nd),
+                                            ctypes.byref(stopped)))
+        return [float(e) for e in errs[:nd.value]], nd.value, bool(stopped.value)
+
+    def _get(self, fn, p, shape, dtype):
+        out = np.empty(shape, dtype=dtype)
+        _check(fn(self._h, int(p), out.ctypes.data, _np_dtype_code(out)))
+        return out
+
+    def get_W(self, p, dtype=np.float64):
+        return self._get(self._lib.klnmf_batch_get_W, p, (self.n, self.k), dtype)
+
+    def get_H(self, p, dtype=np.float64):
+        return self._get(self._lib.klnmf_batch_get_H, p, (self.k, self.f), dtype)
+
+    def get_W_device(self, p, dev_ptr, f64, ld):
+        _check(self._lib.klnmf_batch_get_W_device(self._h, int(p), _c.c_void_p(dev_ptr), DT_F64 if f64 else DT_F32, int(ld)))
+
+    def query(self, what):
+        v = _i64(0)
+        _check(self._lib.klnmf_batch_query(self._h, int(what), ctypes.byref(v)))
+        return int(v.value)
+
+    def exact_regime(self):
+        """(row chunks, W chunks, H segments, from slabs) of the batch's plan, as `Context.exact_regime()` reads."""
+        return (self.query(Q_EX_ROW_CHUNKS), self.query(Q_EX_W_CHUNKS), self.query(Q_EX_H_SEGMENTS), self.query(Q_EX_H_FROM_SLABS))

@@ -1,4 +1,4 @@
-// libklnmf.so, unit 3 of 5: row shards over the GPUs of a node -- the RCCL entry points (opened at run time), the loop entry every
+// libklnmf.so, unit 3 of 6: row shards over the GPUs of a node -- the RCCL entry points (opened at run time), the loop entry every
 // rank agrees on, the iteration with its ONE grouped all-reduce, and the exchange buffers of the torch path (ctx.hip.h lists the units).
 #include "ctx.hip.h"
 

@@ -1,4 +1,4 @@
-// libklnmf.so, unit 1 of 5: contexts, problems, uploads and downloads (ctx.hip.h lists the units).
+// libklnmf.so, unit 1 of 6: contexts, problems, uploads and downloads (ctx.hip.h lists the units).
 #include "ctx.hip.h"
 #include "csc.hip.h"
 #include "csrgather.hip.h"
@@ -273,7 +273,7 @@ void alloc_csr(klnmf_ctx *c) {
 // is released (free_all: ProblemState back to its defaults), the plan and the switches it was made with are stored, and the
 // buffers it sizes are taken.
 void set_problem(klnmf_ctx *c, int64_t n, int64_t f, int64_t k, int64_t cap, int64_t nnz) {
-    const DevSwitches sw = DevSwitches::read();
+    const DevSwitches sw = problem_switches();
     const ProblemPlan plan = plan_problem(c->prec, n, f, k, nnz, c->cu_count, sw);
     if (plan.refuse != KLNMF_OK && !plan.refuse_releases) fail(plan.refuse, plan.refuse_msg);
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -305,6 +305,9 @@ void copy_2d(klnmf_ctx *c, D *dst, int64_t dld, const S *src, int64_t sld, int64
 }  // namespace
 
 namespace klnmf_host {
+
+// the development switches as a new problem reads them (klnmf_set_problem*, klnmf_batch_set_problem)
+DevSwitches problem_switches() { return DevSwitches::read(); }
 
 void reset_state(klnmf_ctx *c) {
     hipLaunchKernelGGL(k_reset_state, dim3(1), dim3(1), 0, c->stream, c->st);

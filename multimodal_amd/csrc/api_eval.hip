@@ -1,4 +1,4 @@
-// libklnmf.so, unit 4 of 5: evaluation and introspection -- reconstruction products, nearest-neighbour distances, the generalized KL of two
+// libklnmf.so, unit 4 of 6: evaluation and introspection -- reconstruction products, nearest-neighbour distances, the generalized KL of two
 // arrays, the hardware probes, queries and profiling (ctx.hip.h lists the units).
 #include "ctx.hip.h"
 #include "probe.hip.h"

@@ -1,4 +1,4 @@
-// libklnmf.so, unit 5 of 5: a group of contexts -- one per row shard, on one device each (a device may repeat) -- driven from ONE
+// libklnmf.so, unit 5 of 6: a group of contexts -- one per row shard, on one device each (a device may repeat) -- driven from ONE
 // host thread (klnmf_group_*).  The numerator of the H rule and the loss are exchanged by the two launches of group.hip.h, which
 // read the peers' buffers directly; the streams are ordered by events only.  DESIGN.md section 8 has the design and its argument.
 #include <chrono>

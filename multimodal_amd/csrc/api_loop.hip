@@ -1,4 +1,4 @@
-// libklnmf.so, unit 2 of 5: the loop of nmf.py:212-222 -- kernel dispatch, the pieces of an iteration, the stop rule's bookkeeping,
+// libklnmf.so, unit 2 of 6: the loop of nmf.py:212-222 -- kernel dispatch, the pieces of an iteration, the stop rule's bookkeeping,
 // the fp8 regime with its monitor, the loop driver, and the entry points that run loops and single steps (ctx.hip.h lists the units).
 #include "ctx.hip.h"
 

@@ -1,0 +1,152 @@
+// Batched forms of the dense exact loop's kernels (exact.hip.h): B unweighted problems of one shape (n, f, k) advance through
+// the loop of nmf.py:212-222 together, every stage ONE launch with the problem index on the grid.
+//
+//   k_gemm_batch<.., EpiQ / EpiW / EpiWpart / EpiN>   the four contractions: k_gemm's tile loop (gemm_body.hip.h), the same epilogues;
+//                                                     problem p = blockIdx.y / (row tiles of one problem)
+//   k_sum_doubles_batch                               loss reduction + stop rule, one block per problem     nmf.py:214-220
+//   k_wrule_batch                                     the W rule from the feature chunks' slabs             nmf.py:338-343
+//   k_sum_partials_batch                              the H numerator from the row chunks' slabs            nmf.py:349
+//   k_update_H_batch / _part_batch / _norm_batch      the H rule: from slabs, from sums, in segments        nmf.py:349-350
+// (the dense loop transposes nothing: a transposed operand of the tile loop is a stride swap)
+//
+// Layout: every buffer of the single problem, B times, problem p at p x (the single problem's element count) -- V, Q, W[2], H,
+// the slabs [B][chunks][..], loss partials [B][tiles], DevState [B], loss records [B][cap].
+// Summation order: what is summed is summed by the code the single-context kernels run -- the tile loop, the epilogues, NumSlabs::get,
+// h_product, block_sum, decide_here -- over the same chunk counts, so a problem in a batch has the bits of the same problem alone.
+// Stop state: one DevState per problem; the blocks of a stopped problem return at their first instruction, as every block of a
+// stopped context does, and nothing waits on anything.
+#pragma once
+#include "exact.hip.h"
+
+namespace klnmf {
+
+// the epilogue of problem p: its pointers moved to the problem's part of each buffer (M x N: the contraction's output shape;
+// the slab epilogues hold gridDim.z slabs per problem)
+template <typename T>
+__device__ __forceinline__ EpiQ<T> at_problem(EpiQ<T> e, int p, int M, int N) {
+    const int64_t o = (int64_t)p * M * N;
+    e.V += o; e.Q += o;      // (loss_part: indexed by blockIdx.y, which carries p)
+    return e;
+}
+template <typename T, typename Fac>
+__device__ __forceinline__ EpiW<T, Fac> at_problem(EpiW<T, Fac> e, int p, int M, int N) {
+    const int64_t o = (int64_t)p * M * N;
+    e.Wold += o; e.Wnew += o;
+    return e;
+}
+template <typename T>
+__device__ __forceinline__ EpiWpart<T, 1> at_problem(EpiWpart<T, 1> e, int p, int, int) {
+    e.P[0] += (int64_t)p * gridDim.z * e.slab;
+    return e;
+}
+template <typename T>
+__device__ __forceinline__ EpiN<T, 1> at_problem(EpiN<T, 1> e, int p, int, int) {
+    e.Npart[0] += (int64_t)p * gridDim.z * e.slab;
+    return e;
+}
+
+// k_gemm for B problems: grid (column tiles, B x ytiles, chunks); A and B `aps` / `bps` elements apart from problem to problem.
+// The tile loop is k_gemm's own text (gemm_body.hip.h) on problem p's operands, in the instantiation the exact modes run
+// (64 x 64 tiles on the fp64 / fp32 MFMA).
+template <typename T, typename Epi>
+__global__ __launch_bounds__(256, 3) void k_gemm_batch(int M, int N, int K, const T *A0, int64_t ars, int64_t acs, int64_t aps,
+                                                       const T *B0, int64_t brs, int64_t bcs, int64_t bps, int kchunk,
+                                                       const DevState *st, int ytiles, Epi epi0) {
+    const int p = blockIdx.y / ytiles;
+    if (st[p].stop) return;
+    constexpr int TT = 4;
+    constexpr bool MF = true;
+    const T *A = A0 + p * aps, *B = B0 + p * bps;
+    Epi epi = at_problem(epi0, p, M, N);
+    const int row_tile = (int)blockIdx.y - p * ytiles;
+#define KL_GEMM_ROW_TILE row_tile
+#include "gemm_body.hip.h"
+#undef KL_GEMM_ROW_TILE
+}
+
+// k_sum_doubles with the stop rule, block p for problem p: `count` partials each, the loss into out[2 p]
+KL_GLOBAL __launch_bounds__(1024) void k_sum_doubles_batch(const double *part, int64_t count, double *out, DevState *st, int decide,
+                                                            double tol_abs, double *errors, int64_t cap) {
+    const int p = blockIdx.x;
+    if (st[p].stop) return;
+    __shared__ double red[16];
+    part += p * count;
+    double s = 0;
+    for (int64_t e = threadIdx.x; e < count; e += blockDim.x) s += part[e];
+    const double t = block_sum(s, red);
+    if (threadIdx.x == 0) {
+        out[2 * p] = t; out[2 * p + 1] = 0;
+        decide_here(DecideArgs{decide, st + p, tol_abs, errors + p * cap, cap}, t);
+    }
+}
+
+// k_wrule_exact, grid (.., B): part / epi hold problem 0's pointers; part.slab = n k, part.nslab slabs per problem
+template <typename T, typename Fac>
+__global__ void k_wrule_batch(NumSlabs<T, Fac::S> part, const DevState *st, EpiW<T, Fac> epi) {
+    const int p = blockIdx.y;
+    if (st[p].stop) return;
+    const NumSlabs<T, Fac::S> mine = part.at((int64_t)p * part.nslab * part.slab);
+    epi.Wold += p * part.slab; epi.Wnew += p * part.slab;
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < part.slab; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = e / epi.k;
+        epi.rule(e, r, e - r * epi.k, mine.get(e));
+    }
+}
+
+// k_sum_partials, grid (.., B)
+template <typename T>
+__global__ void k_sum_partials_batch(NumArray<T, 1> part, T *out, int64_t count, int nslab, const DevState *st) {
+    const int p = blockIdx.y;
+    if (st[p].stop) return;
+    const NumSlabs<T, 1> slabs{part.at((int64_t)p * nslab * count), nslab, count};
+    out += p * count;
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < count; e += (int64_t)gridDim.x * blockDim.x)
+        out[e] = slabs.get(e)[0];
+}
+
+// elements from one problem's numerator source to the next's
+template <typename T> __device__ __forceinline__ int64_t problem_stride(const NumArray<T, 1> &, int64_t kf) { return kf; }
+template <typename T> __device__ __forceinline__ int64_t problem_stride(const NumSlabs<T, 1> &s, int64_t) { return s.nslab * s.slab; }
+
+// k_update_H, grid (k, B)
+template <typename T, typename Num>
+__global__ __launch_bounds__(256) void k_update_H_batch(T *H, RuleIn<Num, FacNum> in, int64_t f, const DevState *st) {
+    const int p = blockIdx.y;
+    if (st[p].stop) return;
+    __shared__ double red[16];
+    __shared__ double total;
+    const int64_t kf = (int64_t)gridDim.x * f;
+    T *row = H + p * kf + blockIdx.x * f;
+    const double s = h_product(row, in.num.at(p * problem_stride(in.num, kf) + blockIdx.x * f), in.fac, (int64_t)blockIdx.x, 0, f);
+    const double t = block_sum(s, red);
+    if (threadIdx.x == 0) total = t;
+    __syncthreads();
+    const T d = (T)(kEpsNorm + total);
+    for (int64_t j = threadIdx.x; j < f; j += blockDim.x) row[j] = row[j] / d;
+}
+
+// k_update_H_part / k_update_H_norm, grid (segments, k, B); part [B][k][segments]
+template <typename T>
+__global__ __launch_bounds__(256) void k_update_H_part_batch(T *H, RuleIn<NumArray<T, 1>, FacNum> in, int64_t f, int64_t seg,
+                                                             double *part, const DevState *st) {
+    const int p = blockIdx.z;
+    if (st[p].stop) return;
+    __shared__ double red[16];
+    const int64_t a = blockIdx.y, j0 = blockIdx.x * seg, j1 = min(f, j0 + seg), pa = (int64_t)p * gridDim.y + a;
+    const double s = h_product(H + pa * f, in.num.at(pa * f), in.fac, a, j0, j1);
+    const double t = block_sum(s, red);
+    if (threadIdx.x == 0) part[pa * gridDim.x + blockIdx.x] = t;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_update_H_norm_batch(T *H, int64_t f, int64_t seg, const double *part, const DevState *st) {
+    const int p = blockIdx.z;
+    if (st[p].stop) return;
+    const int64_t j0 = blockIdx.x * seg, j1 = min(f, j0 + seg), pa = (int64_t)p * gridDim.y + blockIdx.y;
+    double total = 0;
+    for (unsigned z = 0; z < gridDim.x; ++z) total += part[pa * gridDim.x + z];      // (every thread: the same order, the same bits)
+    const T d = (T)(kEpsNorm + total);
+    T *row = H + pa * f;
+    for (int64_t j = j0 + threadIdx.x; j < j1; j += blockDim.x) row[j] = row[j] / d;
+}
+
+}  // namespace klnmf

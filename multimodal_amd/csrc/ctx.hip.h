@@ -8,6 +8,8 @@
 //   api_eval.hip     evaluation and introspection: reconstruction products (learner.py:80-84), distances, queries, profiling
 //   api_group.hip    a group of contexts (row shards, one device each, a device may repeat) driven from one host thread: the
 //                    exchange of group.hip.h between their streams, the loop of klnmf_group_run
+//   api_batch.hip    a batch of dense, unweighted problems of one shape in KLNMF_PREC_F64 / F32 (klnmf_batch_*): the loop's stages as
+//                    one launch each for all of them (batch.hip.h), the plan of one problem for its share of the CUs
 // This header: error handling, the device block cache, the development switches and the context itself -- its state in four
 // groups, one per lifetime (ContextState, ProblemState, LoopState, LoopRecord); plan.hip.h: the launch plan of a problem, the
 // value ProblemState is built on.
@@ -500,6 +502,7 @@ enum PostMode { POST_FULL = 0, POST_SUM = 1, POST_RULE = 2 };
 static const LossArgs kNoLoss{nullptr, 0, 0.0, nullptr, 0, nullptr, 0.0, nullptr, 0, 0};
 struct Refusals { int v_overflow = 0, op_range = 0; };
 // api_context.hip
+DevSwitches problem_switches();
 void reset_state(klnmf_ctx *c);
 void fast_pack_H(klnmf_ctx *c, const unsigned *wmax = nullptr);
 void measure_and_pack(klnmf_ctx *c, bool from_init = false);

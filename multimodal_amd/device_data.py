@@ -20,7 +20,8 @@ import numpy as np
 import scipy.sparse as sp
 
 from . import _native
-from .lib.nmf import KLdivNMF, check_non_negative, check_weights, _default_precision, resolve_precision, _csr_of, _note_once
+from .lib.nmf import (KLdivNMF, check_non_negative, check_weights, _default_precision, resolve_precision, _csr_of, _note_once,
+                      batch_precision, fit_uploaded_batch)
 from .lib.sklearn_utils import atleast2d_or_csr
 
 
@@ -341,6 +342,81 @@ class DeviceDataset(object):
     def reconstruct_internal(self, learner, orig_mod, rows, iterations):
         return self.reconstruct_internal_multi(learner, [orig_mod], rows, iterations)
 
+    # ---- the same calls for the runs of a sweep that share a shape: one batch (klnmf_batch_*, csrc/batch.hip.h) ----
+    def _batch_uploads(self, which, rows_list, coefs_list):
+        """One `upload(batch, p)` per row list: the rows of the dense modalities `which` into problem p of a `_native.Batch`."""
+        uploads = []
+        for rows, coefs in zip(rows_list, coefs_list):
+            rows = np.ascontiguousarray(rows, dtype=np.int64)
+            assert rows.size == 0 or (int(rows.min()) >= 0 and int(rows.max()) < self.n_samples)
+            idx = self._to_device(rows)
+
+            def upload(batch, p, idx=idx, coefs=coefs):
+                col = 0
+                for w, c in zip(which, coefs):
+                    b, f64 = self.source(w, batch.precision_name)
+                    batch.upload_V_device_rows_dt(p, b.data_ptr(), f64, idx.data_ptr(), idx.numel(), b.shape[1], b.stride(0),
+                                                  row0=0, col0=col, scale=c)
+                    col += b.shape[1]
+                self._synchronize()      # the batch runs on its own stream; idx must outlive the kernel
+            uploads.append(upload)
+        return uploads
+
+    def _batch_route(self, which, rows_list, nmfs, n_features):
+        """'f64' / 'f32' if the calls on `rows_list` can run as one batch: row lists of one length, dense unmasked modalities, models
+        that `batch_precision` accepts.  None: the loop over the single calls."""
+        if not nmfs or len(set(len(r) for r in rows_list)) != 1 or self.presence_route(which) or self.sparse_route(which):
+            return None
+        return batch_precision(nmfs, len(rows_list[0]), n_features)
+
+    def train_many(self, learners, rows_list, iterations, init_dictionaries=None):
+        """[self.train(l, rows, iterations, init) for l, rows, init in ...] -- as ONE batch where all row lists have one length,
+        all learners share k and no modality is masked or kept as CSR; the loop over `train` otherwise."""
+        learners, rows_list = list(learners), [list(r) for r in rows_list]
+        inits = list(init_dictionaries) if init_dictionaries is not None else [None] * len(learners)
+        which = list(range(len(self.blocks)))
+        nmfs = []
+        for learner, init in zip(learners, inits):
+            nmf = KLdivNMF(n_components=learner.k, max_iter=iterations, tol=0)
+            if init is not None:
+                nmf._init_dictionary = np.asarray(init)
+            nmfs.append(nmf)
+        plain = all(l.sparseness is None and self.dims == list(l.dim) for l in learners)
+        prec = self._batch_route(which, rows_list, nmfs, sum(self.dims)) if plain else None
+        if prec is None:
+            return [self.train(l, rows, iterations, init_dictionary=init) for l, rows, init in zip(learners, rows_list, inits)]
+        uploads = self._batch_uploads(which, rows_list, [list(l.coef) for l in learners])
+        fit_uploaded_batch(nmfs, prec, len(rows_list[0]), sum(self.dims), uploads, [lambda H: np.float64] * len(nmfs), _fit=True)
+        self.last_weights_route = None
+        for learner, nmf in zip(learners, nmfs):
+            learner.nmf_train = nmf
+            learner.dico = nmf.components_
+        return learners
+
+    def reconstruct_internal_multi_many(self, learners, orig_mods, rows_list, iterations):
+        """[self.reconstruct_internal_multi(l, orig_mods, rows, iterations) for l, rows in ...] -- as one batch under
+        `train_many`'s conditions (here: on the selected modalities)."""
+        learners, rows_list = list(learners), [list(r) for r in rows_list]
+        if not learners:
+            return []
+        which = [learners[0].get_index(m) for m in orig_mods]
+        nmfs = []
+        for learner in learners:
+            dico = learner.get_stacked_dicos(orig_mods)
+            nmf = KLdivNMF(n_components=dico.shape[0], max_iter=iterations, tol=0)
+            nmf.components_ = dico
+            nmf._init_dictionary = dico
+            nmfs.append(nmf)
+        same = all([l.get_index(m) for m in orig_mods] == which and list(l.dim) == self.dims for l in learners)
+        n_features = sum(self.dims[w] for w in which)
+        prec = self._batch_route(which, rows_list, nmfs, n_features) if same else None
+        if prec is None:
+            return [self.reconstruct_internal_multi(l, orig_mods, rows, iterations) for l, rows in zip(learners, rows_list)]
+        uploads = self._batch_uploads(which, rows_list, [[l.coef[w] for w in which] for l in learners])
+        out = fit_uploaded_batch(nmfs, prec, len(rows_list[0]), n_features, uploads, [lambda H: np.float64] * len(nmfs), _fit=False)
+        self.last_weights_route = None
+        return out
+
 
 class DeviceEvaluation(object):
     """What one run's evaluation needs of a trained learner, kept on the GPU (next-row N1; experiment.py:233-277, 332-371):
@@ -405,11 +481,53 @@ class DeviceEvaluation(object):
         torch.cuda.synchronize(self.dev)
         return out
 
-    def _set_dictionary(self, ctx, which):
+    @staticmethod
+    def internal_many(evaluations, mods, rows_list):
+        """[ev.internal(mods, rows) for ev, rows in ...] for the evaluations of a sweep's runs -- as ONE batch where they share the
+        dataset, k, the iteration count and the number of rows, no selected modality is masked or kept as CSR and the shape
+        runs in f64 / f32: the dictionaries go in by klnmf_batch_set_H_device, the coefficients stay on the device
+        (klnmf_batch_get_W_device).  The loop over `internal` otherwise."""
+        evaluations, rows_list = list(evaluations), list(rows_list)
+        if not evaluations:
+            return []
+        first = evaluations[0]
+        torch, ds, lr = first.torch, first.ds, first.learner
+        which = [lr.get_index(m) for m in mods]
+        models = [KLdivNMF(n_components=ev.k, max_iter=ev.iter_test, tol=0) for ev in evaluations]
+        same = all(ev.ds is ds and list(ev.learner.dim) == list(lr.dim) and [ev.learner.get_index(m) for m in mods] == which
+                   for ev in evaluations)
+        n, f = len(rows_list[0]), sum(lr.dim[w] for w in which)
+        prec = ds._batch_route(which, rows_list, models, f) if same else None
+        if prec is None:
+            return [ev.internal(mods, rows) for ev, rows in zip(evaluations, rows_list)]
+        idxs = [ev._rows(rows) for ev, rows in zip(evaluations, rows_list)]
+        outs = [torch.empty((n, ev.k), dtype=torch.float64, device=ev.dev) for ev in evaluations]
+        with _native.Batch(prec, len(evaluations), device=models[0].device) as batch:
+            batch.set_problem(n, f, first.k, first.iter_test)
+            for p, (ev, idx) in enumerate(zip(evaluations, idxs)):
+                col = 0
+                for w in which:
+                    b, f64 = ds.source(w, batch.precision_name)
+                    batch.upload_V_device_rows_dt(p, b.data_ptr(), f64, idx.data_ptr(), n, b.shape[1], b.stride(0), row0=0, col0=col,
+                                                  scale=ev.learner.coef[w])
+                    col += b.shape[1]
+                ev._set_dictionary(batch, which, p)
+                ev.last_weights_route = None
+            ds._synchronize()                              # the batch runs on its own stream; the indices must outlive the kernels
+            batch.init_W()                                 # W0 = X . H^T with the dictionary itself (nmf.py:156, 283)
+            batch.run(first.iter_test, False, 0.0)
+            for p, out in enumerate(outs):
+                batch.get_W_device(p, out.data_ptr(), True, first.k)
+        torch.cuda.synchronize(first.dev)
+        return outs
+
+    def _set_dictionary(self, ctx, which, p=None):
+        """The stacked dictionary of the modalities `which` into `ctx` (p: into problem p of a `_native.Batch`)."""
+        put = ctx.set_H_device if p is None else (lambda *a, **kw: ctx.set_H_device(p, *a, **kw))
         col = 0
         for i, w in enumerate(which):                      # the stacked dictionary of these modalities, block by block
             d = self.learner.dim[w]
-            ctx.set_H_device(self.dico.data_ptr() + 8 * self.offsets[w], True, self.F, col, d, last=(i == len(which) - 1))
+            put(self.dico.data_ptr() + 8 * self.offsets[w], True, self.F, col, d, last=(i == len(which) - 1))
             col += d
 
     def _internal_sparse(self, model, mods, which, rows, out):

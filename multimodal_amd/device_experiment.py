@@ -105,23 +105,39 @@ def evaluate_internal(dataset, learner, rows_test, rows_ex, labels_test, labels_
 
 # ---- the same two evaluations with everything between the transforms and the label lists ON the device (DeviceEvaluation:
 # dictionary uploaded once, coefficients / reconstructions / raw rows as device matrices, distances by one kernel) --------
-def evaluate_on_device(dataset, learner, rows_test, rows_ex, labels_test, labels_ex, iter_test):
-    """`evaluate` (TwoModalitiesExperiment._evaluate) without host round trips."""
+def internal_sets(kind, n_modalities):
+    """The modality sets (tuples of indices) whose internal coefficients an evaluation of `kind` computes, in its order."""
+    if kind == 'two':
+        return [(m,) for m in range(n_modalities)]
+    sets = []
+    for mods, _rest in tested_combinations(n_modalities):
+        if mods not in sets:
+            sets.append(mods)
+    return sets
+
+
+def evaluate_on_device(dataset, learner, rows_test, rows_ex, labels_test, labels_ex, iter_test, ev=None, internals=None):
+    """`evaluate` (TwoModalitiesExperiment._evaluate) without host round trips.  ev / internals: the run's `DeviceEvaluation`
+    and its internal coefficients {(set, 'test' | 'ex'): device tensor} where a batch computed them (`_sweep_batch`)."""
     from .device_data import DeviceEvaluation
-    ev = DeviceEvaluation(dataset, learner, iter_test)
+    if ev is None:
+        ev = DeviceEvaluation(dataset, learner, iter_test)
     M = len(learner.mod)
 
-    def transformations(rows):
-        internals = [ev.internal([learner.mod[m]], rows) for m in range(M)]
+    def transformations(rows, side):
+        if internals is not None:
+            coefficients = [internals[((m,), side)] for m in range(M)]
+        else:
+            coefficients = [ev.internal([learner.mod[m]], rows) for m in range(M)]
         out = [[None] * M for _ in range(M)]
         for i in range(M):
             out[i][i] = ev.raw(i, rows)
             for o in range(M):
                 if o != i:
-                    out[i][o] = ev.reconstruct(internals[i], learner.mod[o])
-            out[i].append(internals[i])
+                    out[i][o] = ev.reconstruct(coefficients[i], learner.mod[o])
+            out[i].append(coefficients[i])
         return out
-    t_test, t_ex = transformations(rows_test), transformations(rows_ex)
+    t_test, t_ex = transformations(rows_test, 'test'), transformations(rows_ex, 'ex')
     results = {}
     for mod1, mod2, mod_cmp in product(range(M), range(M), [INTERNAL] + list(range(M))):
         for metric, suffix in DEVICE_MEASURES:
@@ -132,19 +148,20 @@ def evaluate_on_device(dataset, learner, rows_test, rows_ex, labels_test, labels
     return results
 
 
-def evaluate_internal_on_device(dataset, learner, rows_test, rows_ex, labels_test, labels_ex, iter_test):
-    """`evaluate_internal` (ThreeModalitiesExperiment._evaluate) without host round trips."""
+def evaluate_internal_on_device(dataset, learner, rows_test, rows_ex, labels_test, labels_ex, iter_test, ev=None, internals=None):
+    """`evaluate_internal` (ThreeModalitiesExperiment._evaluate) without host round trips.  ev / internals: as `evaluate_on_device`."""
     from .device_data import DeviceEvaluation
-    ev = DeviceEvaluation(dataset, learner, iter_test)
+    if ev is None:
+        ev = DeviceEvaluation(dataset, learner, iter_test)
     combos = tested_combinations(len(learner.mod))
 
-    def internals(rows):
+    def internals_of(rows, side):
         got = {}
         for mods, _rest in combos:
             if mods not in got:
-                got[mods] = ev.internal([learner.mod[m] for m in mods], rows)
+                got[mods] = internals[(mods, side)] if internals is not None else ev.internal([learner.mod[m] for m in mods], rows)
         return got
-    t_test, t_ex = internals(rows_test), internals(rows_ex)
+    t_test, t_ex = internals_of(rows_test, 'test'), internals_of(rows_ex, 'ex')
     results = {}
     for mods1, mods2 in combos:
         for metric, suffix in DEVICE_MEASURES:
@@ -188,9 +205,8 @@ def perform_one_run(dataset, modalities, coefs, k, iter_train, iter_test, rows_t
     return learner, results
 
 
-def _one_sweep_job(dataset, modalities, coefs, labels, examples, k, run, iter_train, iter_test, test_ratio, seed, kind):
-    """One job of the reference's sweep (samples/launcher.py:71-99: an experiment with run_mode 'single' = one random
-    test_ratio split, experiment.py:131-133): seeded per (k, run), so that it does not matter which rank executes it."""
+def _sweep_split(dataset, examples, k, run, test_ratio, seed):
+    """(train rows, test rows, H0) of the job (k, run): from a stream seeded by (seed, k, run) alone."""
     rs = np.random.RandomState([seed, k, run])
     n_all = dataset.n_samples
     others = [i for i in range(n_all) if i not in set(examples)]
@@ -201,15 +217,60 @@ def _one_sweep_job(dataset, modalities, coefs, labels, examples, k, run, iter_tr
     f = sum(dataset.dims)
     H0 = rs.random_sample((k, f)) + .01                      # the init rule of nmf.py:149-151 from the job's own stream
     H0 /= 1e-16 + H0.sum(axis=1, keepdims=True)
+    return train, test, H0
+
+
+def _one_sweep_job(dataset, modalities, coefs, labels, examples, k, run, iter_train, iter_test, test_ratio, seed, kind):
+    """One job of the reference's sweep (samples/launcher.py:71-99: an experiment with run_mode 'single' = one random
+    test_ratio split, experiment.py:131-133): seeded per (k, run), so that it does not matter which rank executes it."""
+    train, test, H0 = _sweep_split(dataset, examples, k, run, test_ratio, seed)
     _, res = perform_one_run(dataset, modalities, coefs, k, iter_train, iter_test, train, test, list(examples),
                              [labels[t] for t in test], [labels[e] for e in examples], init_dictionary=H0, kind=kind)
     return {kk: float(v) for kk, v in res.items() if kk.startswith('score_')}
 
 
+def _sweep_batch(dataset, modalities, coefs, labels, examples, k, runs, iter_train, iter_test, test_ratio, seed, kind):
+    """The jobs (k, run) for run in `runs` as one batch: the trainings by `DeviceDataset.train_many`, every internal transform of
+    their evaluations by `DeviceEvaluation.internal_many`; reconstructions, distances and scores per run.  Seeds per (k, run), as
+    `_one_sweep_job`'s: which batch a run lands in does not matter."""
+    from .device_data import DeviceEvaluation
+    splits = [_sweep_split(dataset, examples, k, run, test_ratio, seed) for run in runs]
+    learners = [MultimodalLearner(list(modalities), list(dataset.dims), list(coefs), k) for _ in runs]
+    dataset.train_many(learners, [sp[0] for sp in splits], iter_train, init_dictionaries=[sp[2] for sp in splits])
+    if kind is None:
+        kind = 'two' if len(modalities) == 2 else 'internal'
+    evs = [DeviceEvaluation(dataset, learner, iter_test) for learner in learners]
+    internals = [{} for _ in runs]
+    for mods in internal_sets(kind, len(modalities)):
+        names = [modalities[m] for m in mods]
+        for side, rows_list in (('test', [sp[1] for sp in splits]), ('ex', [list(examples)] * len(runs))):
+            for got, t in zip(internals, DeviceEvaluation.internal_many(evs, names, rows_list)):
+                got[(mods, side)] = t
+    evaluate_ = evaluate_on_device if kind == 'two' else evaluate_internal_on_device
+    out = []
+    for run, learner, ev, got, (_train, test, _H0) in zip(runs, learners, evs, internals, splits):
+        res = evaluate_(dataset, learner, test, list(examples), [labels[t] for t in test], [labels[e] for e in examples], iter_test,
+                        ev=ev, internals=got)
+        out.append((k, run, {kk: float(v) for kk, v in res.items() if kk.startswith('score_')}))
+    return out
+
+
+def sweep_batches(pairs, batch):
+    """The (k, run) pairs of one worker as batches: lists of pairs of ONE k, at most `batch` each, every pair in exactly one;
+    the ks in the order they first occur, the pairs of a k in their order.  batch = 1: one pair per batch, in `pairs`' order."""
+    batch = max(1, int(batch))
+    if batch == 1:
+        return [[pair] for pair in pairs]
+    by_k = {}
+    for k, run in pairs:
+        by_k.setdefault(k, []).append((k, run))
+    return [group[i:i + batch] for group in by_k.values() for i in range(0, len(group), batch)]
+
+
 def _sweep_worker(job):
     """One process per GPU: uploads the modalities once, runs its share of the (k, run) grid, returns the scores."""
     (device, rank, world, data, modalities, coefs, labels, examples, ks, n_runs, iter_train, iter_test, test_ratio, seed, kind,
-     precision, keep_sparse, presence) = job
+     precision, keep_sparse, presence, batch) = job
     import os
     import torch
     saved = {name: os.environ.get(name) for name in ('KLNMF_PRECISION', 'KLNMF_DEVICE', 'KLNMF_DEVICES')}
@@ -222,9 +283,14 @@ def _sweep_worker(job):
         from .device_data import DeviceDataset
         ds = DeviceDataset(data, device=device, keep_sparse=keep_sparse, presence=presence)
         out = []
-        for k, run in sweep_assignment(ks, n_runs, rank, world):
-            out.append((k, run, _one_sweep_job(ds, modalities, coefs, labels, examples, k, run, iter_train, iter_test,
-                                               test_ratio, seed, kind)))
+        for group in sweep_batches(sweep_assignment(ks, n_runs, rank, world), batch):
+            if len(group) == 1:      # (batch = 1: today's path, call for call)
+                k, run = group[0]
+                out.append((k, run, _one_sweep_job(ds, modalities, coefs, labels, examples, k, run, iter_train, iter_test,
+                                                   test_ratio, seed, kind)))
+            else:
+                out.extend(_sweep_batch(ds, modalities, coefs, labels, examples, group[0][0], [run for _, run in group], iter_train,
+                                        iter_test, test_ratio, seed, kind))
         return out
     finally:   # a one-device sweep runs in the caller's process: leave its environment as it was
         for name, value in saved.items():
@@ -235,7 +301,7 @@ def _sweep_worker(job):
 
 
 def run_sweep(data_matrices, labels, modalities, ks, n_runs, iter_train=50, iter_test=50, coefs=None, examples=None,
-              test_ratio=.1, seed=0, devices=None, precision=None, kind=None, keep_sparse=False, presence=None):
+              test_ratio=.1, seed=0, devices=None, precision=None, kind=None, keep_sparse=False, presence=None, batch=1):
     """The k sweep of the reference's launcher (samples/launcher.py:68-99, 122-126: Ks x N_RUN independent experiments,
     one OS process each) on the GPUs of this node: ONE process per device, each with the modalities resident on its GPU,
     executing `sweep_assignment`'s share of the (k, run) grid -- replica parallelism, no communication.  Returns
@@ -249,7 +315,10 @@ def run_sweep(data_matrices, labels, modalities, ks, n_runs, iter_train=50, iter
     device and the runs take the reference's sparse branch (`DeviceDataset`; default: densified, as before); presence: a row x
     modality presence mask kept on every device beside the modalities (`DeviceDataset(presence=...)`, checked here before any
     process starts): the runs' fits and transforms on masked modalities minimise the masked cost.  The default coefficients
-    stay 1 / the mean row sum over all samples, absent ones included."""
+    stay 1 / the mean row sum over all samples, absent ones included.
+    batch: each worker runs its (k, run) pairs of equal k in batches of at most `batch` (`sweep_batches`): the trainings and the
+    evaluations' internal transforms of a batch as one launch sequence (klnmf_batch_*) where the shapes allow it (dense, unmasked
+    modalities, f64 / f32); 1 (default): one pair after another, as before."""
     import torch
     if keep_sparse:
         data = [m.tocsr() if hasattr(m, 'tocsr') else np.asarray(m) for m in data_matrices]
@@ -268,7 +337,7 @@ def run_sweep(data_matrices, labels, modalities, ks, n_runs, iter_train=50, iter
         devices = list(range(max(1, torch.cuda.device_count())))
     world = len(devices)
     jobs = [(dev, r, world, data, list(modalities), list(coefs), labels, list(examples), list(ks), int(n_runs), iter_train,
-             iter_test, test_ratio, seed, kind, precision, bool(keep_sparse), presence) for r, dev in enumerate(devices)]
+             iter_test, test_ratio, seed, kind, precision, bool(keep_sparse), presence, int(batch)) for r, dev in enumerate(devices)]
     if world == 1:
         parts = [_sweep_worker(jobs[0])]
     else:

@@ -30,6 +30,7 @@ list of them: the dense loop then runs over row shards, one context per entry --
 `CSR_SHARD_MIN_NNZ` stored entries per shard -- `_fit_group_csr`).  Environment: KLNMF_PRECISION,
 KLNMF_DEVICES (a comma-separated list, the default `device`), KLNMF_DEVICE.
 """
+import copy
 import os
 import sys
 
@@ -763,3 +764,108 @@ class KLdivNMF(object):
         """normalize_rows(H * (W^T.Q)) (reference nmf.py:345-351); array `weights`:
         normalize_rows(H * (W^T.(weights * Q)) / (W^T.weights)), factor 1 where the denominator is 0."""
         return cls._step(X, W, H, Q, eps, 'H', weights)
+
+
+# ------------------------------------------------------------------ batches ---
+_EXACT_LOOP_REPORT = {}
+
+
+def _exact_loop_report(precision, device):
+    """`Context.fp8_report()` behind a loop of the exact modes -- no e4m3 operand, no monitor: the same record whatever the
+    problem -- as the library itself reports it: read once per (precision, device) behind a one-element fit."""
+    key = (precision, int(device))
+    if key not in _EXACT_LOOP_REPORT:
+        with _native.Context(precision=precision, device=int(device)) as ctx:
+            ctx.set_problem(1, 1, 1, 1)
+            ctx.upload_V(np.ones((1, 1)))
+            ctx.set_H(np.ones((1, 1)))
+            ctx.init_W()
+            ctx.run(1, True, 0.0)
+            _EXACT_LOOP_REPORT[key] = ctx.fp8_report()
+    return copy.deepcopy(_EXACT_LOOP_REPORT[key])
+
+
+def batch_precision(models, n, f):
+    """'f64' / 'f32' if `models` can run as ONE batch of dense n x f problems (klnmf_batch_*): they agree in n_components, tol,
+    max_iter and precision, that precision resolves to f64 or f32 for the shape (`resolve_precision`), and every model is on
+    one and the same single device.  None otherwise."""
+    first = models[0]
+    same = all((m.n_components, m.tol, m.max_iter, m.precision, m.devices) ==
+               (first.n_components, first.tol, first.max_iter, first.precision, first.devices) for m in models)
+    if not same or len(first.devices) != 1 or not 1 <= len(models) <= _native.BATCH_MAX:
+        return None
+    prec = resolve_precision(first.precision, n, f, first.n_components or f)
+    return prec if _native.PRECISIONS[prec] in (_native.PREC_F64, _native.PREC_F32) else None
+
+
+def fit_uploaded_batch(models, precision, n_samples, n_features, uploads, out_dtype_ofs, _fit=True, return_errors=False):
+    """`KLdivNMF._fit_uploaded` for len(models) dense, unweighted problems of one shape as one `_native.Batch`: problem p is
+    placed by `uploads[p](batch, p)`; model p ends as its own `_fit_uploaded` would leave it, with `last_batch_size` set.
+    Returns the list of the calls' results."""
+    B = len(models)
+    max_iter = int(models[0].max_iter)
+    H_inits = []
+    for m in models:                          # (list order: the global numpy stream is consumed as the sequential calls would)
+        m.last_weights_route = None
+        if not m.n_components:
+            m.n_components = n_features
+        H_inits.append(m._init_H(n_features))
+    k = models[0].n_components
+    tol_abs = models[0].tol * n_samples * n_features      # nmf.py:207
+    with _native.Batch(precision, B, device=models[0].device) as batch:
+        batch.set_problem(n_samples, n_features, k, max_iter)
+        for p in range(B):
+            uploads[p](batch, p)
+            batch.set_H(p, H_inits[p])
+        batch.init_W()                        # W0 = X . H_init^T (nmf.py:156)
+        for p, m in enumerate(models):
+            if _fit:
+                m.components_ = H_inits[p]    # nmf.py:203-204
+            elif m.components_ is not H_inits[p]:
+                batch.set_H(p, m.components_)      # loop runs on components_ (nmf.py:214)
+        results = batch.run(max_iter, _fit, tol_abs)
+        outs = []
+        for p, (m, (errors, n_done, stopped)) in enumerate(zip(models, results)):
+            out_dtype = out_dtype_ofs[p](H_inits[p])
+            m.last_fp8_report = _exact_loop_report(precision, m.device)
+            m.last_fp8_report['outside_f16_envelope'] = None      # (`_check_f16_envelope`: not a 16-bit loop)
+            m.last_batch_size = B
+            W = batch.get_W(p, dtype=out_dtype)
+            if _fit and n_done > 0:
+                m.components_ = batch.get_H(p, dtype=out_dtype)
+            n_iter = n_done + 1 if stopped else max_iter
+            if max_iter > 0 and n_iter == max_iter and tol_abs > 0:   # nmf.py:224-225
+                sys.stderr.write("Warning: Iteration limit reached during fit\n")
+            outs.append((W, errors) if return_errors else W)
+    return outs
+
+
+def fit_transform_batch(models, Xs, _fit=True, return_errors=False):
+    """[models[i].fit_transform(Xs[i], _fit=_fit, return_errors=return_errors) for i ...] -- the independent fits of a sweep
+    (samples/launcher.py:68-99) -- as ONE batch where that is possible: all Xs dense and of one shape, the models as
+    `batch_precision` asks.  Every stage of an iteration is then one launch for all problems (csrc/batch.hip.h); each model
+    stops on its own loss record.  Otherwise the models run one after another through `fit_transform`, unchanged.  Each model
+    gets `last_batch_size`: the batch's size, or 1.  The initial dictionaries are drawn in list order (or taken from
+    `_init_dictionary`), so the global numpy stream is consumed exactly as by the sequential calls."""
+    models, Xs = list(models), list(Xs)
+    if len(models) != len(Xs):
+        raise ValueError("fit_transform_batch: one X per model expected (%d models, %d Xs)" % (len(models), len(Xs)))
+    dense = bool(Xs) and not any(sp.issparse(X) for X in Xs)
+    if dense:
+        Xs = [atleast2d_or_csr(X) for X in Xs]
+        dense = len(set(X.shape for X in Xs)) == 1
+    precision = batch_precision(models, *Xs[0].shape) if dense else None
+    if precision is None:
+        outs = []
+        for m, X in zip(models, Xs):
+            outs.append(m.fit_transform(X, _fit=_fit, return_errors=return_errors))
+            m.last_batch_size = 1
+        return outs
+    blocks = []
+    for X in Xs:
+        check_non_negative(X, "NMF.fit")
+        blocks.append(_dense(X))
+    n, f = blocks[0].shape
+    uploads = [lambda batch, p, b=b: batch.upload_V(p, b) for b in blocks]
+    out_dtype_ofs = [lambda H_init, b=b: _out_dtype(H_init, b) for b in blocks]
+    return fit_uploaded_batch(models, precision, n, f, uploads, out_dtype_ofs, _fit=_fit, return_errors=return_errors)
