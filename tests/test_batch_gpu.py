@@ -23,6 +23,7 @@ import pytest
 from multimodal_amd import _native
 from oracle import klnmf_oracle as orc
 from tests import exact_cases as ec
+from tests.loop_piece_cases import stop_rule
 from tests.test_sparse_gpu import _MEASURED, _report_measured, check  # noqa: F401  (the autouse fixture prints what was measured)
 
 pytestmark = pytest.mark.gpu
@@ -212,16 +213,6 @@ def test_forced_routes_on_the_batch(monkeypatch, prec, forced):
 
 # ---- 4. problems that stop apart ---------------------------------------------------------------------------------------------------
 STOP_SHAPE, STOP_CAP, STOP_TOL = (300, 700, 17), 40, 1.0
-
-
-def stop_rule(losses, tol_abs):
-    """n_done of nmf.py:214-220 on a loss record computed without the rule; len(losses) if it never fires."""
-    prev = np.inf
-    for i, e in enumerate(losses):
-        if prev - e < tol_abs:
-            return i
-        prev = e
-    return len(losses)
 
 
 @pytest.mark.parametrize('prec', PRECS)
