@@ -22,7 +22,8 @@ extern "C" {
  * (KLNMF_Q_EX_ROW_CHUNKS / _W_CHUNKS) equal the batch's.  The batch's counts are the single problem's plan for
  * max(1, cu_count / count) compute units: klnmf_plan_query(precision, n, f, k, -1, max(1, cu_count / count), ...); the
  * development switches KLNMF_EX_ROW_CHUNKS / _W_CHUNKS / _H_SEG force them as they force a context's.  A batch is a type of its
- * own: neither a mode of klnmf_ctx nor a klnmf_group.  Used from one thread at a time; it owns its stream. */
+ * own: neither a mode of klnmf_ctx nor a klnmf_group.  Used from one thread at a time; it owns its stream.  (Row x modality
+ * presence masks on the problems of a batch: klnmf_batch_mask.h.) */
 typedef struct klnmf_batch klnmf_batch;
 #define KLNMF_BATCH_MAX 256
 /* KLNMF_ERR_UNSUPP for every precision but KLNMF_PREC_F64 / F32 (nothing is created), KLNMF_ERR_ARG unless 1 <= count <=
@@ -55,8 +56,9 @@ int klnmf_batch_result(klnmf_batch *b, int p, double *errors_out, int64_t *n_don
 int klnmf_batch_get_W(klnmf_batch *b, int p, void *dst, int dtype);
 int klnmf_batch_get_H(klnmf_batch *b, int p, void *dst, int dtype);
 int klnmf_batch_get_W_device(klnmf_batch *b, int p, void *ddst, int dtype, int64_t ld);
-/* KLNMF_Q_EX_ROW_CHUNKS / _W_CHUNKS / _H_SEGMENTS / _H_FROM_SLABS of the batch's plan (0 with no problem), and
- * KLNMF_Q_BATCH_COUNT: the count the batch was created with.  Replaces nothing of the reference. */
+/* KLNMF_Q_EX_ROW_CHUNKS / _W_CHUNKS / _H_SEGMENTS / _H_FROM_SLABS of the batch's plan (0 with no problem),
+ * KLNMF_Q_BATCH_COUNT: the count the batch was created with, and KLNMF_Q_PRESENCE: the modalities of the batch's presence masks
+ * (klnmf_batch_mask.h), 0 without one.  Replaces nothing of the reference. */
 #define KLNMF_Q_BATCH_COUNT       22
 int klnmf_batch_query(klnmf_batch *b, int what, int64_t *value);
 

@@ -163,6 +163,16 @@ BATCH_SIGNATURES = {
     'klnmf_batch_query': (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_i64)]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/klnmf_batch_mask.h (presence masks on batches), which the same
+# library exports
+BATCH_MASK_SIGNATURES = {
+    'klnmf_batch_upload_presence': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _i64, _i64, _i64, _c.POINTER(_i64),
+                                               _c.c_int]),
+    'klnmf_batch_upload_presence_device_rows': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _i64, _i64, _c.c_void_p, _i64,
+                                                           _i64, _c.POINTER(_c.c_int), _c.POINTER(_i64), _c.c_int]),
+    'klnmf_batch_clear_presence': (_c.c_int, [_c.c_void_p]),
+}
+
 _lib = None
 
 
@@ -186,7 +196,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(BATCH_MASK_SIGNATURES.items()):
         fn = getattr(lib, name)     # AttributeError if a symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -893,10 +903,11 @@ class Group(object):
 
 
 class Batch(object):
-    """klnmf_batch_*: `count` dense, unweighted problems of one shape (n, f, k) in 'f64' / 'f32' on one device that run the
-    multiplicative-update loop together, every stage of an iteration one launch for all of them.  Each problem `p` keeps its
-    own V, W, H, loss record and stop state; its results are bit for bit those of the same problem alone in a `Context` whose
-    chunk counts equal the batch's (`exact_regime()`).  The methods mirror `Context`'s with the problem index in front."""
+    """klnmf_batch_*: `count` dense problems of one shape (n, f, k) in 'f64' / 'f32' on one device -- unweighted, or all of them
+    under presence masks that share their column bounds (`upload_presence`) -- that run the multiplicative-update loop together,
+    every stage of an iteration one launch for all of them.  Each problem `p` keeps its own V, W, H, mask, loss record and stop
+    state; its results are bit for bit those of the same problem alone in a `Context` whose chunk counts equal the batch's
+    (`exact_regime()`).  The methods mirror `Context`'s with the problem index in front."""
 
     def __init__(self, precision, count, device=0):
         self._lib = load()
@@ -950,6 +961,45 @@ class Batch(object):
         _check(self._lib.klnmf_batch_upload_V_device_rows_dt(self._h, int(p), _c.c_void_p(dev_ptr), DT_F64 if f64 else DT_F32,
                                                              _c.c_void_p(row_idx_ptr) if row_idx_ptr else None, int(rows), int(cols),
                                                              int(ld), int(row0), int(col0), float(scale)))
+
+    def upload_presence(self, p, P, col_bounds, row0=0):
+        """`Context.upload_presence` for problem p (klnmf_batch_upload_presence).  The first call on a batch fixes `col_bounds` for
+        every problem and makes the whole batch masked, every entry not uploaded equal to 1."""
+        a = np.asarray(P)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.ndim != 2:
+            raise ValueError("2-D presence matrix expected")
+        bounds = [int(b) for b in col_bounds]
+        if a.shape[1] != len(bounds) - 1:
+            raise ValueError("presence matrix of %d columns for %d modalities" % (a.shape[1], len(bounds) - 1))
+        if a.strides[1] != a.itemsize or a.strides[0] % a.itemsize or a.strides[0] < a.shape[1] * a.itemsize:
+            a = np.ascontiguousarray(a)
+        ld = a.strides[0] // a.itemsize
+        cb = (_i64 * len(bounds))(*bounds)
+        _check(self._lib.klnmf_batch_upload_presence(self._h, int(p), a.ctypes.data, _np_dtype_code(a), a.shape[0], ld, int(row0), cb,
+                                                     len(bounds) - 1))
+
+    def upload_presence_device_rows(self, p, dev_ptr, f64, src_rows, ld, row_idx_ptr, rows, src_cols, col_bounds, row0=0):
+        """`Context.upload_presence_device_rows` for problem p (klnmf_batch_upload_presence_device_rows): synchronous."""
+        bounds = [int(b) for b in col_bounds]
+        cols = [int(v) for v in src_cols]
+        if len(cols) != len(bounds) - 1:
+            raise ValueError("%d source columns for %d modalities" % (len(cols), len(bounds) - 1))
+        cb = (_i64 * len(bounds))(*bounds)
+        sc = (_c.c_int * max(1, len(cols)))(*cols)
+        _check(self._lib.klnmf_batch_upload_presence_device_rows(self._h, int(p), _c.c_void_p(dev_ptr) if dev_ptr else None,
+                                                                 DT_F64 if f64 else DT_F32, int(src_rows), int(ld),
+                                                                 _c.c_void_p(row_idx_ptr) if row_idx_ptr else None, int(rows), int(row0),
+                                                                 sc, cb, len(cols)))
+
+    def clear_presence(self):
+        """The batch runs the unmasked kernels again (klnmf_batch_clear_presence)."""
+        _check(self._lib.klnmf_batch_clear_presence(self._h))
+
+    def presence(self):
+        """Modalities of the batch's presence masks (klnmf_batch_query KLNMF_Q_PRESENCE); 0 without one."""
+        return self.query(Q_PRESENCE)
 
     def set_H(self, p, H):
         H = _as_float_array(H)

@@ -1,5 +1,5 @@
-// Batched forms of the dense exact loop's kernels (exact.hip.h): B unweighted problems of one shape (n, f, k) advance through
-// the loop of nmf.py:212-222 together, every stage ONE launch with the problem index on the grid.
+// Batched forms of the dense exact loop's kernels (exact.hip.h): B unweighted -- or B masked (presence.hip.h) -- problems of one
+// shape (n, f, k) advance through the loop of nmf.py:212-222 together, every stage ONE launch with the problem index on the grid.
 //
 //   k_gemm_batch<.., EpiQ / EpiW / EpiWpart / EpiN>   the four contractions: k_gemm's tile loop (gemm_body.hip.h), the same epilogues;
 //                                                     problem p = blockIdx.y / (row tiles of one problem)
@@ -8,6 +8,12 @@
 //   k_sum_partials_batch                              the H numerator from the row chunks' slabs            nmf.py:349
 //   k_update_H_batch / _part_batch / _norm_batch      the H rule: from slabs, from sums, in segments        nmf.py:349-350
 // (the dense loop transposes nothing: a transposed operand of the tile loop is a stride swap)
+// A masked batch -- every problem its own presence matrix P, one set of column bounds for all -- runs the same kernels under
+// presence.hip.h's policies (EpiQ<T, PresenceWeight>, FacPresW, FacPresH: at_problem / fac_at_problem move their pointers) and
+//   k_presence_S_batch                                S of every problem from its H, grid (k, M, B)
+//   k_presence_D_part_batch / k_presence_D_sum_batch  D = W_new^T.P of every problem, grid (ceil(k / 64), presence_d_chunks(n), B)
+// which are the single problem's kernels' own text (presence_body.hip.h) on problem p's buffers:
+// P [B][n][M], S [B][M][k], D [B][k][M], D's slabs [B][chunks][k][M] in double; bounds and the modality bytes once per batch.
 //
 // Layout: every buffer of the single problem, B times, problem p at p x (the single problem's element count) -- V, Q, W[2], H,
 // the slabs [B][chunks][..], loss partials [B][tiles], DevState [B], loss records [B][cap].
@@ -16,7 +22,7 @@
 // Stop state: one DevState per problem; the blocks of a stopped problem return at their first instruction, as every block of a
 // stopped context does, and nothing waits on anything.
 #pragma once
-#include "exact.hip.h"
+#include "presence.hip.h"
 
 namespace klnmf {
 
@@ -32,6 +38,33 @@ template <typename T, typename Fac>
 __device__ __forceinline__ EpiW<T, Fac> at_problem(EpiW<T, Fac> e, int p, int M, int N) {
     const int64_t o = (int64_t)p * M * N;
     e.Wold += o; e.Wnew += o;
+    return e;
+}
+// the masked policies: P [n][nmod] and S [nmod][k] / D [k][nmod] of problem p
+template <typename T>
+__device__ __forceinline__ EpiQ<T, PresenceWeight<T>> at_problem(EpiQ<T, PresenceWeight<T>> e, int p, int M, int N) {
+    const int64_t o = (int64_t)p * M * N;
+    e.V += o; e.Q += o;
+    e.wt.P += (int64_t)p * M * e.wt.nmod;
+    return e;
+}
+// (a policy without pointers of its own -- FacNum, FacW0 -- is the same for every problem: itself, by reference)
+template <typename Fac> __device__ __forceinline__ const Fac &fac_at_problem(const Fac &fac, int, int64_t, int64_t) { return fac; }
+template <typename T>
+__device__ __forceinline__ FacPresW<T> fac_at_problem(FacPresW<T> fac, int p, int64_t n, int64_t k) {
+    fac.P += (int64_t)p * n * fac.nmod; fac.Sm += (int64_t)p * fac.nmod * k;
+    return fac;
+}
+template <typename T>
+__device__ __forceinline__ FacPresH<T> fac_at_problem(FacPresH<T> fac, int p, int64_t, int64_t k) {
+    fac.D += (int64_t)p * k * fac.nmod;
+    return fac;
+}
+template <typename T>
+__device__ __forceinline__ EpiW<T, FacPresW<T>> at_problem(EpiW<T, FacPresW<T>> e, int p, int M, int N) {
+    const int64_t o = (int64_t)p * M * N;
+    e.Wold += o; e.Wnew += o;
+    e.fac = fac_at_problem(e.fac, p, (int64_t)M, (int64_t)N);
     return e;
 }
 template <typename T>
@@ -87,6 +120,7 @@ __global__ void k_wrule_batch(NumSlabs<T, Fac::S> part, const DevState *st, EpiW
     if (st[p].stop) return;
     const NumSlabs<T, Fac::S> mine = part.at((int64_t)p * part.nslab * part.slab);
     epi.Wold += p * part.slab; epi.Wnew += p * part.slab;
+    epi.fac = fac_at_problem(epi.fac, p, part.slab / epi.k, epi.k);      // (FacW0: itself)
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < part.slab; e += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = e / epi.k;
         epi.rule(e, r, e - r * epi.k, mine.get(e));
@@ -108,16 +142,17 @@ __global__ void k_sum_partials_batch(NumArray<T, 1> part, T *out, int64_t count,
 template <typename T> __device__ __forceinline__ int64_t problem_stride(const NumArray<T, 1> &, int64_t kf) { return kf; }
 template <typename T> __device__ __forceinline__ int64_t problem_stride(const NumSlabs<T, 1> &s, int64_t) { return s.nslab * s.slab; }
 
-// k_update_H, grid (k, B)
-template <typename T, typename Num>
-__global__ __launch_bounds__(256) void k_update_H_batch(T *H, RuleIn<Num, FacNum> in, int64_t f, const DevState *st) {
+// k_update_H, grid (k, B); Fac: FacNum, or FacPresH with D [B][k][M]
+template <typename T, typename Num, typename Fac = FacNum>
+__global__ __launch_bounds__(256) void k_update_H_batch(T *H, RuleIn<Num, Fac> in, int64_t f, const DevState *st) {
     const int p = blockIdx.y;
     if (st[p].stop) return;
     __shared__ double red[16];
     __shared__ double total;
     const int64_t kf = (int64_t)gridDim.x * f;
     T *row = H + p * kf + blockIdx.x * f;
-    const double s = h_product(row, in.num.at(p * problem_stride(in.num, kf) + blockIdx.x * f), in.fac, (int64_t)blockIdx.x, 0, f);
+    const double s = h_product(row, in.num.at(p * problem_stride(in.num, kf) + blockIdx.x * f),
+                               fac_at_problem(in.fac, p, 0, (int64_t)gridDim.x), (int64_t)blockIdx.x, 0, f);
     const double t = block_sum(s, red);
     if (threadIdx.x == 0) total = t;
     __syncthreads();
@@ -126,14 +161,14 @@ __global__ __launch_bounds__(256) void k_update_H_batch(T *H, RuleIn<Num, FacNum
 }
 
 // k_update_H_part / k_update_H_norm, grid (segments, k, B); part [B][k][segments]
-template <typename T>
-__global__ __launch_bounds__(256) void k_update_H_part_batch(T *H, RuleIn<NumArray<T, 1>, FacNum> in, int64_t f, int64_t seg,
+template <typename T, typename Fac = FacNum>
+__global__ __launch_bounds__(256) void k_update_H_part_batch(T *H, RuleIn<NumArray<T, 1>, Fac> in, int64_t f, int64_t seg,
                                                              double *part, const DevState *st) {
     const int p = blockIdx.z;
     if (st[p].stop) return;
     __shared__ double red[16];
     const int64_t a = blockIdx.y, j0 = blockIdx.x * seg, j1 = min(f, j0 + seg), pa = (int64_t)p * gridDim.y + a;
-    const double s = h_product(H + pa * f, in.num.at(pa * f), in.fac, a, j0, j1);
+    const double s = h_product(H + pa * f, in.num.at(pa * f), fac_at_problem(in.fac, p, 0, (int64_t)gridDim.y), a, j0, j1);
     const double t = block_sum(s, red);
     if (threadIdx.x == 0) part[pa * gridDim.x + blockIdx.x] = t;
 }
@@ -147,6 +182,44 @@ __global__ __launch_bounds__(256) void k_update_H_norm_batch(T *H, int64_t f, in
     const T d = (T)(kEpsNorm + total);
     T *row = H + pa * f;
     for (int64_t j = j0 + threadIdx.x; j < j1; j += blockDim.x) row[j] = row[j] / d;
+}
+
+// ---- what only a masked batch runs: presence.hip.h's kernels (their text: presence_body.hip.h) on problem p's buffers ------------
+// k_presence_S, grid (k, M, B)
+template <typename T>
+__global__ __launch_bounds__(256) void k_presence_S_batch(const T *H0, const int64_t *bounds, T *S0, int64_t f, int64_t k, const DevState *st) {
+    const int p = blockIdx.z;
+    if (st[p].stop) return;
+    const T *H = H0 + p * k * f;
+    T *S = S0 + (int64_t)p * gridDim.y * k;
+#define KL_PRESENCE_BODY_S
+#include "presence_body.hip.h"
+#undef KL_PRESENCE_BODY_S
+}
+
+// k_presence_D_part, grid (ceil(k / 64), chunks, B); slabs [B][chunks][k][nmod]
+template <typename T>
+__global__ __launch_bounds__(256) void k_presence_D_part_batch(const T *W0, const T *P0, double *slab0, int64_t n, int64_t k, int nmod,
+                                                               int64_t chunk, const DevState *st) {
+    const int p = blockIdx.z;
+    if (st[p].stop) return;
+    const T *W = W0 + p * n * k, *P = P0 + p * n * nmod;
+    double *slab = slab0 + (int64_t)p * gridDim.y * k * nmod;
+#define KL_PRESENCE_BODY_D_PART
+#include "presence_body.hip.h"
+#undef KL_PRESENCE_BODY_D_PART
+}
+
+// k_presence_D_sum, grid (.., B); count = k nmod
+template <typename T>
+__global__ void k_presence_D_sum_batch(const double *slab0, int nslab, int64_t count, T *D0, const DevState *st) {
+    const int p = blockIdx.y;
+    if (st[p].stop) return;
+    const double *slab = slab0 + (int64_t)p * nslab * count;
+    T *D = D0 + p * count;
+#define KL_PRESENCE_BODY_D_SUM
+#include "presence_body.hip.h"
+#undef KL_PRESENCE_BODY_D_SUM
 }
 
 }  // namespace klnmf

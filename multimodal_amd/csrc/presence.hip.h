@@ -12,7 +12,8 @@
 //   k_presence_D_part / k_presence_D_sum   D = W_new^T.P over row chunks, slabs in double summed in a fixed order
 //   k_update_H / k_update_H_part under FacPresH   the H rule: factor = D > 0 ? num / D : 1
 // The ratio epilogue and the rules are the one family of exact.hip.h under the policies PresenceWeight, FacPresW and FacPresH; this
-// file holds them and what only a masked problem runs: k_presence_S, k_presence_D_part, k_presence_D_sum.
+// file holds them and what only a masked problem runs: k_presence_S, k_presence_D_part, k_presence_D_sum -- their bodies in
+// presence_body.hip.h, included as text here and in their batched forms (batch.hip.h), as gemm_body.hip.h is.
 // The mask itself comes from the host (klnmf_upload_presence: k_place_V on the n x M matrix) or from a mask resident in device
 // memory, gathered by row index and source column (klnmf_upload_presence_device_rows: k_presence_rows_check, k_presence_gather).
 // S and D are accumulated in double in a fixed order and rounded once to T (as the H rule's row sums are): two runs give the
@@ -45,14 +46,9 @@ struct PresenceWeight {
 template <typename T>
 __global__ __launch_bounds__(256) void k_presence_S(const T *H, const int64_t *bounds, T *S, int64_t f, int64_t k, const DevState *st) {
     if (st && st->stop) return;
-    __shared__ double red[16];
-    const int64_t a = blockIdx.x, m = blockIdx.y;
-    const int64_t j0 = bounds[m], j1 = bounds[m + 1];
-    const T *row = H + a * f;
-    double s = 0;
-    for (int64_t j = j0 + threadIdx.x; j < j1; j += blockDim.x) s += (double)row[j];
-    const double t = block_sum(s, red);
-    if (threadIdx.x == 0) S[m * k + a] = (T)t;
+#define KL_PRESENCE_BODY_S
+#include "presence_body.hip.h"      // (the block's work: shared with k_presence_S_batch)
+#undef KL_PRESENCE_BODY_S
 }
 
 // den = sum_m P[r][m] * S[m][c], m ascending, in T
@@ -88,44 +84,18 @@ template <typename T>
 __global__ __launch_bounds__(256) void k_presence_D_part(const T *W, const T *P, double *slab, int64_t n, int64_t k, int nmod,
                                                          int64_t chunk, const DevState *st) {
     if (st && st->stop) return;
-    __shared__ double red[3][kMaxMod][64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t a = (int64_t)blockIdx.x * 64 + lane;
-    const int64_t i0 = (int64_t)blockIdx.y * chunk, i1 = min(n, i0 + chunk);
-    double acc[kMaxMod];
-#pragma unroll
-    for (int m = 0; m < kMaxMod; ++m) acc[m] = 0.0;
-    if (a < k) {
-        for (int64_t i = i0 + wv; i < i1; i += 4) {
-            const double w = (double)W[i * k + a];
-            const T *prow = P + i * nmod;
-#pragma unroll
-            for (int m = 0; m < kMaxMod; ++m)
-                if (m < nmod) acc[m] += w * (double)prow[m];
-        }
-    }
-    if (wv > 0) {
-#pragma unroll
-        for (int m = 0; m < kMaxMod; ++m) red[wv - 1][m][lane] = acc[m];
-    }
-    __syncthreads();
-    if (wv == 0 && a < k) {
-        double *out = slab + ((int64_t)blockIdx.y * k + a) * nmod;
-#pragma unroll
-        for (int m = 0; m < kMaxMod; ++m)
-            if (m < nmod) out[m] = ((acc[m] + red[0][m][lane]) + red[1][m][lane]) + red[2][m][lane];
-    }
+#define KL_PRESENCE_BODY_D_PART
+#include "presence_body.hip.h"      // (the block's work: shared with k_presence_D_part_batch)
+#undef KL_PRESENCE_BODY_D_PART
 }
 
 // D[a][m] = the slabs' sum, chunk 0 first, rounded once to T
 template <typename T>
 __global__ void k_presence_D_sum(const double *slab, int nslab, int64_t count, T *D, const DevState *st) {
     if (st && st->stop) return;
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < count; e += (int64_t)gridDim.x * blockDim.x) {
-        double s = 0;
-        for (int z = 0; z < nslab; ++z) s += slab[z * count + e];
-        D[e] = (T)s;
-    }
+#define KL_PRESENCE_BODY_D_SUM
+#include "presence_body.hip.h"      // (shared with k_presence_D_sum_batch)
+#undef KL_PRESENCE_BODY_D_SUM
 }
 
 // The source column of every modality of one gather, passed by value (read through the kernel-argument segment: uniform loads, no

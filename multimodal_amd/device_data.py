@@ -196,14 +196,19 @@ class DeviceDataset(object):
                              % ', '.join('%d is' % w for w in which if self.sparse[w]))
         return True
 
-    def upload_presence(self, ctx, which, idx_ptr, n):
-        """The rows of the mask for the modalities `which` into the problem of `ctx`: gathered on the device by the row indices
-        at `idx_ptr` (`n` int64 in device memory), column `w` of the resident mask for a masked modality w, 1 for the others."""
+    def upload_presence(self, ctx, which, idx_ptr, n, p=None):
+        """The rows of the mask for the modalities `which` into the problem of `ctx` (p: into problem p of a `_native.Batch`):
+        gathered on the device by the row indices at `idx_ptr` (`n` int64 in device memory), column `w` of the resident mask for a
+        masked modality w, 1 for the others; the bounds are the selected modalities' widths."""
         bounds = [0]
         for w in which:
             bounds.append(bounds[-1] + self.dims[w])
-        ctx.upload_presence_device_rows(self.presence.data_ptr(), True, self.n_samples, self.presence.stride(0), idx_ptr, n,
-                                        [w if self.masked[w] else -1 for w in which], bounds)
+        args = (self.presence.data_ptr(), True, self.n_samples, self.presence.stride(0), idx_ptr, n,
+                [w if self.masked[w] else -1 for w in which], bounds)
+        if p is None:
+            ctx.upload_presence_device_rows(*args)
+        else:
+            ctx.upload_presence_device_rows(p, *args)
 
     def sparse_route(self, which):
         """The modalities `which` run the sparse branch: at least one of them is kept as CSR (`KLdivNMF._sparse_route`)."""
@@ -343,8 +348,9 @@ class DeviceDataset(object):
         return self.reconstruct_internal_multi(learner, [orig_mod], rows, iterations)
 
     # ---- the same calls for the runs of a sweep that share a shape: one batch (klnmf_batch_*, csrc/batch.hip.h) ----
-    def _batch_uploads(self, which, rows_list, coefs_list):
-        """One `upload(batch, p)` per row list: the rows of the dense modalities `which` into problem p of a `_native.Batch`."""
+    def _batch_uploads(self, which, rows_list, coefs_list, masked=False):
+        """One `upload(batch, p)` per row list: the rows of the dense modalities `which` into problem p of a `_native.Batch`;
+        masked: and problem p's rows of the resident presence mask behind them (`upload_presence`)."""
         uploads = []
         for rows, coefs in zip(rows_list, coefs_list):
             rows = np.ascontiguousarray(rows, dtype=np.int64)
@@ -358,20 +364,28 @@ class DeviceDataset(object):
                     batch.upload_V_device_rows_dt(p, b.data_ptr(), f64, idx.data_ptr(), idx.numel(), b.shape[1], b.stride(0),
                                                   row0=0, col0=col, scale=c)
                     col += b.shape[1]
+                if masked:
+                    self.upload_presence(batch, which, idx.data_ptr(), idx.numel(), p=p)
                 self._synchronize()      # the batch runs on its own stream; idx must outlive the kernel
             uploads.append(upload)
         return uploads
 
     def _batch_route(self, which, rows_list, nmfs, n_features):
-        """'f64' / 'f32' if the calls on `rows_list` can run as one batch: row lists of one length, dense unmasked modalities, models
-        that `batch_precision` accepts.  None: the loop over the single calls."""
-        if not nmfs or len(set(len(r) for r in rows_list)) != 1 or self.presence_route(which) or self.sparse_route(which):
+        """'f64' / 'f32' if the calls on `rows_list` can run as one batch: row lists of one length, dense modalities -- masked ones
+        included: the batch is then the masked one, `presence_route(which)`, in `weighted_precision`'s arithmetic as the single masked
+        call -- and models that `batch_precision` accepts.  None: the loop over the single calls.  ValueError for a masked
+        selection that includes a CSR modality (`presence_route`)."""
+        if not nmfs or len(set(len(r) for r in rows_list)) != 1:
             return None
-        return batch_precision(nmfs, len(rows_list[0]), n_features)
+        masked = self.presence_route(which)
+        if self.sparse_route(which):
+            return None
+        return batch_precision(nmfs, len(rows_list[0]), n_features, weighted=masked)
 
     def train_many(self, learners, rows_list, iterations, init_dictionaries=None):
         """[self.train(l, rows, iterations, init) for l, rows, init in ...] -- as ONE batch where all row lists have one length,
-        all learners share k and no modality is masked or kept as CSR; the loop over `train` otherwise."""
+        all learners share k and no modality is kept as CSR; the loop over `train` otherwise.  With a presence mask on the
+        dataset the batch is the masked one: `last_weights_route` 'presence' here and on every `learner.nmf_train`."""
         learners, rows_list = list(learners), [list(r) for r in rows_list]
         inits = list(init_dictionaries) if init_dictionaries is not None else [None] * len(learners)
         which = list(range(len(self.blocks)))
@@ -385,9 +399,11 @@ class DeviceDataset(object):
         prec = self._batch_route(which, rows_list, nmfs, sum(self.dims)) if plain else None
         if prec is None:
             return [self.train(l, rows, iterations, init_dictionary=init) for l, rows, init in zip(learners, rows_list, inits)]
-        uploads = self._batch_uploads(which, rows_list, [list(l.coef) for l in learners])
-        fit_uploaded_batch(nmfs, prec, len(rows_list[0]), sum(self.dims), uploads, [lambda H: np.float64] * len(nmfs), _fit=True)
-        self.last_weights_route = None
+        masked = self.presence_route(which)
+        uploads = self._batch_uploads(which, rows_list, [list(l.coef) for l in learners], masked)
+        fit_uploaded_batch(nmfs, prec, len(rows_list[0]), sum(self.dims), uploads, [lambda H: np.float64] * len(nmfs), _fit=True,
+                           masked=masked)
+        self.last_weights_route = 'presence' if masked else None
         for learner, nmf in zip(learners, nmfs):
             learner.nmf_train = nmf
             learner.dico = nmf.components_
@@ -412,9 +428,11 @@ class DeviceDataset(object):
         prec = self._batch_route(which, rows_list, nmfs, n_features) if same else None
         if prec is None:
             return [self.reconstruct_internal_multi(l, orig_mods, rows, iterations) for l, rows in zip(learners, rows_list)]
-        uploads = self._batch_uploads(which, rows_list, [[l.coef[w] for w in which] for l in learners])
-        out = fit_uploaded_batch(nmfs, prec, len(rows_list[0]), n_features, uploads, [lambda H: np.float64] * len(nmfs), _fit=False)
-        self.last_weights_route = None
+        masked = self.presence_route(which)
+        uploads = self._batch_uploads(which, rows_list, [[l.coef[w] for w in which] for l in learners], masked)
+        out = fit_uploaded_batch(nmfs, prec, len(rows_list[0]), n_features, uploads, [lambda H: np.float64] * len(nmfs), _fit=False,
+                                 masked=masked)
+        self.last_weights_route = 'presence' if masked else None
         return out
 
 
@@ -484,9 +502,10 @@ class DeviceEvaluation(object):
     @staticmethod
     def internal_many(evaluations, mods, rows_list):
         """[ev.internal(mods, rows) for ev, rows in ...] for the evaluations of a sweep's runs -- as ONE batch where they share the
-        dataset, k, the iteration count and the number of rows, no selected modality is masked or kept as CSR and the shape
-        runs in f64 / f32: the dictionaries go in by klnmf_batch_set_H_device, the coefficients stay on the device
-        (klnmf_batch_get_W_device).  The loop over `internal` otherwise."""
+        dataset, k, the iteration count and the number of rows, no selected modality is kept as CSR and the shape runs in
+        f64 / f32 (a masked selection: the masked batch, `last_weights_route` 'presence' on every evaluation): the dictionaries go
+        in by klnmf_batch_set_H_device, the coefficients stay on the device (klnmf_batch_get_W_device).  The loop over `internal`
+        otherwise."""
         evaluations, rows_list = list(evaluations), list(rows_list)
         if not evaluations:
             return []
@@ -500,6 +519,7 @@ class DeviceEvaluation(object):
         prec = ds._batch_route(which, rows_list, models, f) if same else None
         if prec is None:
             return [ev.internal(mods, rows) for ev, rows in zip(evaluations, rows_list)]
+        masked = ds.presence_route(which)
         idxs = [ev._rows(rows) for ev, rows in zip(evaluations, rows_list)]
         outs = [torch.empty((n, ev.k), dtype=torch.float64, device=ev.dev) for ev in evaluations]
         with _native.Batch(prec, len(evaluations), device=models[0].device) as batch:
@@ -511,8 +531,10 @@ class DeviceEvaluation(object):
                     batch.upload_V_device_rows_dt(p, b.data_ptr(), f64, idx.data_ptr(), n, b.shape[1], b.stride(0), row0=0, col0=col,
                                                   scale=ev.learner.coef[w])
                     col += b.shape[1]
+                if masked:
+                    ds.upload_presence(batch, which, idx.data_ptr(), n, p=p)
                 ev._set_dictionary(batch, which, p)
-                ev.last_weights_route = None
+                ev.last_weights_route = models[p].last_weights_route = 'presence' if masked else None
             ds._synchronize()                              # the batch runs on its own stream; the indices must outlive the kernels
             batch.init_W()                                 # W0 = X . H^T with the dictionary itself (nmf.py:156, 283)
             batch.run(first.iter_test, False, 0.0)

@@ -317,8 +317,9 @@ def run_sweep(data_matrices, labels, modalities, ks, n_runs, iter_train=50, iter
     process starts): the runs' fits and transforms on masked modalities minimise the masked cost.  The default coefficients
     stay 1 / the mean row sum over all samples, absent ones included.
     batch: each worker runs its (k, run) pairs of equal k in batches of at most `batch` (`sweep_batches`): the trainings and the
-    evaluations' internal transforms of a batch as one launch sequence (klnmf_batch_*) where the shapes allow it (dense, unmasked
-    modalities, f64 / f32); 1 (default): one pair after another, as before."""
+    evaluations' internal transforms of a batch as one launch sequence (klnmf_batch_*) where the shapes allow it (dense
+    modalities, f64 / f32; with `presence`: the masked batch, every run its own rows of the mask); 1 (default): one pair after
+    another, as before."""
     import torch
     if keep_sparse:
         data = [m.tocsr() if hasattr(m, 'tocsr') else np.asarray(m) for m in data_matrices]

@@ -785,23 +785,27 @@ def _exact_loop_report(precision, device):
     return copy.deepcopy(_EXACT_LOOP_REPORT[key])
 
 
-def batch_precision(models, n, f):
+def batch_precision(models, n, f, weighted=False):
     """'f64' / 'f32' if `models` can run as ONE batch of dense n x f problems (klnmf_batch_*): they agree in n_components, tol,
     max_iter and precision, that precision resolves to f64 or f32 for the shape (`resolve_precision`), and every model is on
-    one and the same single device.  None otherwise."""
+    one and the same single device.  None otherwise.  weighted: a batch of masked problems -- the arithmetic is
+    `weighted_precision`'s, which is what the single masked call runs in ('auto' -> f64, the 16-bit modes -> f32)."""
     first = models[0]
     same = all((m.n_components, m.tol, m.max_iter, m.precision, m.devices) ==
                (first.n_components, first.tol, first.max_iter, first.precision, first.devices) for m in models)
     if not same or len(first.devices) != 1 or not 1 <= len(models) <= _native.BATCH_MAX:
         return None
+    if weighted:
+        return weighted_precision(first.precision)
     prec = resolve_precision(first.precision, n, f, first.n_components or f)
     return prec if _native.PRECISIONS[prec] in (_native.PREC_F64, _native.PREC_F32) else None
 
 
-def fit_uploaded_batch(models, precision, n_samples, n_features, uploads, out_dtype_ofs, _fit=True, return_errors=False):
-    """`KLdivNMF._fit_uploaded` for len(models) dense, unweighted problems of one shape as one `_native.Batch`: problem p is
-    placed by `uploads[p](batch, p)`; model p ends as its own `_fit_uploaded` would leave it, with `last_batch_size` set.
-    Returns the list of the calls' results."""
+def fit_uploaded_batch(models, precision, n_samples, n_features, uploads, out_dtype_ofs, _fit=True, return_errors=False, masked=False):
+    """`KLdivNMF._fit_uploaded` for len(models) dense problems of one shape as one `_native.Batch`: problem p is placed by
+    `uploads[p](batch, p)`; model p ends as its own `_fit_uploaded` would leave it, with `last_batch_size` set.  masked: the
+    uploads place a presence mask behind every V (`Batch.upload_presence*`, one set of bounds) and the loop is the masked one;
+    every model ends with `last_weights_route` 'presence' (None otherwise).  Returns the list of the calls' results."""
     B = len(models)
     max_iter = int(models[0].max_iter)
     H_inits = []
@@ -830,6 +834,7 @@ def fit_uploaded_batch(models, precision, n_samples, n_features, uploads, out_dt
             m.last_fp8_report = _exact_loop_report(precision, m.device)
             m.last_fp8_report['outside_f16_envelope'] = None      # (`_check_f16_envelope`: not a 16-bit loop)
             m.last_batch_size = B
+            m.last_weights_route = 'presence' if masked else None
             W = batch.get_W(p, dtype=out_dtype)
             if _fit and n_done > 0:
                 m.components_ = batch.get_H(p, dtype=out_dtype)
@@ -840,25 +845,37 @@ def fit_uploaded_batch(models, precision, n_samples, n_features, uploads, out_dt
     return outs
 
 
-def fit_transform_batch(models, Xs, _fit=True, return_errors=False):
-    """[models[i].fit_transform(Xs[i], _fit=_fit, return_errors=return_errors) for i ...] -- the independent fits of a sweep
-    (samples/launcher.py:68-99) -- as ONE batch where that is possible: all Xs dense and of one shape, the models as
-    `batch_precision` asks.  Every stage of an iteration is then one launch for all problems (csrc/batch.hip.h); each model
-    stops on its own loss record.  Otherwise the models run one after another through `fit_transform`, unchanged.  Each model
-    gets `last_batch_size`: the batch's size, or 1.  The initial dictionaries are drawn in list order (or taken from
+def fit_transform_batch(models, Xs, weights=None, _fit=True, return_errors=False):
+    """[models[i].fit_transform(Xs[i], weights=weights[i], _fit=_fit, return_errors=return_errors) for i ...] -- the independent
+    fits of a sweep (samples/launcher.py:68-99) -- as ONE batch where that is possible: all Xs dense and of one shape, the models
+    as `batch_precision` asks, and `weights` (None, or one entry per model as `fit_transform` takes it) either without an array
+    -- every entry None or a scalar: the unweighted batch -- or every entry None / a scalar / an (n, 1) presence column
+    (`weights_route` 'presence'): the masked batch, a model without an array on a mask of ones.  Every stage of an iteration is
+    then one launch for all problems (csrc/batch.hip.h); each model stops on its own loss record.  Otherwise (an entry that
+    routes to 'array' among them) the models run one after another through `fit_transform`, unchanged.  Each model gets
+    `last_batch_size`: the batch's size, or 1.  The initial dictionaries are drawn in list order (or taken from
     `_init_dictionary`), so the global numpy stream is consumed exactly as by the sequential calls."""
     models, Xs = list(models), list(Xs)
     if len(models) != len(Xs):
         raise ValueError("fit_transform_batch: one X per model expected (%d models, %d Xs)" % (len(models), len(Xs)))
+    if weights is not None:
+        weights = list(weights)
+        if len(weights) != len(models):
+            raise ValueError("fit_transform_batch: one weights entry per model expected (%d models, %d entries)" % (len(models), len(weights)))
     dense = bool(Xs) and not any(sp.issparse(X) for X in Xs)
     if dense:
         Xs = [atleast2d_or_csr(X) for X in Xs]
         dense = len(set(X.shape for X in Xs)) == 1
-    precision = batch_precision(models, *Xs[0].shape) if dense else None
+    routes = [None] * len(models) if weights is None or not dense else [weights_route([w], [X]) for w, X in zip(weights, Xs)]
+    masked = 'presence' in routes
+    precision = batch_precision(models, *Xs[0].shape, weighted=masked) if dense and 'array' not in routes else None
     if precision is None:
         outs = []
-        for m, X in zip(models, Xs):
-            outs.append(m.fit_transform(X, _fit=_fit, return_errors=return_errors))
+        for i, (m, X) in enumerate(zip(models, Xs)):
+            if weights is None:
+                outs.append(m.fit_transform(X, _fit=_fit, return_errors=return_errors))
+            else:
+                outs.append(m.fit_transform(X, weights=weights[i], _fit=_fit, return_errors=return_errors))
             m.last_batch_size = 1
         return outs
     blocks = []
@@ -866,6 +883,15 @@ def fit_transform_batch(models, Xs, _fit=True, return_errors=False):
         check_non_negative(X, "NMF.fit")
         blocks.append(_dense(X))
     n, f = blocks[0].shape
-    uploads = [lambda batch, p, b=b: batch.upload_V(p, b) for b in blocks]
+    if masked:
+        # one presence column per problem (1 for a model without an array), one modality of all f columns: `_fit_blocks`'s form
+        Ps = [np.ones((n, 1)) if r is None else np.array(check_weights(w, (n, 1)), dtype=np.float64) for w, r in zip(weights, routes)]
+
+        def place(batch, p, b, P):
+            batch.upload_V(p, b)
+            batch.upload_presence(p, P, [0, f])
+        uploads = [lambda batch, p, b=b, P=P: place(batch, p, b, P) for b, P in zip(blocks, Ps)]
+    else:
+        uploads = [lambda batch, p, b=b: batch.upload_V(p, b) for b in blocks]
     out_dtype_ofs = [lambda H_init, b=b: _out_dtype(H_init, b) for b in blocks]
-    return fit_uploaded_batch(models, precision, n, f, uploads, out_dtype_ofs, _fit=_fit, return_errors=return_errors)
+    return fit_uploaded_batch(models, precision, n, f, uploads, out_dtype_ofs, _fit=_fit, return_errors=return_errors, masked=masked)
