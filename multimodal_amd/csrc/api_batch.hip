@@ -9,10 +9,8 @@
 #include "../../include/klnmf_batch_mask.h"
 #include "batch.hip.h"
 
-struct klnmf_batch {
-    int device = 0, prec = KLNMF_PREC_F64, cu_count = 256, count = 1;
-    hipStream_t stream = nullptr;
-    std::vector<std::pair<void *, size_t>> allocs;      // (block, size class) of the current problem's device blocks
+struct klnmf_batch : DeviceBlocks, PresenceState {
+    int prec = KLNMF_PREC_F64, cu_count = 256, count = 1;
     // ---- the current problem
     bool have_problem = false;
     ProblemPlan plan;
@@ -23,50 +21,13 @@ struct klnmf_batch {
     DevState *st = nullptr, *st_init = nullptr;         // [B]; st_init: the state every loop starts from
     double *errors = nullptr, *loss_xchg = nullptr, *loss_part = nullptr, *hpart = nullptr;
     void *V = nullptr, *Q = nullptr, *W[2] = {nullptr, nullptr}, *H = nullptr, *Npart = nullptr, *numer = nullptr, *Wpart = nullptr;
-    // ---- a masked batch (klnmf_batch_upload_presence*; batch.hip.h has the layout): every problem's P -- taken filled with 1 by the
-    // first upload --, S, D and D's slabs, and once per batch the bounds (host and device) and the per-column modality bytes.
-    // Dropped by klnmf_batch_clear_presence and with the problem
-    int pres_M = 0, pres_dchunks = 0;
-    int64_t pres_bounds[kMaxMod + 1] = {};
-    void *Pm = nullptr, *pres_S = nullptr, *pres_D = nullptr, *pres_Dslab = nullptr, *pres_dbounds = nullptr, *pres_mod = nullptr;
-    bool presence() const { return pres_M > 0; }
+    // (a masked batch: PresenceState, every problem's P, S, D and D's slabs and once per batch the bounds and the modality bytes --
+    // taken by the first klnmf_batch_upload_presence*, dropped by klnmf_batch_clear_presence and with the problem)
 
     size_t esize() const { return prec_esize(prec); }
-    void *dalloc(size_t bytes) {      // (klnmf_ctx::dalloc: the block cache of api_context.hip, zero-filled blocks)
-        if (bytes == 0) bytes = 16;
-        const size_t cls = DevBlockCache::size_class(bytes);
-        void *p = g_block_cache.take(device, cls);
-        if (!p) {
-            hipError_t e = hipMalloc(&p, cls);
-            if (e == hipErrorOutOfMemory) {
-                (void)hipGetLastError();
-                g_block_cache.flush(device);
-                e = hipMalloc(&p, cls);
-            }
-            HIPCHK(e);
-        }
-        allocs.push_back({p, cls});
-        HIPCHK(hipMemsetAsync(p, 0, bytes, stream));
-        return p;
-    }
-    void dfree(void *&p) {      // one block back (callers have synchronised the stream)
-        for (size_t i = 0; p && i < allocs.size(); ++i)
-            if (allocs[i].first == p) {
-                if (!g_block_cache.give(device, allocs[i].second, p)) (void)hipFree(p);
-                allocs.erase(allocs.begin() + (std::ptrdiff_t)i);
-                break;
-            }
-        p = nullptr;
-    }
-    void forget_presence() {      // (the blocks are gone or go with `allocs`)
-        Pm = pres_S = pres_D = pres_Dslab = pres_dbounds = pres_mod = nullptr;
-        pres_M = 0; pres_dchunks = 0;
-        std::fill(pres_bounds, pres_bounds + kMaxMod + 1, (int64_t)0);
-    }
+    MaskDims mask_dims() const { return {n, f, k, count, prec}; }
     void free_all() {      // (callers have synchronised the stream)
-        for (auto &a : allocs)
-            if (!g_block_cache.give(device, a.second, a.first)) (void)hipFree(a.first);
-        allocs.clear();
+        release_all();
         forget_presence();
         have_problem = false;
     }
@@ -86,9 +47,6 @@ void need_p(klnmf_batch *b, int p) {
     need_problem(b);
     if (p < 0 || p >= b->count) fail(KLNMF_ERR_ARG, "problem index " + std::to_string(p) + " outside the batch of " + std::to_string(b->count));
 }
-void check_dtype(int dtype) {
-    if (dtype != KLNMF_DT_F32 && dtype != KLNMF_DT_F64) fail(KLNMF_ERR_ARG, "dtype must be KLNMF_DT_F32 or KLNMF_DT_F64");
-}
 
 // fn<T>(b, ...) in the batch's element type
 #define BATCH_CALL(b, fn, ...)                                         \
@@ -97,17 +55,6 @@ void check_dtype(int dtype) {
         else fn<float>(b, ##__VA_ARGS__);                              \
     } while (0)
 
-// dst[rows, cols] (rows dld apart, type D by `d64`) = src[rows, cols] (rows sld apart, type by `s64`), on the device
-void copy_2d_any(klnmf_batch *b, void *dst, bool d64, int64_t dld, const void *src, bool s64, int64_t sld, int64_t rows, int64_t cols) {
-    if (rows * cols == 0) return;
-    const dim3 grid(grid_for(rows * cols, 256, 8192));
-#define KL_COPY(D, S) hipLaunchKernelGGL((k_copy_2d<D, S>), grid, dim3(256), 0, b->stream, (D *)dst, dld, (const S *)src, sld, rows, cols, 1.0)
-    if (d64) { if (s64) KL_COPY(double, double); else KL_COPY(double, float); }
-    else { if (s64) KL_COPY(float, double); else KL_COPY(float, float); }
-#undef KL_COPY
-    HIPCHK(hipGetLastError());
-}
-
 // a host matrix [rows, cols] into a device matrix of the batch's type, and back (klnmf_set_H / klnmf_get_W of a context)
 void set_matrix(klnmf_batch *b, void *dst, const void *src, int dtype, int64_t rows, int64_t cols) {
     const size_t bytes = (size_t)rows * cols * (dtype == KLNMF_DT_F64 ? 8 : 4);
@@ -115,7 +62,7 @@ void set_matrix(klnmf_batch *b, void *dst, const void *src, int dtype, int64_t r
     HIPCHK(hipMalloc(&d, bytes ? bytes : 16));
     try {
         HIPCHK(hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, b->stream));
-        copy_2d_any(b, dst, b->prec == KLNMF_PREC_F64, cols, d, dtype == KLNMF_DT_F64, cols, rows, cols);
+        copy_2d_any(b->stream, dst, b->prec == KLNMF_PREC_F64, cols, d, dtype == KLNMF_DT_F64, cols, rows, cols);
         HIPCHK(hipStreamSynchronize(b->stream));
     } catch (...) {
         (void)hipFree(d);
@@ -128,7 +75,7 @@ void get_matrix(klnmf_batch *b, void *dst, int dtype, const void *src, int64_t r
     void *d = nullptr;
     HIPCHK(hipMalloc(&d, bytes ? bytes : 16));
     try {
-        copy_2d_any(b, d, dtype == KLNMF_DT_F64, cols, src, b->prec == KLNMF_PREC_F64, cols, rows, cols);
+        copy_2d_any(b->stream, d, dtype == KLNMF_DT_F64, cols, src, b->prec == KLNMF_PREC_F64, cols, rows, cols);
         HIPCHK(hipMemcpyAsync(dst, d, bytes, hipMemcpyDeviceToHost, b->stream));
         HIPCHK(hipStreamSynchronize(b->stream));
     } catch (...) {
@@ -144,19 +91,9 @@ void *problem_ptr(const klnmf_batch *b, void *base, int p, int64_t elems) { retu
 void place_block(klnmf_batch *b, int p, const void *dsrc, int dtype, const int64_t *row_idx, int64_t rows, int64_t cols, int64_t ld,
                  int64_t row0, int64_t col0, double scale) {
     if (rows * cols == 0) return;
-    void *V = problem_ptr(b, b->V, p, b->n * b->f);
-    const dim3 grid(grid_for(rows * cols, 256, 8192));
-#define KL_PLACE(T, S) hipLaunchKernelGGL((k_place_V<T, S>), grid, dim3(256), 0, b->stream, (T *)V, b->f, (const S *)dsrc, rows, cols, ld, row0, col0, scale, row_idx)
-    if (b->prec == KLNMF_PREC_F64) { if (dtype == KLNMF_DT_F64) KL_PLACE(double, double); else KL_PLACE(double, float); }
-    else { if (dtype == KLNMF_DT_F64) KL_PLACE(float, double); else KL_PLACE(float, float); }
-#undef KL_PLACE
-    HIPCHK(hipGetLastError());
+    place_rows(b->stream, problem_ptr(b, b->V, p, b->n * b->f), b->prec == KLNMF_PREC_F64, b->f, dsrc, dtype == KLNMF_DT_F64, rows, cols, ld,
+               row0, col0, scale, row_idx);
     b->has_V[(size_t)p] = 1;
-}
-
-void check_block(const klnmf_batch *b, int64_t rows, int64_t cols, int64_t ld, int64_t row0, int64_t col0) {
-    if (rows < 0 || cols < 0 || row0 < 0 || col0 < 0 || row0 + rows > b->n || col0 + cols > b->f || ld < cols)
-        fail(KLNMF_ERR_ARG, "V block out of range");
 }
 
 void reset_states(klnmf_batch *b) {
@@ -355,58 +292,10 @@ void set_problem(klnmf_batch *b, int64_t n, int64_t f, int64_t k, int64_t cap) {
     b->have_problem = true;
 }
 
-// ---- presence masks (klnmf_batch_mask.h): presence_check_args / presence_take of api_context.hip for a batch -------------------
-// `rows_ok`: the caller's own part of "rows out of range" (the source's leading dimension).  Everything here is checked before
-// anything is taken or written: a refused call leaves the batch as it was.
-void batch_presence_check(klnmf_batch *b, const std::string &who, int64_t rows, int64_t row0, bool rows_ok, const int64_t *col_bounds,
-                          int n_mod) {
-    if (n_mod < 1 || n_mod > KLNMF_MAX_MODALITIES)
-        fail(KLNMF_ERR_ARG, who + ": 1 <= n_mod <= KLNMF_MAX_MODALITIES (" + std::to_string(KLNMF_MAX_MODALITIES) + ")");
-    if (!col_bounds) fail(KLNMF_ERR_ARG, who + ": null column bounds");
-    if (col_bounds[0] != 0 || col_bounds[n_mod] != b->f) fail(KLNMF_ERR_ARG, who + ": the column bounds must run from 0 to f");
-    for (int m = 0; m < n_mod; ++m)
-        if (col_bounds[m] >= col_bounds[m + 1]) fail(KLNMF_ERR_ARG, who + ": the column bounds must increase strictly");
-    if (rows < 0 || row0 < 0 || row0 + rows > b->n || !rows_ok) fail(KLNMF_ERR_ARG, who + ": rows out of range");
-    if (b->presence() && (n_mod != b->pres_M || !std::equal(col_bounds, col_bounds + n_mod + 1, b->pres_bounds)))
-        fail(KLNMF_ERR_ARG, who + ": the column bounds differ from the ones the batch's first upload fixed");
-}
-
-// The first mask upload of a batch: every problem's P filled with 1, S, D, D's slabs, and once for all the bounds and the
-// per-column modality bytes.  All or nothing; a batch that holds a mask already is left alone.
-void batch_presence_take(klnmf_batch *b, const int64_t *col_bounds, int n_mod) {
-    if (b->presence()) return;
-    const size_t es = b->esize(), B = (size_t)b->count;
-    const int64_t M = n_mod;
-    HIPCHK(hipStreamSynchronize(b->stream));
-    void *pm = nullptr, *S = nullptr, *D = nullptr, *Dslab = nullptr, *dbounds = nullptr, *mod = nullptr;
-    try {
-        const int dch = presence_d_chunks(b->n);
-        pm = b->dalloc(B * (size_t)(b->n * M) * es);
-        S = b->dalloc(B * (size_t)(M * b->k) * es);
-        D = b->dalloc(B * (size_t)(b->k * M) * es);
-        Dslab = b->dalloc(B * (size_t)dch * (size_t)(b->k * M) * sizeof(double));
-        dbounds = b->dalloc((size_t)(M + 1) * sizeof(int64_t));
-        mod = b->dalloc((size_t)b->f);
-        std::vector<unsigned char> modv((size_t)b->f);
-        for (int m = 0; m < n_mod; ++m) std::fill(modv.begin() + col_bounds[m], modv.begin() + col_bounds[m + 1], (unsigned char)m);
-        HIPCHK(hipMemcpyAsync(mod, modv.data(), modv.size(), hipMemcpyHostToDevice, b->stream));
-        HIPCHK(hipMemcpyAsync(dbounds, col_bounds, (size_t)(M + 1) * sizeof(int64_t), hipMemcpyHostToDevice, b->stream));
-        const int64_t count = (int64_t)B * b->n * M;
-        if (b->prec == KLNMF_PREC_F64)
-            hipLaunchKernelGGL((k_fill<double>), dim3(grid_for(count, 256, 8192)), dim3(256), 0, b->stream, (double *)pm, count, 1.0);
-        else
-            hipLaunchKernelGGL((k_fill<float>), dim3(grid_for(count, 256, 8192)), dim3(256), 0, b->stream, (float *)pm, count, 1.0f);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(b->stream));      // (the host images above are read by the copies until here)
-        b->pres_dchunks = dch;
-    } catch (...) {                     // all or nothing: a failed first upload leaves the batch without a mask
-        (void)hipStreamSynchronize(b->stream);
-        b->dfree(pm); b->dfree(S); b->dfree(D); b->dfree(Dslab); b->dfree(dbounds); b->dfree(mod);
-        throw;
-    }
-    b->Pm = pm; b->pres_S = S; b->pres_D = D; b->pres_Dslab = Dslab; b->pres_dbounds = dbounds; b->pres_mod = mod;
-    std::copy(col_bounds, col_bounds + n_mod + 1, b->pres_bounds);
-    b->pres_M = n_mod;
+// the shared argument checks of a mask upload (a batch holds no weights)
+void presence_check_all(klnmf_batch *b, const std::string &who, int64_t rows, int64_t row0, bool rows_ok, const int64_t *col_bounds, int n_mod) {
+    presence_check_args(who, b->mask_dims(), rows, row0, rows_ok, col_bounds, n_mod);
+    presence_check_bounds(*b, who, "batch", col_bounds, n_mod);
 }
 
 }  // namespace
@@ -465,26 +354,11 @@ int klnmf_batch_upload_V(klnmf_batch *b, int p, const void *src, int dtype, int6
         need_p(b, p);
         if (!src) fail(KLNMF_ERR_ARG, "null source");
         check_dtype(dtype);
-        check_block(b, rows, cols, ld, row0, col0);
+        check_block(b->n, b->f, rows, cols, ld, row0, col0);
         if (rows * cols == 0) return;
-        // through a bounded device staging buffer, as klnmf_upload_V
-        const size_t es = dtype == KLNMF_DT_F64 ? 8 : 4;
-        const int64_t rows_per = std::min(rows, std::max<int64_t>(1, (int64_t)((256ull << 20) / (es * (size_t)ld))));
-        void *d = nullptr;
-        HIPCHK(hipMalloc(&d, (size_t)rows_per * ld * es + 16));
-        try {
-            for (int64_t r0 = 0; r0 < rows; r0 += rows_per) {
-                const int64_t rr = std::min(rows_per, rows - r0);
-                HIPCHK(hipMemcpyAsync(d, (const char *)src + (size_t)r0 * ld * es, ((size_t)(rr - 1) * ld + cols) * es,
-                                      hipMemcpyHostToDevice, b->stream));
-                place_block(b, p, d, dtype, nullptr, rr, cols, ld, row0 + r0, col0, scale);
-                HIPCHK(hipStreamSynchronize(b->stream));
-            }
-        } catch (...) {
-            (void)hipFree(d);
-            throw;
-        }
-        (void)hipFree(d);
+        staged_upload(b->stream, src, dt_size(dtype), rows, cols, ld, [&](const void *d, int64_t r0, int64_t rr) {
+            place_block(b, p, d, dtype, nullptr, rr, cols, ld, row0 + r0, col0, scale);
+        });
     });
 }
 
@@ -494,7 +368,7 @@ int klnmf_batch_upload_V_device_rows_dt(klnmf_batch *b, int p, const void *dsrc,
         need_p(b, p);
         if (!dsrc) fail(KLNMF_ERR_ARG, "null source");
         check_dtype(dtype);
-        check_block(b, rows, cols, ld, row0, col0);
+        check_block(b->n, b->f, rows, cols, ld, row0, col0);
         place_block(b, p, dsrc, dtype, drow_idx, rows, cols, ld, row0, col0, scale);
     });
 }
@@ -516,7 +390,7 @@ int klnmf_batch_set_H_device(klnmf_batch *b, int p, const void *dsrc, int dtype,
         check_dtype(dtype);
         if (col0 < 0 || ncols < 0 || col0 + ncols > b->f || ld < ncols) fail(KLNMF_ERR_ARG, "klnmf_batch_set_H_device: column block out of range");
         char *H = (char *)problem_ptr(b, b->H, p, b->k * b->f) + (size_t)col0 * b->esize();
-        copy_2d_any(b, H, b->prec == KLNMF_PREC_F64, b->f, dsrc, dtype == KLNMF_DT_F64, ld, b->k, ncols);
+        copy_2d_any(b->stream, H, b->prec == KLNMF_PREC_F64, b->f, dsrc, dtype == KLNMF_DT_F64, ld, b->k, ncols);
         if (last) {
             HIPCHK(hipStreamSynchronize(b->stream));      // the caller's buffer may go away
             b->has_H[(size_t)p] = 1;
@@ -605,7 +479,7 @@ int klnmf_batch_get_W_device(klnmf_batch *b, int p, void *ddst, int dtype, int64
         if (!ddst) fail(KLNMF_ERR_ARG, "null destination");
         check_dtype(dtype);
         if (ld < b->k) fail(KLNMF_ERR_ARG, "klnmf_batch_get_W_device: row stride shorter than k");
-        copy_2d_any(b, ddst, dtype == KLNMF_DT_F64, ld, problem_ptr(b, b->W[b->cur], p, b->n * b->k), b->prec == KLNMF_PREC_F64, b->k, b->n, b->k);
+        copy_2d_any(b->stream, ddst, dtype == KLNMF_DT_F64, ld, problem_ptr(b, b->W[b->cur], p, b->n * b->k), b->prec == KLNMF_PREC_F64, b->k, b->n, b->k);
         HIPCHK(hipStreamSynchronize(b->stream));
     });
 }
@@ -624,7 +498,7 @@ int klnmf_batch_query(klnmf_batch *b, int what, int64_t *value) {
 }
 
 // ---- klnmf_batch_mask.h --------------------------------------------------------------------------------------------------------
-// klnmf_upload_presence for problem p: P_p[row0 + i, m] = src[i, m], cast and placed by k_place_V on problem p's n x M matrix
+// klnmf_upload_presence for problem p: P_p[row0 + i, m] = src[i, m]
 int klnmf_batch_upload_presence(klnmf_batch *b, int p, const void *src, int dtype, int64_t rows, int64_t ld, int64_t row0,
                                 const int64_t *col_bounds, int n_mod) {
     return guarded([&] {
@@ -632,41 +506,15 @@ int klnmf_batch_upload_presence(klnmf_batch *b, int p, const void *src, int dtyp
         const std::string who = "klnmf_batch_upload_presence";
         if (!src) fail(KLNMF_ERR_ARG, "null source");
         check_dtype(dtype);
-        batch_presence_check(b, who, rows, row0, ld >= n_mod, col_bounds, n_mod);
-        const int64_t M = n_mod;
-        batch_presence_take(b, col_bounds, n_mod);
+        presence_check_all(b, who, rows, row0, ld >= n_mod, col_bounds, n_mod);
+        presence_take(*b, *b, b->mask_dims(), col_bounds, n_mod);
         if (rows == 0) return;
-        const size_t ses = dtype == KLNMF_DT_F64 ? 8 : 4;
-        int64_t rows_per = (int64_t)((256ull << 20) / (ses * (size_t)ld));
-        rows_per = std::max<int64_t>(1, std::min(rows_per, rows));
-        void *P = problem_ptr(b, b->Pm, p, b->n * M);
-        void *d = nullptr;
-        HIPCHK(hipMalloc(&d, (size_t)rows_per * ld * ses + 16));
-        try {
-            for (int64_t r0 = 0; r0 < rows; r0 += rows_per) {
-                const int64_t rr = std::min(rows_per, rows - r0);
-                HIPCHK(hipMemcpyAsync(d, (const char *)src + (size_t)r0 * ld * ses, ((size_t)(rr - 1) * ld + M) * ses,
-                                      hipMemcpyHostToDevice, b->stream));
-                const int grid = grid_for(rr * M, 256, 8192);
-                const int64_t *no_idx = nullptr;
-#define KL_PLACE_P(T, S) hipLaunchKernelGGL((k_place_V<T, S>), dim3(grid), dim3(256), 0, b->stream, (T *)P, M, (const S *)d, rr, M, ld, \
-                                            row0 + r0, (int64_t)0, 1.0, no_idx)
-                if (b->prec == KLNMF_PREC_F64) { if (dtype == KLNMF_DT_F64) KL_PLACE_P(double, double); else KL_PLACE_P(double, float); }
-                else { if (dtype == KLNMF_DT_F64) KL_PLACE_P(float, double); else KL_PLACE_P(float, float); }
-#undef KL_PLACE_P
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipStreamSynchronize(b->stream));
-            }
-        } catch (...) {
-            (void)hipFree(d);
-            throw;
-        }
-        (void)hipFree(d);
+        presence_upload(*b, *b, b->mask_dims(), p, src, dtype, rows, ld, row0);
     });
 }
 
-// klnmf_upload_presence_device_rows for problem p: the row indices are checked on the device first (k_presence_rows_check); the host
-// reads the flag back, and only a clean flag takes the mask (a first upload) and launches the gather into problem p's P
+// klnmf_upload_presence_device_rows for problem p: only clean row indices take the mask (a first upload) and launch the gather into
+// problem p's P
 int klnmf_batch_upload_presence_device_rows(klnmf_batch *b, int p, const void *dP, int dtype, int64_t src_rows, int64_t ld,
                                             const int64_t *drow_idx, int64_t rows, int64_t row0, const int *src_cols,
                                             const int64_t *col_bounds, int n_mod) {
@@ -675,42 +523,17 @@ int klnmf_batch_upload_presence_device_rows(klnmf_batch *b, int p, const void *d
         const std::string who = "klnmf_batch_upload_presence_device_rows";
         if (!dP) fail(KLNMF_ERR_ARG, "null source");
         check_dtype(dtype);
-        batch_presence_check(b, who, rows, row0, ld >= 0 && src_rows >= 0 && (drow_idx || rows <= src_rows), col_bounds, n_mod);
+        presence_check_all(b, who, rows, row0, ld >= 0 && src_rows >= 0 && (drow_idx || rows <= src_rows), col_bounds, n_mod);
         if (!src_cols) fail(KLNMF_ERR_ARG, who + ": null source columns");
         PresenceCols cols{};
         for (int m = 0; m < n_mod; ++m) {
             if (src_cols[m] < -1 || src_cols[m] >= ld) fail(KLNMF_ERR_ARG, who + ": a source column outside [-1, ld)");
             cols.col[m] = src_cols[m];
         }
-        if (rows > 0 && drow_idx) {
-            void *flag = b->dalloc(sizeof(int64_t));      // (zero-filled)
-            int64_t bad = 0;
-            try {
-                hipLaunchKernelGGL(k_presence_rows_check, dim3(grid_for(rows, 256, kPresGatherMaxBlocks)), dim3(256), 0, b->stream, drow_idx,
-                                   rows, src_rows, (int64_t *)flag);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpyAsync(&bad, flag, sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
-                HIPCHK(hipStreamSynchronize(b->stream));
-            } catch (...) {
-                (void)hipStreamSynchronize(b->stream);
-                b->dfree(flag);
-                throw;
-            }
-            b->dfree(flag);
-            if (bad) fail(KLNMF_ERR_ARG, who + ": a row index outside [0, src_rows)");
-        }
-        batch_presence_take(b, col_bounds, n_mod);
+        if (rows > 0 && drow_idx) presence_rows_check(*b, who, drow_idx, rows, src_rows);
+        presence_take(*b, *b, b->mask_dims(), col_bounds, n_mod);
         if (rows == 0) return;
-        // every index is a source row, every column one of its ld, and row0 + rows <= n: the gather reads and writes in range
-        void *P = problem_ptr(b, b->Pm, p, b->n * n_mod);
-        const int grid = grid_for(rows, 256, kPresGatherMaxBlocks);
-#define KL_GATHER_P(T, S) hipLaunchKernelGGL((k_presence_gather<T, S>), dim3(grid), dim3(256), 0, b->stream, (T *)P, n_mod, (const S *)dP, ld, \
-                                             drow_idx, rows, row0, cols)
-        if (b->prec == KLNMF_PREC_F64) { if (dtype == KLNMF_DT_F64) KL_GATHER_P(double, double); else KL_GATHER_P(double, float); }
-        else { if (dtype == KLNMF_DT_F64) KL_GATHER_P(float, double); else KL_GATHER_P(float, float); }
-#undef KL_GATHER_P
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(b->stream));      // (dP and drow_idx are the caller's: free to go from here)
+        presence_gather(*b, *b, b->mask_dims(), p, dP, dtype, ld, drow_idx, rows, row0, cols);
     });
 }
 
@@ -718,10 +541,7 @@ int klnmf_batch_upload_presence_device_rows(klnmf_batch *b, int p, const void *d
 int klnmf_batch_clear_presence(klnmf_batch *b) {
     return guarded([&] {
         need_problem(b);
-        if (!b->presence()) return;
-        HIPCHK(hipStreamSynchronize(b->stream));
-        b->dfree(b->Pm); b->dfree(b->pres_S); b->dfree(b->pres_D); b->dfree(b->pres_Dslab); b->dfree(b->pres_dbounds); b->dfree(b->pres_mod);
-        b->forget_presence();
+        presence_drop(*b, *b);
     });
 }
 

@@ -41,67 +41,30 @@ void fill_v_tiles(klnmf_ctx *c, void *tiles, size_t bytes) {
 
 // ---------------------------------------------------------------- uploads ---
 // `om` (a weighted problem's weights, exact modes): the block goes to Om instead of V, and V's upload state is left alone
-template <typename S>
-void place_block(klnmf_ctx *c, const S *dsrc, int64_t rows, int64_t cols, int64_t ld, int64_t row0,
-                 int64_t col0, double scale, const int64_t *row_idx = nullptr, bool om = false) {
-    const int64_t total = rows * cols;
-    const int grid = grid_for(total, 256, 8192);
-    void *dst = om ? c->Om : c->V;
-    switch (c->prec) {
-        case KLNMF_PREC_F64:
-            hipLaunchKernelGGL((k_place_V<double, S>), dim3(grid), dim3(256), 0, c->stream,
-                               (double *)dst, c->f, dsrc, rows, cols, ld, row0, col0, scale, row_idx);
-            break;
-        case KLNMF_PREC_F32:
-        case KLNMF_PREC_BF16X3:
-        case KLNMF_PREC_F16X3:
-            hipLaunchKernelGGL((k_place_V<float, S>), dim3(grid), dim3(256), 0, c->stream,
-                               (float *)dst, c->f, dsrc, rows, cols, ld, row0, col0, scale, row_idx);
-            break;
-        default:
-            hipLaunchKernelGGL((k_tile_V<S>), dim3(grid), dim3(256), 0, c->stream,
-                               (_Float16 *)c->VtA, c->nrt, c->nct, dsrc, rows, cols,
-                               ld, row0, col0, scale * c->v_scale, c->st, row_idx, kEpsRatio * c->v_scale);
-            break;
+void place_block(klnmf_ctx *c, const void *dsrc, bool s64, int64_t rows, int64_t cols, int64_t ld, int64_t row0, int64_t col0,
+                 double scale, const int64_t *row_idx = nullptr, bool om = false) {
+    if (c->is_exact()) {
+        place_rows(c->stream, om ? c->Om : c->V, c->prec == KLNMF_PREC_F64, c->f, dsrc, s64, rows, cols, ld, row0, col0, scale, row_idx);
+    } else {
+        dispatch_type(s64, [&](auto st) {
+            typedef tag_t<decltype(st)> S;
+            hipLaunchKernelGGL((k_tile_V<S>), dim3(grid_for(rows * cols, 256, 8192)), dim3(256), 0, c->stream, (_Float16 *)c->VtA, c->nrt,
+                               c->nct, (const S *)dsrc, rows, cols, ld, row0, col0, scale * c->v_scale, c->st, row_idx,
+                               kEpsRatio * c->v_scale);
+        });
+        HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipGetLastError());
     if (om) return;
     c->v_uploaded = true;
     c->refusals_dirty = true;
 }
 
-// a host block [rows, cols] (leading dimension ld) into V (or Om) through a bounded device staging buffer
+// a host block [rows, cols] (leading dimension ld) into V (or Om) through the bounded staging buffer
 void upload_block(klnmf_ctx *c, const void *src, int dtype, int64_t rows, int64_t cols, int64_t ld, int64_t row0, int64_t col0,
                   double scale, bool om) {
-    const size_t es = dt_size(dtype);
-    int64_t rows_per = (int64_t)((256ull << 20) / (es * (size_t)ld));
-    if (rows_per < 1) rows_per = 1;
-    if (rows_per > rows) rows_per = rows;
-    void *d = nullptr;
-    HIPCHK(hipMalloc(&d, (size_t)rows_per * ld * es + 16));
-    try {
-        for (int64_t r0 = 0; r0 < rows; r0 += rows_per) {
-            const int64_t rr = std::min(rows_per, rows - r0);
-            const size_t bytes = ((size_t)(rr - 1) * ld + cols) * es;
-            HIPCHK(hipMemcpyAsync(d, (const char *)src + (size_t)r0 * ld * es, bytes,
-                                  hipMemcpyHostToDevice, c->stream));
-            if (dtype == KLNMF_DT_F64)
-                place_block<double>(c, (const double *)d, rr, cols, ld, row0 + r0, col0, scale, nullptr, om);
-            else
-                place_block<float>(c, (const float *)d, rr, cols, ld, row0 + r0, col0, scale, nullptr, om);
-            HIPCHK(hipStreamSynchronize(c->stream));
-        }
-    } catch (...) {
-        (void)hipFree(d);
-        throw;
-    }
-    (void)hipFree(d);
-}
-
-void check_block(klnmf_ctx *c, int64_t rows, int64_t cols, int64_t ld, int64_t row0, int64_t col0) {
-    if (rows < 0 || cols < 0 || row0 < 0 || col0 < 0 || row0 + rows > c->n || col0 + cols > c->f ||
-        ld < cols)
-        fail(KLNMF_ERR_ARG, "V block out of range");
+    staged_upload(c->stream, src, dt_size(dtype), rows, cols, ld, [&](const void *d, int64_t r0, int64_t rr) {
+        place_block(c, d, dtype == KLNMF_DT_F64, rr, cols, ld, row0 + r0, col0, scale, nullptr, om);
+    });
 }
 
 // dense [rows,cols] host array -> device array of the context's element type / padded fp32
@@ -109,24 +72,18 @@ void set_matrix(klnmf_ctx *c, const void *src, int dtype, int64_t rows, int64_t 
                 float *fast_dst, int64_t fast_ld, double mul = 1.0) {
     const int64_t count = rows * cols;
     void *d = stage_to_device(c, src, dtype, count);
-    const int grid = grid_for(count, 256, 8192);
+    const dim3 grid(grid_for(count, 256, 8192));
     if (c->is_exact()) {
-        if (c->prec == KLNMF_PREC_F64) {
-            if (dtype == KLNMF_DT_F64)
-                hipLaunchKernelGGL((k_convert<double, double>), dim3(grid), dim3(256), 0, c->stream, (double *)exact_dst, (const double *)d, count);
-            else
-                hipLaunchKernelGGL((k_convert<double, float>), dim3(grid), dim3(256), 0, c->stream, (double *)exact_dst, (const float *)d, count);
-        } else {
-            if (dtype == KLNMF_DT_F64)
-                hipLaunchKernelGGL((k_convert<float, double>), dim3(grid), dim3(256), 0, c->stream, (float *)exact_dst, (const double *)d, count);
-            else
-                hipLaunchKernelGGL((k_convert<float, float>), dim3(grid), dim3(256), 0, c->stream, (float *)exact_dst, (const float *)d, count);
-        }
+        dispatch_types(c->prec == KLNMF_PREC_F64, dtype == KLNMF_DT_F64, [&](auto dt, auto st) {
+            typedef tag_t<decltype(dt)> D;
+            typedef tag_t<decltype(st)> S;
+            hipLaunchKernelGGL((k_convert<D, S>), grid, dim3(256), 0, c->stream, (D *)exact_dst, (const S *)d, count);
+        });
     } else {
-        if (dtype == KLNMF_DT_F64)
-            hipLaunchKernelGGL((k_place_padded<double>), dim3(grid), dim3(256), 0, c->stream, fast_dst, fast_ld, (const double *)d, rows, cols, mul);
-        else
-            hipLaunchKernelGGL((k_place_padded<float>), dim3(grid), dim3(256), 0, c->stream, fast_dst, fast_ld, (const float *)d, rows, cols, mul);
+        dispatch_type(dtype == KLNMF_DT_F64, [&](auto st) {
+            typedef tag_t<decltype(st)> S;
+            hipLaunchKernelGGL((k_place_padded<S>), grid, dim3(256), 0, c->stream, fast_dst, fast_ld, (const S *)d, rows, cols, mul);
+        });
     }
     hipError_t e = hipGetLastError();
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -140,24 +97,18 @@ void get_matrix(klnmf_ctx *c, void *dst, int dtype, int64_t rows, int64_t cols, 
     void *d = nullptr;
     const size_t bytes = (size_t)count * dt_size(dtype);
     HIPCHK(hipMalloc(&d, bytes ? bytes : 16));
-    const int grid = grid_for(count, 256, 8192);
+    const dim3 grid(grid_for(count, 256, 8192));
     if (c->is_exact()) {
-        if (c->prec == KLNMF_PREC_F64) {
-            if (dtype == KLNMF_DT_F64)
-                hipLaunchKernelGGL((k_convert<double, double>), dim3(grid), dim3(256), 0, c->stream, (double *)d, (const double *)exact_src, count);
-            else
-                hipLaunchKernelGGL((k_convert<float, double>), dim3(grid), dim3(256), 0, c->stream, (float *)d, (const double *)exact_src, count);
-        } else {
-            if (dtype == KLNMF_DT_F64)
-                hipLaunchKernelGGL((k_convert<double, float>), dim3(grid), dim3(256), 0, c->stream, (double *)d, (const float *)exact_src, count);
-            else
-                hipLaunchKernelGGL((k_convert<float, float>), dim3(grid), dim3(256), 0, c->stream, (float *)d, (const float *)exact_src, count);
-        }
+        dispatch_types(dtype == KLNMF_DT_F64, c->prec == KLNMF_PREC_F64, [&](auto dt, auto st) {
+            typedef tag_t<decltype(dt)> D;
+            typedef tag_t<decltype(st)> S;
+            hipLaunchKernelGGL((k_convert<D, S>), grid, dim3(256), 0, c->stream, (D *)d, (const S *)exact_src, count);
+        });
     } else {
-        if (dtype == KLNMF_DT_F64)
-            hipLaunchKernelGGL((k_gather_padded<double>), dim3(grid), dim3(256), 0, c->stream, (double *)d, fast_src, fast_ld, rows, cols, mul);
-        else
-            hipLaunchKernelGGL((k_gather_padded<float>), dim3(grid), dim3(256), 0, c->stream, (float *)d, fast_src, fast_ld, rows, cols, mul);
+        dispatch_type(dtype == KLNMF_DT_F64, [&](auto dt) {
+            typedef tag_t<decltype(dt)> D;
+            hipLaunchKernelGGL((k_gather_padded<D>), grid, dim3(256), 0, c->stream, (D *)d, fast_src, fast_ld, rows, cols, mul);
+        });
     }
     hipError_t e = hipGetLastError();
     hipError_t e2 = hipMemcpyAsync(dst, d, bytes, hipMemcpyDeviceToHost, c->stream);
@@ -293,15 +244,6 @@ void set_problem(klnmf_ctx *c, int64_t n, int64_t f, int64_t k, int64_t cap, int
     c->have_problem = true;
 }
 
-// =============================================================== exports ===
-template <typename D, typename S>
-void copy_2d(klnmf_ctx *c, D *dst, int64_t dld, const S *src, int64_t sld, int64_t rows, int64_t cols, double mul = 1.0) {
-    if (rows * cols == 0) return;
-    hipLaunchKernelGGL((k_copy_2d<D, S>), dim3(grid_for(rows * cols, 256, 8192)), dim3(256), 0, c->stream, dst, dld, src, sld,
-                       rows, cols, mul);
-    HIPCHK(hipGetLastError());
-}
-
 }  // namespace
 
 namespace klnmf_host {
@@ -354,9 +296,8 @@ void measure_and_pack(klnmf_ctx *c, bool from_init) {
 }
 
 size_t dt_size(int dtype) {
-    if (dtype == KLNMF_DT_F32) return 4;
-    if (dtype == KLNMF_DT_F64) return 8;
-    fail(KLNMF_ERR_ARG, "unknown dtype");
+    check_dtype(dtype, "unknown dtype");
+    return dtype == KLNMF_DT_F64 ? 8 : 4;
 }
 
 // host [rows,cols] (dtype) -> device staging buffer; returns device pointer (freed by caller)
@@ -370,6 +311,146 @@ void *stage_to_device(klnmf_ctx *c, const void *src, int dtype, int64_t count) {
         fail(KLNMF_ERR_HIP, std::string("hipMemcpyAsync H2D: ") + hipGetErrorString(e));
     }
     return d;
+}
+
+// ---- what contexts and batches share (ctx.hip.h) -------------------------------------------------------------------------------
+void place_rows(hipStream_t stream, void *dst, bool d64, int64_t dld, const void *dsrc, bool s64, int64_t rows, int64_t cols, int64_t ld,
+                int64_t row0, int64_t col0, double scale, const int64_t *row_idx) {
+    const dim3 grid(grid_for(rows * cols, 256, 8192));
+    dispatch_types(d64, s64, [&](auto dt, auto st) {
+        typedef tag_t<decltype(dt)> T;
+        typedef tag_t<decltype(st)> S;
+        hipLaunchKernelGGL((k_place_V<T, S>), grid, dim3(256), 0, stream, (T *)dst, dld, (const S *)dsrc, rows, cols, ld, row0, col0, scale,
+                           row_idx);
+    });
+    HIPCHK(hipGetLastError());
+}
+
+void copy_2d_any(hipStream_t stream, void *dst, bool d64, int64_t dld, const void *src, bool s64, int64_t sld, int64_t rows, int64_t cols,
+                 double mul) {
+    if (rows * cols == 0) return;
+    const dim3 grid(grid_for(rows * cols, 256, 8192));
+    dispatch_types(d64, s64, [&](auto dt, auto st) {
+        typedef tag_t<decltype(dt)> D;
+        typedef tag_t<decltype(st)> S;
+        hipLaunchKernelGGL((k_copy_2d<D, S>), grid, dim3(256), 0, stream, (D *)dst, dld, (const S *)src, sld, rows, cols, mul);
+    });
+    HIPCHK(hipGetLastError());
+}
+
+void fill_ones(hipStream_t stream, void *dst, bool f64, int64_t count) {
+    dispatch_type(f64, [&](auto t) {
+        typedef tag_t<decltype(t)> T;
+        hipLaunchKernelGGL((k_fill<T>), dim3(grid_for(count, 256, 8192)), dim3(256), 0, stream, (T *)dst, count, (T)1);
+    });
+    HIPCHK(hipGetLastError());
+}
+
+// `rows_ok`: the caller's own part of "rows out of range" (the source's leading dimension)
+void presence_check_args(const std::string &who, const MaskDims &d, int64_t rows, int64_t row0, bool rows_ok, const int64_t *col_bounds,
+                         int n_mod) {
+    if (n_mod < 1 || n_mod > KLNMF_MAX_MODALITIES)
+        fail(KLNMF_ERR_ARG, who + ": 1 <= n_mod <= KLNMF_MAX_MODALITIES (" + std::to_string(KLNMF_MAX_MODALITIES) + ")");
+    if (!col_bounds) fail(KLNMF_ERR_ARG, who + ": null column bounds");
+    if (col_bounds[0] != 0 || col_bounds[n_mod] != d.f) fail(KLNMF_ERR_ARG, who + ": the column bounds must run from 0 to f");
+    for (int m = 0; m < n_mod; ++m)
+        if (col_bounds[m] >= col_bounds[m + 1]) fail(KLNMF_ERR_ARG, who + ": the column bounds must increase strictly");
+    if (rows < 0 || row0 < 0 || row0 + rows > d.n || !rows_ok) fail(KLNMF_ERR_ARG, who + ": rows out of range");
+}
+// ... and, last of the checks, against a mask that is held: `owner` is "problem" or "batch"
+void presence_check_bounds(const PresenceState &ps, const std::string &who, const char *owner, const int64_t *col_bounds, int n_mod) {
+    if (ps.presence() && (n_mod != ps.pres_M || !std::equal(col_bounds, col_bounds + n_mod + 1, ps.pres_bounds)))
+        fail(KLNMF_ERR_ARG, who + ": the column bounds differ from the ones the " + owner + "'s first upload fixed");
+}
+
+// The first mask upload: every problem's P filled with 1 (taken without the zero-fill: k_fill writes all of it), S, D, D's slabs, and
+// once for all the bounds and the per-column modality bytes.  All or nothing; an owner that holds a mask already is left alone.
+void presence_take(DeviceBlocks &a, PresenceState &ps, const MaskDims &d, const int64_t *col_bounds, int n_mod) {
+    if (ps.presence()) return;
+    const size_t es = prec_esize(d.prec), B = (size_t)d.B;
+    const int64_t M = n_mod;
+    HIPCHK(hipStreamSynchronize(a.stream));
+    PresenceState t;
+    try {
+        t.pres_dchunks = presence_d_chunks(d.n);
+        t.Pm = a.dalloc(B * (size_t)(d.n * M) * es, false);
+        t.pres_S = a.dalloc(B * (size_t)(M * d.k) * es);
+        t.pres_D = a.dalloc(B * (size_t)(d.k * M) * es);
+        t.pres_Dslab = a.dalloc(B * (size_t)t.pres_dchunks * (size_t)(d.k * M) * sizeof(double));
+        t.pres_dbounds = a.dalloc((size_t)(M + 1) * sizeof(int64_t));
+        t.pres_mod = a.dalloc((size_t)d.f);
+        std::vector<unsigned char> mod((size_t)d.f);
+        for (int m = 0; m < n_mod; ++m) std::fill(mod.begin() + col_bounds[m], mod.begin() + col_bounds[m + 1], (unsigned char)m);
+        HIPCHK(hipMemcpyAsync(t.pres_mod, mod.data(), mod.size(), hipMemcpyHostToDevice, a.stream));
+        HIPCHK(hipMemcpyAsync(t.pres_dbounds, col_bounds, (size_t)(M + 1) * sizeof(int64_t), hipMemcpyHostToDevice, a.stream));
+        fill_ones(a.stream, t.Pm, d.prec == KLNMF_PREC_F64, (int64_t)B * d.n * M);
+        HIPCHK(hipStreamSynchronize(a.stream));      // (the host images above are read by the copies until here)
+    } catch (...) {                     // all or nothing: a failed first upload leaves the owner without a mask
+        (void)hipStreamSynchronize(a.stream);
+        for (void **b : {&t.Pm, &t.pres_S, &t.pres_D, &t.pres_Dslab, &t.pres_dbounds, &t.pres_mod}) a.dfree(*b);
+        throw;
+    }
+    std::copy(col_bounds, col_bounds + n_mod + 1, t.pres_bounds);
+    t.pres_M = n_mod;
+    ps = t;
+}
+
+static void *presence_of(const PresenceState &ps, const MaskDims &d, int p) {
+    return (char *)ps.Pm + (size_t)p * (size_t)(d.n * ps.pres_M) * prec_esize(d.prec);
+}
+
+// P_p[row0 + i, m] = src[i, m] from the host: the rows through the bounded staging buffer, cast and placed by k_place_V on problem
+// p's n x M matrix
+void presence_upload(DeviceBlocks &a, PresenceState &ps, const MaskDims &d, int p, const void *src, int dtype, int64_t rows, int64_t ld,
+                     int64_t row0) {
+    const int64_t M = ps.pres_M;
+    staged_upload(a.stream, src, dt_size(dtype), rows, M, ld, [&](const void *chunk, int64_t r0, int64_t rr) {
+        place_rows(a.stream, presence_of(ps, d, p), d.prec == KLNMF_PREC_F64, M, chunk, dtype == KLNMF_DT_F64, rr, M, ld, row0 + r0, 0, 1.0,
+                   nullptr);
+    });
+}
+
+// The row indices of a device-side upload, checked on the device (k_presence_rows_check; the pattern of k_csrg_len): the host reads
+// the flag back and refuses before anything is taken or written.
+void presence_rows_check(DeviceBlocks &a, const std::string &who, const int64_t *drow_idx, int64_t rows, int64_t src_rows) {
+    void *flag = a.dalloc(sizeof(int64_t));      // (zero-filled)
+    int64_t bad = 0;
+    try {
+        hipLaunchKernelGGL(k_presence_rows_check, dim3(grid_for(rows, 256, kPresGatherMaxBlocks)), dim3(256), 0, a.stream, drow_idx, rows,
+                           src_rows, (int64_t *)flag);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&bad, flag, sizeof(int64_t), hipMemcpyDeviceToHost, a.stream));
+        HIPCHK(hipStreamSynchronize(a.stream));
+    } catch (...) {
+        (void)hipStreamSynchronize(a.stream);
+        a.dfree(flag);
+        throw;
+    }
+    a.dfree(flag);
+    if (bad) fail(KLNMF_ERR_ARG, who + ": a row index outside [0, src_rows)");
+}
+
+// P_p[row0 + i, m] = dP[drow_idx[i], cols.col[m]] (1 where the column is -1), gathered by k_presence_gather.  Callers have checked
+// that every index is a source row, every column one of its ld, and row0 + rows <= n: the gather reads and writes in range
+void presence_gather(DeviceBlocks &a, PresenceState &ps, const MaskDims &d, int p, const void *dP, int dtype, int64_t ld,
+                     const int64_t *drow_idx, int64_t rows, int64_t row0, const PresenceCols &cols) {
+    const dim3 grid(grid_for(rows, 256, kPresGatherMaxBlocks));
+    dispatch_types(d.prec == KLNMF_PREC_F64, dtype == KLNMF_DT_F64, [&](auto dt, auto st) {
+        typedef tag_t<decltype(dt)> T;
+        typedef tag_t<decltype(st)> S;
+        hipLaunchKernelGGL((k_presence_gather<T, S>), grid, dim3(256), 0, a.stream, (T *)presence_of(ps, d, p), ps.pres_M, (const S *)dP, ld,
+                           drow_idx, rows, row0, cols);
+    });
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(a.stream));      // (dP and drow_idx are the caller's: free to go from here)
+}
+
+// the owner runs the unmasked kernels again
+void presence_drop(DeviceBlocks &a, PresenceState &ps) {
+    if (!ps.presence()) return;
+    HIPCHK(hipStreamSynchronize(a.stream));
+    for (void **b : {&ps.Pm, &ps.pres_S, &ps.pres_D, &ps.pres_Dslab, &ps.pres_dbounds, &ps.pres_mod}) a.dfree(*b);
+    ps.forget_presence();
 }
 
 }  // namespace klnmf_host
@@ -542,7 +623,7 @@ int klnmf_upload_csr(klnmf_ctx *c, int dtype, const int64_t *indptr, const int64
         if (!c->sparse) fail(KLNMF_ERR_ARG, "klnmf_upload_csr needs klnmf_set_problem_sparse");
         if (!indptr || !csc_indptr || (c->nnz > 0 && (!indices || !data || !csc_rows || !csc_perm)))
             fail(KLNMF_ERR_ARG, "null pointer");
-        if (dtype != KLNMF_DT_F32 && dtype != KLNMF_DT_F64) fail(KLNMF_ERR_ARG, "dtype must be KLNMF_DT_F32 or KLNMF_DT_F64");
+        check_dtype(dtype);
         if (indptr[0] != 0 || indptr[c->n] != c->nnz || csc_indptr[0] != 0 || csc_indptr[c->f] != c->nnz)
             fail(KLNMF_ERR_ARG, "index pointers do not match n, f, nnz");
         HIPCHK(hipMemcpyAsync(c->sp_indptr, indptr, sizeof(int64_t) * (c->n + 1), hipMemcpyHostToDevice, c->stream));
@@ -566,7 +647,7 @@ int klnmf_upload_csr_rows(klnmf_ctx *c, int dtype, const int64_t *indptr, const 
         need_problem(c);
         if (!c->sparse) fail(KLNMF_ERR_ARG, "klnmf_upload_csr_rows needs klnmf_set_problem_sparse");
         if (!indptr || (c->nnz > 0 && (!indices || !data))) fail(KLNMF_ERR_ARG, "null pointer");
-        if (dtype != KLNMF_DT_F32 && dtype != KLNMF_DT_F64) fail(KLNMF_ERR_ARG, "dtype must be KLNMF_DT_F32 or KLNMF_DT_F64");
+        check_dtype(dtype);
         if (indptr[0] != 0 || indptr[c->n] != c->nnz) fail(KLNMF_ERR_ARG, "the row pointers do not match n, nnz");
         c->v_uploaded = false;
         HIPCHK(hipMemcpyAsync(c->sp_indptr, indptr, sizeof(int64_t) * (c->n + 1), hipMemcpyHostToDevice, c->stream));
@@ -605,8 +686,7 @@ int klnmf_upload_csr_device_rows(klnmf_ctx *c, int n_mod, const int64_t *const *
             if (col_bounds[m] > col_bounds[m + 1]) fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: the column bounds must not decrease");
             if (col_bounds[m + 1] - col_bounds[m] > (int64_t)std::numeric_limits<int32_t>::max())
                 fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: a modality of 2^31 columns or more (int32 source indices)");
-            if (dtype[m] != KLNMF_DT_F32 && dtype[m] != KLNMF_DT_F64)
-                fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: dtype must be KLNMF_DT_F32 or KLNMF_DT_F64");
+            check_dtype(dtype[m], std::string("klnmf_upload_csr_device_rows: ") + kDtypeMsg);
             if (!indptr[m] || (c->nnz > 0 && (!indices[m] || !data[m]))) fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: null pointer");
             S.indptr[m] = indptr[m];
             S.indices[m] = indices[m];
@@ -662,8 +742,7 @@ int klnmf_csr_rows_to_dense_device(int device, int dtype, const int64_t *indptr,
     return guarded([&] {
         if (rows < 0 || d < 0 || src_rows < 0 || rows > (1LL << 40) || d > (int64_t)std::numeric_limits<int32_t>::max())
             fail(KLNMF_ERR_ARG, "klnmf_csr_rows_to_dense_device: bad shape");
-        if (dtype != KLNMF_DT_F32 && dtype != KLNMF_DT_F64)
-            fail(KLNMF_ERR_ARG, "klnmf_csr_rows_to_dense_device: dtype must be KLNMF_DT_F32 or KLNMF_DT_F64");
+        check_dtype(dtype, std::string("klnmf_csr_rows_to_dense_device: ") + kDtypeMsg);
         if (rows == 0 || d == 0) return;
         if (!indptr || !drow_idx || !dout || ld < d) fail(KLNMF_ERR_ARG, "klnmf_csr_rows_to_dense_device: null pointer or short stride");
         HIPCHK(hipSetDevice(device));
@@ -734,7 +813,7 @@ int klnmf_upload_V(klnmf_ctx *c, const void *src, int dtype, int64_t rows, int64
     return guarded([&] {
         need_problem(c);
         if (!src) fail(KLNMF_ERR_ARG, "null source");
-        check_block(c, rows, cols, ld, row0, col0);
+        check_block(c->n, c->f, rows, cols, ld, row0, col0);
         upload_block(c, src, dtype, rows, cols, ld, row0, col0, scale, false);
     });
 }
@@ -750,11 +829,11 @@ int klnmf_upload_weights(klnmf_ctx *c, const void *src, int dtype, int64_t rows,
         if (c->prec != KLNMF_PREC_F64 && c->prec != KLNMF_PREC_F32)
             fail(KLNMF_ERR_UNSUPP, "klnmf_upload_weights: the weighted kernels exist in KLNMF_PREC_F64 and KLNMF_PREC_F32 only");
         if (!src) fail(KLNMF_ERR_ARG, "null source");
-        if (dtype != KLNMF_DT_F64 && dtype != KLNMF_DT_F32) fail(KLNMF_ERR_ARG, "unknown dtype");
+        check_dtype(dtype, "unknown dtype");
         if (c->sharded_loop)
             fail(KLNMF_ERR_UNSUPP, "klnmf_upload_weights: a loop over row shards is open on this context (klnmf_loop_begin on a communicator, "
                                    "klnmf_loop_begin_sharded / _agreed) and its exchange carries no denominator; klnmf_loop_end first");
-        check_block(c, rows, cols, ld, row0, col0);
+        check_block(c->n, c->f, rows, cols, ld, row0, col0);
         if (c->presence())
             fail(KLNMF_ERR_ARG, "klnmf_upload_weights: the problem holds a presence mask (klnmf_upload_presence); klnmf_clear_weights first");
         const size_t es = c->esize(), n = (size_t)c->n, f = (size_t)c->f, k = (size_t)c->k;
@@ -766,12 +845,7 @@ int klnmf_upload_weights(klnmf_ctx *c, const void *src, int dtype, int64_t rows,
                 c->Dpart = c->dalloc((size_t)c->nsplit * k * f * es);
                 c->denom = c->dalloc(k * f * es);
                 if (c->wsplit > 1) c->WDpart = c->dalloc((size_t)c->wsplit * n * k * es);
-                const int64_t count = c->n * c->f;
-                if (c->prec == KLNMF_PREC_F64)
-                    hipLaunchKernelGGL((k_fill<double>), dim3(grid_for(count, 256, 8192)), dim3(256), 0, c->stream, (double *)om, count, 1.0);
-                else
-                    hipLaunchKernelGGL((k_fill<float>), dim3(grid_for(count, 256, 8192)), dim3(256), 0, c->stream, (float *)om, count, 1.0f);
-                HIPCHK(hipGetLastError());
+                fill_ones(c->stream, om, c->prec == KLNMF_PREC_F64, c->n * c->f);
             } catch (...) {                     // all or nothing: a failed first upload leaves the problem unweighted
                 (void)hipStreamSynchronize(c->stream);
                 c->dfree(c->Dpart); c->dfree(c->denom); c->dfree(c->WDpart); c->dfree(om);
@@ -784,8 +858,8 @@ int klnmf_upload_weights(klnmf_ctx *c, const void *src, int dtype, int64_t rows,
     });
 }
 
-// What klnmf_upload_presence and klnmf_upload_presence_device_rows refuse alike, in this order around their own argument checks, and
-// how the first of them on a problem takes the mask's state.
+// What klnmf_upload_presence and klnmf_upload_presence_device_rows refuse alike and a batch never meets, in this order around their
+// own argument checks.
 static void presence_check_supported(klnmf_ctx *c, const std::string &who) {
     if (c->sparse) fail(KLNMF_ERR_UNSUPP, who + ": CSR problems have no masked kernels (the ratio lives on the stored entries only)");
     if (c->prec != KLNMF_PREC_F64 && c->prec != KLNMF_PREC_F32)
@@ -795,58 +869,13 @@ static void presence_check_supported(klnmf_ctx *c, const std::string &who) {
                                      "klnmf_loop_begin_sharded / _agreed) and its exchange carries no W^T.P; klnmf_loop_end first");
 }
 
-// `rows_ok`: the caller's own part of "rows out of range" (the source's leading dimension)
-static void presence_check_args(klnmf_ctx *c, const std::string &who, int64_t rows, int64_t row0, bool rows_ok, const int64_t *col_bounds,
-                                int n_mod) {
-    if (n_mod < 1 || n_mod > KLNMF_MAX_MODALITIES)
-        fail(KLNMF_ERR_ARG, who + ": 1 <= n_mod <= KLNMF_MAX_MODALITIES (" + std::to_string(KLNMF_MAX_MODALITIES) + ")");
-    if (!col_bounds) fail(KLNMF_ERR_ARG, who + ": null column bounds");
-    if (col_bounds[0] != 0 || col_bounds[n_mod] != c->f) fail(KLNMF_ERR_ARG, who + ": the column bounds must run from 0 to f");
-    for (int m = 0; m < n_mod; ++m)
-        if (col_bounds[m] >= col_bounds[m + 1]) fail(KLNMF_ERR_ARG, who + ": the column bounds must increase strictly");
-    if (rows < 0 || row0 < 0 || row0 + rows > c->n || !rows_ok) fail(KLNMF_ERR_ARG, who + ": rows out of range");
+// the shared argument checks around the one refusal that is a context's own
+static MaskDims mask_dims(const klnmf_ctx *c) { return {c->n, c->f, c->k, 1, c->prec}; }
+static void presence_check_all(klnmf_ctx *c, const std::string &who, int64_t rows, int64_t row0, bool rows_ok, const int64_t *col_bounds,
+                               int n_mod) {
+    presence_check_args(who, mask_dims(c), rows, row0, rows_ok, col_bounds, n_mod);
     if (c->weighted()) fail(KLNMF_ERR_ARG, who + ": the problem holds weights (klnmf_upload_weights); klnmf_clear_weights first");
-    if (c->presence() && (n_mod != c->pres_M || !std::equal(col_bounds, col_bounds + n_mod + 1, c->pres_bounds)))
-        fail(KLNMF_ERR_ARG, who + ": the column bounds differ from the ones the problem's first upload fixed");
-}
-
-// The first mask upload of a problem: P filled with 1, S, D, D's slabs, the bounds and the per-column modality bytes (ProblemState).
-// All or nothing; a problem that holds a mask already is left alone.
-static void presence_take(klnmf_ctx *c, const int64_t *col_bounds, int n_mod) {
-    if (c->presence()) return;
-    const size_t es = c->esize();
-    const int64_t M = n_mod;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    void *pm = nullptr;
-    try {
-        const int dch = presence_d_chunks(c->n);
-        pm = c->dalloc((size_t)(c->n * M) * es, false);
-        c->pres_S = c->dalloc((size_t)(M * c->k) * es);
-        c->pres_D = c->dalloc((size_t)(c->k * M) * es);
-        c->pres_Dslab = c->dalloc((size_t)dch * (size_t)(c->k * M) * sizeof(double));
-        c->pres_dbounds = c->dalloc((size_t)(M + 1) * sizeof(int64_t));
-        c->pres_mod = c->dalloc((size_t)c->f);
-        std::vector<unsigned char> mod((size_t)c->f);
-        for (int m = 0; m < n_mod; ++m) std::fill(mod.begin() + col_bounds[m], mod.begin() + col_bounds[m + 1], (unsigned char)m);
-        HIPCHK(hipMemcpyAsync(c->pres_mod, mod.data(), mod.size(), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->pres_dbounds, col_bounds, (size_t)(M + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        const int64_t count = c->n * M;
-        if (c->prec == KLNMF_PREC_F64)
-            hipLaunchKernelGGL((k_fill<double>), dim3(grid_for(count, 256, 8192)), dim3(256), 0, c->stream, (double *)pm, count, 1.0);
-        else
-            hipLaunchKernelGGL((k_fill<float>), dim3(grid_for(count, 256, 8192)), dim3(256), 0, c->stream, (float *)pm, count, 1.0f);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(c->stream));      // (the host images above are read by the copies until here)
-        c->pres_dchunks = dch;
-    } catch (...) {                     // all or nothing: a failed first upload leaves the problem without a mask
-        (void)hipStreamSynchronize(c->stream);
-        c->dfree(c->pres_S); c->dfree(c->pres_D); c->dfree(c->pres_Dslab); c->dfree(c->pres_dbounds); c->dfree(c->pres_mod);
-        c->dfree(pm);
-        throw;
-    }
-    c->Pm = pm;
-    std::copy(col_bounds, col_bounds + n_mod + 1, c->pres_bounds);
-    c->pres_M = n_mod;
+    presence_check_bounds(*c, who, "problem", col_bounds, n_mod);
 }
 
 // P[row0 + i, m] = src[i, m] for the M = n_mod modalities whose columns are [col_bounds[m], col_bounds[m + 1]) (presence.hip.h).  The
@@ -859,43 +888,16 @@ int klnmf_upload_presence(klnmf_ctx *c, const void *src, int dtype, int64_t rows
         const std::string who = "klnmf_upload_presence";
         presence_check_supported(c, who);
         if (!src && rows > 0) fail(KLNMF_ERR_ARG, "null source");
-        if (dtype != KLNMF_DT_F64 && dtype != KLNMF_DT_F32) fail(KLNMF_ERR_ARG, "unknown dtype");
-        presence_check_args(c, who, rows, row0, ld >= n_mod, col_bounds, n_mod);
-        const int64_t M = n_mod;
-        presence_take(c, col_bounds, n_mod);
+        check_dtype(dtype, "unknown dtype");
+        presence_check_all(c, who, rows, row0, ld >= n_mod, col_bounds, n_mod);
+        presence_take(*c, *c, mask_dims(c), col_bounds, n_mod);
         if (rows == 0) return;
-        // the rows through a bounded staging buffer (upload_block's scheme), cast and placed by k_place_V on an n x M matrix
-        const size_t ses = dt_size(dtype);
-        int64_t rows_per = (int64_t)((256ull << 20) / (ses * (size_t)ld));
-        rows_per = std::max<int64_t>(1, std::min(rows_per, rows));
-        void *d = nullptr;
-        HIPCHK(hipMalloc(&d, (size_t)rows_per * ld * ses + 16));
-        try {
-            for (int64_t r0 = 0; r0 < rows; r0 += rows_per) {
-                const int64_t rr = std::min(rows_per, rows - r0);
-                HIPCHK(hipMemcpyAsync(d, (const char *)src + (size_t)r0 * ld * ses, ((size_t)(rr - 1) * ld + M) * ses,
-                                      hipMemcpyHostToDevice, c->stream));
-                const int grid = grid_for(rr * M, 256, 8192);
-                const int64_t *no_idx = nullptr;
-#define KL_PLACE_P(T, S) hipLaunchKernelGGL((k_place_V<T, S>), dim3(grid), dim3(256), 0, c->stream, (T *)c->Pm, M, (const S *)d, rr, M, ld, \
-                                            row0 + r0, (int64_t)0, 1.0, no_idx)
-                if (c->prec == KLNMF_PREC_F64) { if (dtype == KLNMF_DT_F64) KL_PLACE_P(double, double); else KL_PLACE_P(double, float); }
-                else { if (dtype == KLNMF_DT_F64) KL_PLACE_P(float, double); else KL_PLACE_P(float, float); }
-#undef KL_PLACE_P
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipStreamSynchronize(c->stream));
-            }
-        } catch (...) {
-            (void)hipFree(d);
-            throw;
-        }
-        (void)hipFree(d);
+        presence_upload(*c, *c, mask_dims(c), 0, src, dtype, rows, ld, row0);
     });
 }
 
-// klnmf_upload_presence for a mask in device memory: P[row0 + i, m] = dP[drow_idx[i], src_cols[m]], 1 where src_cols[m] is -1, gathered by
-// k_presence_gather (presence.hip.h).  The row indices are checked on the device first (k_presence_rows_check; the pattern of
-// k_csrg_len): the host reads the flag back, and only a clean flag takes the mask (a first upload) and launches the gather -- a
+// klnmf_upload_presence for a mask in device memory: P[row0 + i, m] = dP[drow_idx[i], src_cols[m]], 1 where src_cols[m] is -1.  The row
+// indices are checked on the device first, and only a clean flag takes the mask (a first upload) and launches the gather -- a
 // refused call leaves the problem as it was.
 int klnmf_upload_presence_device_rows(klnmf_ctx *c, const void *dP, int dtype, int64_t src_rows, int64_t ld, const int64_t *drow_idx,
                                       int64_t rows, int64_t row0, const int *src_cols, const int64_t *col_bounds, int n_mod) {
@@ -904,42 +906,18 @@ int klnmf_upload_presence_device_rows(klnmf_ctx *c, const void *dP, int dtype, i
         const std::string who = "klnmf_upload_presence_device_rows";
         presence_check_supported(c, who);
         if (!dP && rows > 0) fail(KLNMF_ERR_ARG, "null source");
-        if (dtype != KLNMF_DT_F64 && dtype != KLNMF_DT_F32) fail(KLNMF_ERR_ARG, "unknown dtype");
-        presence_check_args(c, who, rows, row0, ld >= 0 && src_rows >= 0 && (drow_idx || rows <= src_rows), col_bounds, n_mod);
+        check_dtype(dtype, "unknown dtype");
+        presence_check_all(c, who, rows, row0, ld >= 0 && src_rows >= 0 && (drow_idx || rows <= src_rows), col_bounds, n_mod);
         if (!src_cols) fail(KLNMF_ERR_ARG, who + ": null source columns");
         PresenceCols cols{};
         for (int m = 0; m < n_mod; ++m) {
             if (src_cols[m] < -1 || src_cols[m] >= ld) fail(KLNMF_ERR_ARG, who + ": a source column outside [-1, ld)");
             cols.col[m] = src_cols[m];
         }
-        if (rows > 0 && drow_idx) {
-            void *flag = c->dalloc(sizeof(int64_t));      // (zero-filled)
-            int64_t bad = 0;
-            try {
-                hipLaunchKernelGGL(k_presence_rows_check, dim3(grid_for(rows, 256, kPresGatherMaxBlocks)), dim3(256), 0, c->stream, drow_idx,
-                                   rows, src_rows, (int64_t *)flag);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpyAsync(&bad, flag, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipStreamSynchronize(c->stream));
-            } catch (...) {
-                (void)hipStreamSynchronize(c->stream);
-                c->dfree(flag);
-                throw;
-            }
-            c->dfree(flag);
-            if (bad) fail(KLNMF_ERR_ARG, who + ": a row index outside [0, src_rows)");
-        }
-        presence_take(c, col_bounds, n_mod);
+        if (rows > 0 && drow_idx) presence_rows_check(*c, who, drow_idx, rows, src_rows);
+        presence_take(*c, *c, mask_dims(c), col_bounds, n_mod);
         if (rows == 0) return;
-        // every index is a source row, every column one of its ld, and row0 + rows <= n: the gather reads and writes in range
-        const int grid = grid_for(rows, 256, kPresGatherMaxBlocks);
-#define KL_GATHER_P(T, S) hipLaunchKernelGGL((k_presence_gather<T, S>), dim3(grid), dim3(256), 0, c->stream, (T *)c->Pm, n_mod, (const S *)dP, ld, \
-                                             drow_idx, rows, row0, cols)
-        if (c->prec == KLNMF_PREC_F64) { if (dtype == KLNMF_DT_F64) KL_GATHER_P(double, double); else KL_GATHER_P(double, float); }
-        else { if (dtype == KLNMF_DT_F64) KL_GATHER_P(float, double); else KL_GATHER_P(float, float); }
-#undef KL_GATHER_P
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(c->stream));      // (dP and drow_idx are the caller's: free to go from here)
+        presence_gather(*c, *c, mask_dims(c), 0, dP, dtype, ld, drow_idx, rows, row0, cols);
     });
 }
 
@@ -948,11 +926,7 @@ int klnmf_clear_weights(klnmf_ctx *c) {
     return guarded([&] {
         need_problem(c);
         if (c->presence()) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            c->dfree(c->Pm); c->dfree(c->pres_S); c->dfree(c->pres_D); c->dfree(c->pres_Dslab); c->dfree(c->pres_dbounds);
-            c->dfree(c->pres_mod);
-            c->pres_M = 0; c->pres_dchunks = 0;
-            std::fill(c->pres_bounds, c->pres_bounds + kMaxMod + 1, (int64_t)0);
+            presence_drop(*c, *c);
             return;
         }
         if (!c->weighted()) return;
@@ -966,8 +940,8 @@ int klnmf_upload_V_device(klnmf_ctx *c, const float *dsrc, int64_t rows, int64_t
     return guarded([&] {
         need_problem(c);
         if (!dsrc) fail(KLNMF_ERR_ARG, "null source");
-        check_block(c, rows, cols, ld, row0, col0);
-        place_block<float>(c, dsrc, rows, cols, ld, row0, col0, scale);
+        check_block(c->n, c->f, rows, cols, ld, row0, col0);
+        place_block(c, dsrc, false, rows, cols, ld, row0, col0, scale);
     });
 }
 
@@ -976,8 +950,8 @@ int klnmf_upload_V_device_rows(klnmf_ctx *c, const float *dsrc, const int64_t *d
     return guarded([&] {
         need_problem(c);
         if (!dsrc || !drow_idx) fail(KLNMF_ERR_ARG, "null source");
-        check_block(c, rows, cols, ld, row0, col0);
-        place_block<float>(c, dsrc, rows, cols, ld, row0, col0, scale, drow_idx);
+        check_block(c->n, c->f, rows, cols, ld, row0, col0);
+        place_block(c, dsrc, false, rows, cols, ld, row0, col0, scale, drow_idx);
     });
 }
 
@@ -1003,22 +977,16 @@ int klnmf_set_H_device(klnmf_ctx *c, const void *dsrc, int dtype, int64_t ld, in
     return guarded([&] {
         need_problem(c);
         if (!dsrc) fail(KLNMF_ERR_ARG, "null source");
-        if (dtype != KLNMF_DT_F32 && dtype != KLNMF_DT_F64) fail(KLNMF_ERR_ARG, "dtype must be KLNMF_DT_F32 or KLNMF_DT_F64");
+        check_dtype(dtype);
         if (col0 < 0 || ncols < 0 || col0 + ncols > c->f || ld < ncols) fail(KLNMF_ERR_ARG, "klnmf_set_H_device: column block out of range");
-        const bool f64 = dtype == KLNMF_DT_F64;
         // the first block of a dictionary (col0 = 0) starts from zeros, as klnmf_set_H does: a pooled or re-used context
         // must not keep padding rows / columns of the previous dictionary in its images
         if (col0 == 0 && !c->is_exact()) HIPCHK(hipMemsetAsync(c->H32, 0, (size_t)c->KP * c->f_pad * 4, c->stream));
-        if (c->prec == KLNMF_PREC_F64) {
-            if (f64) copy_2d(c, (double *)c->H + col0, c->f, (const double *)dsrc, ld, c->k, ncols);
-            else copy_2d(c, (double *)c->H + col0, c->f, (const float *)dsrc, ld, c->k, ncols);
-        } else if (c->is_f32()) {
-            if (f64) copy_2d(c, (float *)c->H + col0, c->f, (const double *)dsrc, ld, c->k, ncols);
-            else copy_2d(c, (float *)c->H + col0, c->f, (const float *)dsrc, ld, c->k, ncols);
-        } else {
-            if (f64) copy_2d(c, c->H32 + col0, c->f_pad, (const double *)dsrc, ld, c->k, ncols);
-            else copy_2d(c, c->H32 + col0, c->f_pad, (const float *)dsrc, ld, c->k, ncols);
-        }
+        if (c->is_exact())
+            copy_2d_any(c->stream, (char *)c->H + (size_t)col0 * c->esize(), c->prec == KLNMF_PREC_F64, c->f, dsrc, dtype == KLNMF_DT_F64, ld,
+                        c->k, ncols);
+        else
+            copy_2d_any(c->stream, c->H32 + col0, false, c->f_pad, dsrc, dtype == KLNMF_DT_F64, ld, c->k, ncols);
         if (last) {
             if (!c->is_exact()) {
                 fast_pack_H(c);
@@ -1033,19 +1001,12 @@ int klnmf_get_W_device(klnmf_ctx *c, void *ddst, int dtype, int64_t ld) {
     return guarded([&] {
         need_problem(c);
         if (!ddst) fail(KLNMF_ERR_ARG, "null destination");
-        if (dtype != KLNMF_DT_F32 && dtype != KLNMF_DT_F64) fail(KLNMF_ERR_ARG, "dtype must be KLNMF_DT_F32 or KLNMF_DT_F64");
+        check_dtype(dtype);
         if (ld < c->k) fail(KLNMF_ERR_ARG, "klnmf_get_W_device: row stride shorter than k");
-        const bool f64 = dtype == KLNMF_DT_F64;
-        if (c->prec == KLNMF_PREC_F64) {
-            if (f64) copy_2d(c, (double *)ddst, ld, (const double *)c->W[c->cur], c->k, c->n, c->k);
-            else copy_2d(c, (float *)ddst, ld, (const double *)c->W[c->cur], c->k, c->n, c->k);
-        } else if (c->is_f32()) {
-            if (f64) copy_2d(c, (double *)ddst, ld, (const float *)c->W[c->cur], c->k, c->n, c->k);
-            else copy_2d(c, (float *)ddst, ld, (const float *)c->W[c->cur], c->k, c->n, c->k);
-        } else {
-            if (f64) copy_2d(c, (double *)ddst, ld, (const float *)c->W32[c->cur], (int64_t)c->KP, c->n, c->k, 1.0 / c->v_scale);
-            else copy_2d(c, (float *)ddst, ld, (const float *)c->W32[c->cur], (int64_t)c->KP, c->n, c->k, 1.0 / c->v_scale);
-        }
+        if (c->is_exact())
+            copy_2d_any(c->stream, ddst, dtype == KLNMF_DT_F64, ld, c->W[c->cur], c->prec == KLNMF_PREC_F64, c->k, c->n, c->k);
+        else
+            copy_2d_any(c->stream, ddst, dtype == KLNMF_DT_F64, ld, c->W32[c->cur], false, c->KP, c->n, c->k, 1.0 / c->v_scale);
         HIPCHK(hipStreamSynchronize(c->stream));
     });
 }
@@ -1055,10 +1016,9 @@ int klnmf_upload_V_device_rows_dt(klnmf_ctx *c, const void *dsrc, int dtype, con
     return guarded([&] {
         need_problem(c);
         if (!dsrc) fail(KLNMF_ERR_ARG, "null source");
-        if (dtype != KLNMF_DT_F32 && dtype != KLNMF_DT_F64) fail(KLNMF_ERR_ARG, "dtype must be KLNMF_DT_F32 or KLNMF_DT_F64");
-        check_block(c, rows, cols, ld, row0, col0);
-        if (dtype == KLNMF_DT_F64) place_block<double>(c, (const double *)dsrc, rows, cols, ld, row0, col0, scale, drow_idx);
-        else place_block<float>(c, (const float *)dsrc, rows, cols, ld, row0, col0, scale, drow_idx);
+        check_dtype(dtype);
+        check_block(c->n, c->f, rows, cols, ld, row0, col0);
+        place_block(c, dsrc, dtype == KLNMF_DT_F64, rows, cols, ld, row0, col0, scale, drow_idx);
     });
 }
 

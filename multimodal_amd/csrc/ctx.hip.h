@@ -8,11 +8,14 @@
 //   api_eval.hip     evaluation and introspection: reconstruction products (learner.py:80-84), distances, queries, profiling
 //   api_group.hip    a group of contexts (row shards, one device each, a device may repeat) driven from one host thread: the
 //                    exchange of group.hip.h between their streams, the loop of klnmf_group_run
-//   api_batch.hip    a batch of dense, unweighted problems of one shape in KLNMF_PREC_F64 / F32 (klnmf_batch_*): the loop's stages as
-//                    one launch each for all of them (batch.hip.h), the plan of one problem for its share of the CUs
-// This header: error handling, the device block cache, the development switches and the context itself -- its state in four
-// groups, one per lifetime (ContextState, ProblemState, LoopState, LoopRecord); plan.hip.h: the launch plan of a problem, the
-// value ProblemState is built on.
+//   api_batch.hip    a batch of dense problems of one shape in KLNMF_PREC_F64 / F32, unweighted or all under presence masks
+//                    (klnmf_batch_*): the [B] layout, the loop's stages as one launch each for all of them (batch.hip.h), the plan
+//                    of one problem for its share of the CUs
+// This header: error handling, the type dispatch of the host-facing kernels, the device block cache and the arena over it
+// (DeviceBlocks), the staged host upload, the development switches, the mask state (PresenceState) and the context itself -- its
+// state in four groups, one per lifetime (ContextState, ProblemState, LoopState, LoopRecord) -- and what contexts and batches share
+// (defined once, in api_context.hip: the mask helpers, place_rows, copy_2d_any, fill_ones).  plan.hip.h: the launch plan of a
+// problem, the value ProblemState is built on; stage_chunks.h: the chunk arithmetic of staged_upload, free of HIP.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -32,6 +35,7 @@
 #include <vector>
 
 #include "../../include/klnmf.h"
+#include "stage_chunks.h"
 #include "common.hip.h"
 #include "exact.hip.h"
 #include "weighted.hip.h"
@@ -94,6 +98,29 @@ inline int grid_for(int64_t count, int block = 256, int cap = 4096) {
     if (g < 1) g = 1;
     if (g > cap) g = cap;
     return (int)g;
+}
+
+// The host-facing kernels (placing, copying, converting, filling) exist for double and float on either side; a dtype or precision
+// known at run time picks the instantiation: f(TypeTag<T>{}) for `f64`, f(TypeTag<D>{}, TypeTag<S>{}) for (`d64`, `s64`).
+template <typename T> struct TypeTag { using type = T; };
+template <typename Tag> using tag_t = typename Tag::type;
+template <typename F>
+void dispatch_type(bool f64, F &&f) {
+    if (f64) f(TypeTag<double>{}); else f(TypeTag<float>{});
+}
+template <typename F>
+void dispatch_types(bool d64, bool s64, F &&f) {
+    dispatch_type(d64, [&](auto d) { dispatch_type(s64, [&](auto s) { f(d, s); }); });
+}
+
+constexpr const char *kDtypeMsg = "dtype must be KLNMF_DT_F32 or KLNMF_DT_F64";
+inline void check_dtype(int dtype, const std::string &msg = kDtypeMsg) {
+    if (dtype != KLNMF_DT_F32 && dtype != KLNMF_DT_F64) fail(KLNMF_ERR_ARG, msg);
+}
+// a block [rows, cols] (leading dimension ld) at (row0, col0) of an n x f matrix
+inline void check_block(int64_t n, int64_t f, int64_t rows, int64_t cols, int64_t ld, int64_t row0, int64_t col0) {
+    if (rows < 0 || cols < 0 || row0 < 0 || col0 < 0 || row0 + rows > n || col0 + cols > f || ld < cols)
+        fail(KLNMF_ERR_ARG, "V block out of range");
 }
 
 constexpr int kW8Blocks = 1024;             // conversion kernel's grid: per-block column maxima [kW8Blocks][KP]
@@ -175,6 +202,66 @@ struct DevBlockCache {
 };
 extern DevBlockCache g_block_cache;      // (api_context.hip)
 
+// The device blocks of one owner (a context, a batch) on its device and stream: taken from the cache or the driver, handed back
+// one by one or all at once.  Callers of dfree / release_all have synchronised the stream: no kernel still touches the blocks.
+struct DeviceBlocks {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::vector<std::pair<void *, size_t>> allocs;      // (block, size class) of the current problem's device blocks
+    void *dalloc(size_t bytes, bool zero = true) {
+        if (bytes == 0) bytes = 16;
+        const size_t cls = DevBlockCache::size_class(bytes);
+        void *p = g_block_cache.take(device, cls);
+        if (!p) {
+            hipError_t e = hipMalloc(&p, cls);
+            if (e == hipErrorOutOfMemory) {        // the cache may be what is in the way: give its blocks back and retry once
+                (void)hipGetLastError();
+                g_block_cache.flush(device);
+                e = hipMalloc(&p, cls);
+            }
+            HIPCHK(e);
+        }
+        allocs.push_back({p, cls});
+        if (zero) HIPCHK(hipMemsetAsync(p, 0, bytes, stream));
+        return p;
+    }
+    void dfree(void *&p) {
+        for (size_t i = 0; i < allocs.size(); ++i) {
+            if (allocs[i].first != p) continue;
+            if (!g_block_cache.give(device, allocs[i].second, p)) (void)hipFree(p);
+            allocs.erase(allocs.begin() + (std::ptrdiff_t)i);
+            break;
+        }
+        p = nullptr;
+    }
+    void release_all() {
+        for (auto &b : allocs)
+            if (!g_block_cache.give(device, b.second, b.first)) (void)hipFree(b.first);
+        allocs.clear();
+    }
+};
+
+// A host block [rows, cols] (rows `ld` elements of `es` bytes apart) through a bounded device staging buffer (stage_chunks.h):
+// place(device_chunk, r0, rr) enqueues what puts rows [r0, r0 + rr) where they belong; the stream is synchronised behind every
+// chunk, and the buffer is released on the normal and on the throwing path.
+template <typename Place>
+void staged_upload(hipStream_t stream, const void *src, size_t es, int64_t rows, int64_t cols, int64_t ld, Place &&place) {
+    const int64_t rows_per = stage_rows_per(rows, ld, es);
+    void *d = nullptr;
+    HIPCHK(hipMalloc(&d, stage_alloc_bytes(rows_per, ld, es)));
+    try {
+        stage_walk(rows, cols, ld, es, rows_per, [&](const StageChunk &ch) {
+            HIPCHK(hipMemcpyAsync(d, (const char *)src + ch.offset, ch.bytes, hipMemcpyHostToDevice, stream));
+            place((const void *)d, ch.r0, ch.rr);
+            HIPCHK(hipStreamSynchronize(stream));
+        });
+    } catch (...) {
+        (void)hipFree(d);
+        throw;
+    }
+    (void)hipFree(d);
+}
+
 // Development switches: what only measurements and tests need.  Read in ONE place (here), afresh at every klnmf_set_problem and
 // loop entry, and honoured only under KLNMF_DEV=1 -- a production process cannot change the library's arithmetic by accident.
 // (User-facing environment: KLNMF_QTILE=16 -- never fp8 ratio tiles -- and KLNMF_ALLOC_CACHE_MB, plus the host layer's
@@ -239,13 +326,10 @@ namespace klnmf_host {
 //   * profile_every and profile_seq survive both calls; profiling survives klnmf_set_problem* and is cleared by
 //     klnmf_release_problem;
 //   * the communicator (comm, its stream, events and scratch) survives both.
-struct ContextState {
-    int device = 0;
+struct ContextState : DeviceBlocks {
     int prec = KLNMF_PREC_F64;
-    hipStream_t stream = nullptr;
     bool own_stream = false;
     int cu_count = 256;
-    std::vector<std::pair<void *, size_t>> allocs;      // (block, size class) of the current problem's device blocks
     double ratio_eps = kEpsRatio;   // only the step API honours a non-default value
     // polls of the monitor's verdict (poll_fp8_overflow).  The dry run's poll synchronises (its answer decides the NEXT iteration's
     // kernels); every later one is deferred: the counts are copied to pinned host memory behind the monitored iteration, an event
@@ -270,10 +354,24 @@ struct ContextState {
     hipEvent_t ev_part[kPostMaxParts] = {}, ev_ar[kPostMaxParts] = {};
 };
 
+// A mask (presence.hip.h; dense, KLNMF_PREC_F64 / F32) of a context's problem or of all B problems of a batch (batch.hip.h has the
+// [B] layout): the presence matrices P [B][n][M] -- taken filled with 1 by the first upload --, S [B][M][k] and D [B][k][M] of the two
+// collapsed denominators, D's row-chunk slabs, and once for all B the modalities' column bounds (host and device) and the per-column
+// modality index.  pres_M > 0 IS "a mask is held" (KLNMF_Q_PRESENCE).  The blocks are the owner's (DeviceBlocks): they go with
+// presence_drop or with the problem.
+struct PresenceState {
+    int pres_M = 0, pres_dchunks = 0;
+    int64_t pres_bounds[kMaxMod + 1] = {};
+    void *Pm = nullptr, *pres_S = nullptr, *pres_D = nullptr;
+    void *pres_dbounds = nullptr, *pres_mod = nullptr, *pres_Dslab = nullptr;      // int64 [M + 1]; bytes [f]; double [B][chunks][k][M]
+    bool presence() const { return pres_M > 0; }
+    void forget_presence() { *this = PresenceState(); }      // (the blocks are gone or go with the owner's)
+};
+
 // ---- as long as a problem: the plan (plan.hip.h: every shape-derived count), every device buffer, and what uploads and setters
 // leave on them.  Default-constructed by klnmf_set_problem* (behind free_all, before the new plan is stored) and by
 // klnmf_release_problem.
-struct ProblemState : ProblemPlan {
+struct ProblemState : ProblemPlan, PresenceState {
     DevSwitches sw;               // as klnmf_set_problem* read them; read afresh at every loop entry
     int64_t cap = 0;
     bool have_problem = false;
@@ -298,14 +396,8 @@ struct ProblemState : ProblemPlan {
     // by the first klnmf_upload_weights, dropped by klnmf_clear_weights -- and the denominators' slabs and sums, laid out as
     // Npart / numer / Wpart are.  Om != nullptr IS "the current problem is weighted" (klnmf_query KLNMF_Q_WEIGHTED).
     void *Om = nullptr, *Dpart = nullptr, *denom = nullptr, *WDpart = nullptr;
-    // a masked problem (presence.hip.h; dense, KLNMF_PREC_F64 / F32): the n x M presence matrix P -- allocated filled with 1 by the
-    // first klnmf_upload_presence, dropped by klnmf_clear_weights -- the modalities' column bounds (host and device) and the
-    // per-column modality index, S [M][k] and D [k][M] of the two collapsed denominators and D's row-chunk slabs.  pres_M > 0 IS
-    // "the current problem holds a mask" (klnmf_query KLNMF_Q_PRESENCE); a problem holds Om or P, never both.
-    int pres_M = 0, pres_dchunks = 0;
-    int64_t pres_bounds[kMaxMod + 1] = {};
-    void *Pm = nullptr, *pres_S = nullptr, *pres_D = nullptr;
-    void *pres_dbounds = nullptr, *pres_mod = nullptr, *pres_Dslab = nullptr;      // int64 [M + 1]; bytes [f]; double [chunks][k][M]
+    // a masked problem: PresenceState, taken by the first klnmf_upload_presence*, dropped by klnmf_clear_weights; a problem holds
+    // Om or P, never both
     float *x3_hs = nullptr, *x3_qr = nullptr;     // per-component H scales; per-row ratio scales of the column pass
     unsigned *x3_xmax = nullptr;                  // per-component maxima of W_new qr (bit patterns of non-negative floats)
     double *x3_loss = nullptr;                    // one loss partial per 64 rows
@@ -423,41 +515,11 @@ struct klnmf_ctx : ContextState, ProblemState, LoopState, LoopRecord {
     bool x3_fused() const { return x3; }
     size_t esize() const { return prec_esize(prec); }
     bool weighted() const { return Om != nullptr; }
-    bool presence() const { return pres_M > 0; }
 
-    void *dalloc(size_t bytes, bool zero = true) {
-        if (bytes == 0) bytes = 16;
-        const size_t cls = DevBlockCache::size_class(bytes);
-        void *p = g_block_cache.take(device, cls);
-        if (!p) {
-            hipError_t e = hipMalloc(&p, cls);
-            if (e == hipErrorOutOfMemory) {        // the cache may be what is in the way: give its blocks back and retry once
-                (void)hipGetLastError();
-                g_block_cache.flush(device);
-                e = hipMalloc(&p, cls);
-            }
-            HIPCHK(e);
-        }
-        allocs.push_back({p, cls});
-        if (zero) HIPCHK(hipMemsetAsync(p, 0, bytes, stream));
-        return p;
-    }
-    // one block of the current problem back to the cache before the problem ends (callers have synchronised the stream)
-    void dfree(void *&p) {
-        for (size_t i = 0; i < allocs.size(); ++i) {
-            if (allocs[i].first != p) continue;
-            if (!g_block_cache.give(device, allocs[i].second, p)) (void)hipFree(p);
-            allocs.erase(allocs.begin() + (std::ptrdiff_t)i);
-            break;
-        }
-        p = nullptr;
-    }
     // The problem ends: its blocks go back to the cache and its state to the defaults.  Callers have synchronised the stream: no
     // kernel of this context still touches the blocks.
     void free_all() {
-        for (auto &b : allocs)
-            if (!g_block_cache.give(device, b.second, b.first)) (void)hipFree(b.first);
-        allocs.clear();
+        release_all();
         for (auto *v : {&ev_row, &ev_col, &ev_tail}) {
             for (auto &e : *v) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
             v->clear();
@@ -503,6 +565,26 @@ static const LossArgs kNoLoss{nullptr, 0, 0.0, nullptr, 0, nullptr, 0.0, nullptr
 struct Refusals { int v_overflow = 0, op_range = 0; };
 // api_context.hip
 DevSwitches problem_switches();
+// ... what contexts and batches share.  dst[row0 + i, col0 + j] = scale * src[row_idx ? row_idx[i] : i, j] on a matrix of row
+// length dld (k_place_V); dst[rows, cols] = mul * src[rows, cols] (k_copy_2d); `count` ones (k_fill) -- types by d64 / s64
+void place_rows(hipStream_t stream, void *dst, bool d64, int64_t dld, const void *dsrc, bool s64, int64_t rows, int64_t cols, int64_t ld,
+                int64_t row0, int64_t col0, double scale, const int64_t *row_idx);
+void copy_2d_any(hipStream_t stream, void *dst, bool d64, int64_t dld, const void *src, bool s64, int64_t sld, int64_t rows, int64_t cols,
+                 double mul = 1.0);
+void fill_ones(hipStream_t stream, void *dst, bool f64, int64_t count);
+// ... the mask of B problems of the shape n x f x k in `prec` (a context: B = 1, problem 0), blocks from `a`, state in `ps`.  Every
+// check comes before anything is taken or written: a refused call leaves the owner as it was.
+struct MaskDims { int64_t n, f, k; int B, prec; };
+void presence_check_args(const std::string &who, const MaskDims &d, int64_t rows, int64_t row0, bool rows_ok, const int64_t *col_bounds,
+                         int n_mod);
+void presence_check_bounds(const PresenceState &ps, const std::string &who, const char *owner, const int64_t *col_bounds, int n_mod);
+void presence_take(DeviceBlocks &a, PresenceState &ps, const MaskDims &d, const int64_t *col_bounds, int n_mod);
+void presence_upload(DeviceBlocks &a, PresenceState &ps, const MaskDims &d, int p, const void *src, int dtype, int64_t rows, int64_t ld,
+                     int64_t row0);
+void presence_rows_check(DeviceBlocks &a, const std::string &who, const int64_t *drow_idx, int64_t rows, int64_t src_rows);
+void presence_gather(DeviceBlocks &a, PresenceState &ps, const MaskDims &d, int p, const void *dP, int dtype, int64_t ld,
+                     const int64_t *drow_idx, int64_t rows, int64_t row0, const PresenceCols &cols);
+void presence_drop(DeviceBlocks &a, PresenceState &ps);
 void reset_state(klnmf_ctx *c);
 void fast_pack_H(klnmf_ctx *c, const unsigned *wmax = nullptr);
 void measure_and_pack(klnmf_ctx *c, bool from_init = false);

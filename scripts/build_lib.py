@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Builds the library for gfx950:  python scripts/build_lib.py OUT.so [-DFLAG ...]   (__graft_entry__.compile_library: seven
-translation units in parallel, the -D flags on every one; KLNMF_LIB=OUT.so selects the variant at run time)."""
+"""Builds the library for gfx950:  python scripts/build_lib.py OUT.so [-DFLAG ...]   (__graft_entry__.compile_library: every
+translation unit in parallel, the -D flags on every one; KLNMF_LIB=OUT.so selects the variant at run time)."""
 import os
 import sys
 

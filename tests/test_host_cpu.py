@@ -338,7 +338,7 @@ def test_build_staleness_sees_every_kernel_header():
     names = {os.path.basename(p) for p in ge._sources()}
     for must in ('ctx.hip.h', 'api_context.hip', 'api_loop.hip', 'api_comm.hip', 'api_eval.hip', 'mfma4.hip.h', 'colq.hip.h', 'colq8x.hip.h',
                  'post.hip.h', 'monitor.hip.h', 'exact.hip.h', 'sparse.hip.h', 'sparseb.hip.h', 'klnmf.h',
-                 'rowpass4_list.hip.h', 'rowpass4_inst_1.hip', 'rowpass4_inst_2.hip', 'rowpass4_inst_3.hip'):
+                 'rowpass4_list.hip.h', 'stage_chunks.h', 'api_batch.hip', 'rowpass4_inst_1.hip', 'rowpass4_inst_2.hip', 'rowpass4_inst_3.hip'):
         assert must in names
     if not os.path.exists(ge.LIB):
         assert ge._stale()
