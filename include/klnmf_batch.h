@@ -23,7 +23,7 @@ extern "C" {
  * max(1, cu_count / count) compute units: klnmf_plan_query(precision, n, f, k, -1, max(1, cu_count / count), ...); the
  * development switches KLNMF_EX_ROW_CHUNKS / _W_CHUNKS / _H_SEG force them as they force a context's.  A batch is a type of its
  * own: neither a mode of klnmf_ctx nor a klnmf_group.  Used from one thread at a time; it owns its stream.  (Row x modality
- * presence masks on the problems of a batch: klnmf_batch_mask.h.) */
+ * presence masks on the problems of a batch: klnmf_batch_mask.h; CSR problems on a batch: klnmf_batch_csr.h.) */
 typedef struct klnmf_batch klnmf_batch;
 #define KLNMF_BATCH_MAX 256
 /* KLNMF_ERR_UNSUPP for every precision but KLNMF_PREC_F64 / F32 (nothing is created), KLNMF_ERR_ARG unless 1 <= count <=

@@ -173,6 +173,16 @@ BATCH_MASK_SIGNATURES = {
     'klnmf_batch_clear_presence': (_c.c_int, [_c.c_void_p]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/klnmf_batch_csr.h (CSR problems on batches), which the same
+# library exports
+BATCH_CSR_SIGNATURES = {
+    'klnmf_batch_set_problem_sparse': (_c.c_int, [_c.c_void_p, _i64, _i64, _i64, _i64, _c.POINTER(_i64)]),
+    'klnmf_batch_upload_csr_rows': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    'klnmf_batch_upload_csr_device_rows': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p),
+                                                      _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_int), _c.POINTER(_i64),
+                                                      _c.POINTER(_c.c_double), _i64, _c.c_void_p, _i64]),
+}
+
 _lib = None
 
 
@@ -196,12 +206,22 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(BATCH_MASK_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(BATCH_MASK_SIGNATURES.items()) \
+            + list(BATCH_CSR_SIGNATURES.items()):
         fn = getattr(lib, name)     # AttributeError if a symbol is not exported
         fn.restype = res
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def csr_canonical(X):
+    """X as the CSR uploads take it: a scipy CSR copy without explicit zeros, indices sorted (nmf.py:66 does the same)."""
+    import scipy.sparse as sp
+    X = sp.csr_matrix(X, copy=True)
+    X.eliminate_zeros()
+    X.sort_indices()
+    return X
 
 
 def _check(status):
@@ -942,6 +962,45 @@ class Batch(object):
     def set_problem(self, n, f, k, max_iter_capacity):
         _check(self._lib.klnmf_batch_set_problem(self._h, int(n), int(f), int(k), max(1, int(max_iter_capacity))))
         self.n, self.f, self.k, self.cap = int(n), int(f), int(k), max(1, int(max_iter_capacity))
+
+    # ---- CSR problems (klnmf_batch_csr.h): every problem its own stored entries, one shape ----
+    def set_problem_sparse(self, n, f, k, max_iter_capacity, nnzs):
+        """`count` CSR problems of n x f with nnzs[p] stored entries each (klnmf_batch_set_problem_sparse); `upload_csr_rows` /
+        `upload_csr_device_rows` fill them.  Refused (NativeError, the previous problem stays): k > 512, an empty problem."""
+        nnzs = [int(v) for v in nnzs]
+        if len(nnzs) != self.count:
+            raise ValueError("%d nnz for a batch of %d" % (len(nnzs), self.count))
+        cap = max(1, int(max_iter_capacity))
+        _check(self._lib.klnmf_batch_set_problem_sparse(self._h, int(n), int(f), int(k), cap, (_i64 * self.count)(*nnzs)))
+        self.n, self.f, self.k, self.cap = int(n), int(f), int(k), cap
+        self.nnzs = nnzs
+
+    def upload_csr_rows(self, p, X):
+        """Problem p's X from a scipy CSR matrix (klnmf_batch_upload_csr_rows): explicit zeros dropped and indices sorted by the
+        caller -- `csr_canonical` -- so that X.nnz is the nnzs[p] the problem was set for."""
+        indptr = np.ascontiguousarray(X.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(X.indices, dtype=np.int64)
+        dt = np.float32 if X.dtype == np.float32 else np.float64
+        data = np.ascontiguousarray(X.data, dtype=dt)
+        ptr = lambda a: a.ctypes.data_as(_c.c_void_p)
+        _check(self._lib.klnmf_batch_upload_csr_rows(self._h, int(p), DT_F32 if dt == np.float32 else DT_F64, ptr(indptr), ptr(indices),
+                                                     ptr(data)))
+
+    def upload_csr_device_rows(self, p, sources, col_bounds, scales, src_rows, row_idx_ptr, rows):
+        """`Context.upload_csr_device_rows` for problem p (klnmf_batch_upload_csr_device_rows): synchronous."""
+        M = len(sources)
+        if len(col_bounds) != M + 1 or len(scales) != M:
+            raise ValueError("%d sources need %d column bounds and %d scales" % (M, M + 1, M))
+        ptrs = lambda j: (_c.c_void_p * M)(*[int(s[j]) or None for s in sources])
+        dts = (_c.c_int * M)(*[DT_F64 if s[3] else DT_F32 for s in sources])
+        cb = (_i64 * (M + 1))(*[int(b) for b in col_bounds])
+        sc = (_c.c_double * M)(*[float(v) for v in scales])
+        _check(self._lib.klnmf_batch_upload_csr_device_rows(self._h, int(p), M, ptrs(0), ptrs(1), ptrs(2), dts, cb, sc, int(src_rows),
+                                                            _c.c_void_p(row_idx_ptr), int(rows)))
+
+    def sparse_blocks(self):
+        """(column blocks, row blocks) of a CSR batch's plan, as `Context.query` answers them; (0, 0) for a dense batch."""
+        return (self.query(Q_SP_COL_BLOCKS), self.query(Q_SP_ROW_BLOCKS))
 
     def upload_V(self, p, block, row0=0, col0=0, scale=1.0):
         a = np.asarray(block)

@@ -4,9 +4,13 @@
 // sequence of an iteration is local_iteration's for a dense unweighted problem of the exact modes (api_loop.hip: exact_Q, exact_W,
 // exact_N, exact_H), stage for stage -- with a mask: for a dense masked problem (presence_S in front of the W rule, presence_D in
 // front of the H numerator).
+// A CSR batch (klnmf_batch_csr.h; batch_sparse.hip.h has the kernels and the layout): B unweighted CSR problems of one shape, each
+// with its own stored entries, on the blocked sparse kernels; the plan is plan_csr's for the batch's mean entries per problem, the
+// launch sequence local_iteration's for a blocked CSR problem (sparse_Q, the blocked arms of exact_W and exact_N, exact_H).
 #include "ctx.hip.h"
 #include "../../include/klnmf_batch.h"
 #include "../../include/klnmf_batch_mask.h"
+#include "../../include/klnmf_batch_csr.h"
 #include "batch.hip.h"
 
 struct klnmf_batch : DeviceBlocks, PresenceState {
@@ -21,6 +25,15 @@ struct klnmf_batch : DeviceBlocks, PresenceState {
     DevState *st = nullptr, *st_init = nullptr;         // [B]; st_init: the state every loop starts from
     double *errors = nullptr, *loss_xchg = nullptr, *loss_part = nullptr, *hpart = nullptr;
     void *V = nullptr, *Q = nullptr, *W[2] = {nullptr, nullptr}, *H = nullptr, *Npart = nullptr, *numer = nullptr, *Wpart = nullptr;
+    // ---- a CSR batch (sparse): per problem H^T, the block pointers, the slabs G / NT and the loss term's sums; per entry the
+    // problems' arrays one behind another, problem p's at off[p]; and the arrays ONE upload works in (u_*: a problem's own positions)
+    bool sparse = false;
+    std::vector<int64_t> nnz, off;                      // [B], [B + 1]
+    void *HT = nullptr, *sp_data = nullptr, *sp_q = nullptr, *sp_G = nullptr, *sp_NT = nullptr;
+    int *sp_idx32 = nullptr, *csc_rows32 = nullptr, *csc_perm32 = nullptr, *sp_bad = nullptr;
+    int64_t *sp_blkptr = nullptr, *csc_blkptr = nullptr;
+    double *sp_loss_part = nullptr, *sp_wpart = nullptr, *sp_prod = nullptr;
+    int64_t *u_indptr = nullptr, *u_indices = nullptr, *u_csc_indptr = nullptr, *u_csc_rows = nullptr, *u_csc_perm = nullptr, *u_work = nullptr;
     // (a masked batch: PresenceState, every problem's P, S, D and D's slabs and once per batch the bounds and the modality bytes --
     // taken by the first klnmf_batch_upload_presence*, dropped by klnmf_batch_clear_presence and with the problem)
 
@@ -30,6 +43,7 @@ struct klnmf_batch : DeviceBlocks, PresenceState {
         release_all();
         forget_presence();
         have_problem = false;
+        sparse = false;
     }
 };
 
@@ -229,9 +243,92 @@ void batch_H(klnmf_batch *b, bool from_slabs) {
     else batch_H_rule<T>(b, from_slabs, FacNum{});
 }
 
+// ---- a CSR batch's stages: api_loop.hip's sparse_Q and the blocked arms of exact_W / exact_N for B problems ----------------------
+// k_spb_*<T, KC, ..>: KC = 1, 2, 4, 8 component chunks of 64 by k, as a context picks them
+#define KL_BATCH_KC(b, LAUNCH)                                   \
+    do {                                                         \
+        const int kcb_ = (int)(((b)->k + 63) / 64);              \
+        if (kcb_ <= 1) LAUNCH(1); else if (kcb_ == 2) LAUNCH(2); \
+        else if (kcb_ <= 4) LAUNCH(4); else LAUNCH(8);           \
+    } while (0)
+
+template <typename T>
+void csr_transpose_H(klnmf_batch *b) {
+    hipLaunchKernelGGL((k_sp_transpose_H_batch<T>), dim3(grid_for(b->k * b->f), (unsigned)b->count), dim3(256), 0, b->stream,
+                       (const T *)b->H, (T *)b->HT, b->k, b->f, (const DevState *)b->st);
+    HIPCHK(hipGetLastError());
+}
+
+// the fused pass over the stored entries: SPB_UPDATE (ratio, loss partials, G) or SPB_INIT (G from the entries' values themselves)
+template <typename T, int MODE>
+void csr_qw(klnmf_batch *b) {
+    const ProblemPlan &pl = b->plan;
+    const dim3 grid((unsigned)((int64_t)pl.sp_cb * b->n), (unsigned)b->count);
+#define KL_BQW(KCV) hipLaunchKernelGGL((k_spb_qw_batch<T, KCV, MODE>), grid, dim3(64), 0, b->stream, (const int64_t *)b->sp_blkptr,        \
+        (const int *)b->sp_idx32, (const T *)b->sp_data, (const T *)b->W[b->cur], (const T *)b->HT, (T *)b->sp_q, b->sp_loss_part, (T *)b->sp_G, \
+        b->n, b->k, b->f, pl.sp_cb, (T)(MODE == SPB_INIT ? 0.0 : kEpsRatio), (const DevState *)b->st)
+    KL_BATCH_KC(b, KL_BQW);
+#undef KL_BQW
+    HIPCHK(hipGetLastError());
+}
+
+// ratio on the stored entries + loss + stop rule (sparse_Q)
+template <typename T>
+void csr_Q(klnmf_batch *b, int decide, double tol_abs) {
+    const ProblemPlan &pl = b->plan;
+    const unsigned B = (unsigned)b->count;
+    csr_transpose_H<T>(b);
+    csr_qw<T, SPB_UPDATE>(b);
+    hipLaunchKernelGGL((k_sp_colsum_part_batch<T>), dim3((unsigned)pl.sp_nblk, B), dim3(256), 0, b->stream, (const T *)b->W[b->cur],
+                       b->sp_wpart, b->n, b->k, (const DevState *)b->st);
+    if (pl.hseg_n > 1)
+        hipLaunchKernelGGL((k_sp_hsum_part_batch<T>), dim3((unsigned)pl.hseg_n, (unsigned)b->k, B), dim3(256), 0, b->stream, (const T *)b->H,
+                           b->f, pl.hseg, b->hpart, (const DevState *)b->st);
+    hipLaunchKernelGGL((k_sp_dots_batch<T>), dim3((unsigned)b->k, B), dim3(256), 0, b->stream, (const double *)b->sp_wpart, pl.sp_nblk,
+                       (const T *)b->H, b->k, b->f, b->sp_prod, (const DevState *)b->st,
+                       (const double *)(pl.hseg_n > 1 ? b->hpart : nullptr), pl.hseg_n > 1 ? pl.hseg_n : 0);
+    hipLaunchKernelGGL(k_sp_loss_batch, dim3(B), dim3(1024), 0, b->stream, (const double *)b->sp_loss_part, (int64_t)pl.sp_cb * b->n,
+                       (const double *)b->sp_prod, b->k, b->loss_xchg, b->st, decide, tol_abs, b->errors, b->cap);
+    HIPCHK(hipGetLastError());
+}
+
+// W_new = (multiply ? W : 1) * sum over the column blocks' slabs G -- which csr_Q left (multiply), or the SPB_INIT pass fills here
+template <typename T>
+void csr_W(klnmf_batch *b, int multiply) {
+    if (!multiply) csr_qw<T, SPB_INIT>(b);
+    hipLaunchKernelGGL((k_spb_wrule_batch<T>), dim3(grid_for(b->n * b->k, 256, 8192), (unsigned)b->count), dim3(256), 0, b->stream,
+                       (const T *)b->sp_G, b->plan.sp_cb, (const T *)b->W[b->cur], (T *)b->W[b->cur ^ 1], b->n, b->k, multiply,
+                       (const DevState *)b->st);
+    HIPCHK(hipGetLastError());
+}
+
+// numer = W[widx]^T . Q over the CSC order, row block by row block
+template <typename T>
+void csr_N(klnmf_batch *b, int widx) {
+    const ProblemPlan &pl = b->plan;
+    const dim3 grid((unsigned)((int64_t)pl.sp_rb * b->f), (unsigned)b->count);
+#define KL_BN(KCV) hipLaunchKernelGGL((k_spb_n_batch<T, KCV>), grid, dim3(64), 0, b->stream, (const int64_t *)b->csc_blkptr, (const int *)b->csc_rows32, \
+        (const int *)b->csc_perm32, (const T *)b->sp_q, (const T *)b->W[widx], (T *)b->sp_NT, b->n, b->k, b->f, pl.sp_rb, (const DevState *)b->st)
+    KL_BATCH_KC(b, KL_BN);
+#undef KL_BN
+    hipLaunchKernelGGL((k_spb_numer_batch<T>), dim3((unsigned)((b->f + 31) / 32), (unsigned)((b->k + 31) / 32), (unsigned)b->count), dim3(256),
+                       0, b->stream, (const T *)b->sp_NT, pl.sp_rb, (T *)b->numer, b->k, b->f, (const DevState *)b->st);
+    HIPCHK(hipGetLastError());
+}
+
 // one iteration for every problem (local_iteration of api_loop.hip): ratio + loss, stop rule, W rule, and in a fit the H rule;
 // masked: Q, then S and the W rule, and in a fit D, N and the H rule
 void batch_iteration(klnmf_batch *b, int fit, double tol_abs) {
+    if (b->sparse) {
+        BATCH_CALL(b, csr_Q, 1, tol_abs);
+        BATCH_CALL(b, csr_W, 1);
+        if (fit) {
+            BATCH_CALL(b, csr_N, b->cur ^ 1);
+            BATCH_CALL(b, batch_H, false);
+        }
+        b->cur ^= 1;
+        return;
+    }
     BATCH_CALL(b, batch_Q, 1, tol_abs);
     BATCH_CALL(b, batch_W, b->Q, 1);
     if (fit) {
@@ -250,6 +347,22 @@ bool read_states(klnmf_batch *b) {
     return std::all_of(b->last.begin(), b->last.end(), [](const DevState &s) { return s.stop != 0; });
 }
 
+void start_states(klnmf_batch *b);
+
+// what both kinds of problem hold: shape, plan, the problems' states, loss records and flags
+void take_common(klnmf_batch *b, const ProblemPlan &plan, int64_t n, int64_t f, int64_t k, int64_t cap) {
+    b->plan = plan;
+    b->n = n; b->f = f; b->k = k; b->cap = cap;
+    b->cur = 0;
+    const size_t B = (size_t)b->count;
+    b->has_V.assign(B, 0); b->has_H.assign(B, 0);
+    b->last.assign(B, DevState{});
+    b->st = (DevState *)b->dalloc(sizeof(DevState) * B);
+    b->st_init = (DevState *)b->dalloc(sizeof(DevState) * B);
+    b->errors = (double *)b->dalloc(sizeof(double) * B * (size_t)cap);
+    b->loss_xchg = (double *)b->dalloc(sizeof(double) * 2 * B);
+}
+
 void set_problem(klnmf_batch *b, int64_t n, int64_t f, int64_t k, int64_t cap) {
     const DevSwitches sw = problem_switches();
     const ProblemPlan plan = plan_dense_exact(n, f, k, b->prec, std::max(1, b->cu_count / b->count), sw);
@@ -261,16 +374,8 @@ void set_problem(klnmf_batch *b, int64_t n, int64_t f, int64_t k, int64_t cap) {
         fail(KLNMF_ERR_UNSUPP, "klnmf_batch_set_problem: more than 65535 chunks or components (gridDim.z, gridDim.y)");
     HIPCHK(hipStreamSynchronize(b->stream));
     b->free_all();
-    b->plan = plan;
-    b->n = n; b->f = f; b->k = k; b->cap = cap;
-    b->cur = 0;
+    take_common(b, plan, n, f, k, cap);
     const size_t B = (size_t)b->count, es = b->esize(), un = (size_t)n, uf = (size_t)f, uk = (size_t)k;
-    b->has_V.assign(B, 0); b->has_H.assign(B, 0);
-    b->last.assign(B, DevState{});
-    b->st = (DevState *)b->dalloc(sizeof(DevState) * B);
-    b->st_init = (DevState *)b->dalloc(sizeof(DevState) * B);
-    b->errors = (double *)b->dalloc(sizeof(double) * B * (size_t)cap);
-    b->loss_xchg = (double *)b->dalloc(sizeof(double) * 2 * B);
     b->V = b->dalloc(B * un * uf * es);
     b->Q = b->dalloc(B * un * uf * es);
     for (void *&w : b->W) w = b->dalloc(B * un * uk * es);
@@ -280,6 +385,101 @@ void set_problem(klnmf_batch *b, int64_t n, int64_t f, int64_t k, int64_t cap) {
     b->numer = b->dalloc(B * uk * uf * es);
     b->Wpart = plan.wsplit > 1 ? b->dalloc(B * (size_t)plan.wsplit * un * uk * es) : nullptr;
     b->loss_part = (double *)b->dalloc(sizeof(double) * B * (size_t)plan.loss_part_count);
+    start_states(b);
+}
+
+// what klnmf_batch_set_problem_sparse does: the refusals, then -- the previous problem released -- the CSR layout of batch_sparse.hip.h
+void set_problem_sparse(klnmf_batch *b, int64_t n, int64_t f, int64_t k, int64_t cap, const int64_t *nnz) {
+    const std::string who = "klnmf_batch_set_problem_sparse";
+    if (!nnz) fail(KLNMF_ERR_ARG, who + ": null nnz");
+    int64_t total = 0, most = 0;
+    bool empty = false;
+    for (int p = 0; p < b->count; ++p) {
+        if (nnz[p] < 0) fail(KLNMF_ERR_ARG, "n, f, k must be positive, nnz >= 0");
+        if (nnz[p] >= (int64_t)1 << 31) fail(KLNMF_ERR_UNSUPP, who + ": 2^31 or more stored entries in the batch (int32 positions)");      // (and the total cannot overflow)
+        empty = empty || nnz[p] == 0;
+        total += nnz[p];
+        most = std::max(most, nnz[p]);
+    }
+    const DevSwitches sw = problem_switches();
+    // one pair of block counts for every problem: the context's rule on the batch's mean entries per problem
+    const ProblemPlan plan = plan_csr(n, f, k, total / b->count, b->prec, b->cu_count, sw);
+    if (plan.refuse != KLNMF_OK) fail(plan.refuse, plan.refuse_msg);
+    if (k > 512) fail(KLNMF_ERR_UNSUPP, who + ": k > 512 has no blocked CSR kernels; run such problems one context each");
+    if (empty) fail(KLNMF_ERR_UNSUPP, who + ": a problem without stored entries has no blocked CSR kernels; run it in a context");
+    if (total >= (int64_t)1 << 31) fail(KLNMF_ERR_UNSUPP, who + ": 2^31 or more stored entries in the batch (int32 positions)");
+    if (!plan.sp_blocked) fail(KLNMF_ERR_UNSUPP, who + ": the shape has no blocked CSR regime");
+    HIPCHK(hipStreamSynchronize(b->stream));
+    b->free_all();
+    take_common(b, plan, n, f, k, cap);
+    b->sparse = true;
+    const size_t B = (size_t)b->count, es = b->esize(), un = (size_t)n, uf = (size_t)f, uk = (size_t)k, nz = (size_t)total, mz = (size_t)most;
+    b->nnz.assign(nnz, nnz + b->count);
+    b->off.assign(B + 1, 0);
+    for (size_t p = 0; p < B; ++p) b->off[p + 1] = b->off[p] + nnz[p];
+    for (void *&w : b->W) w = b->dalloc(B * un * uk * es);
+    b->H = b->dalloc(B * uk * uf * es);
+    b->HT = b->dalloc(B * uk * uf * es);
+    b->numer = b->dalloc(B * uk * uf * es);
+    b->hpart = plan.hseg_n > 1 ? (double *)b->dalloc(sizeof(double) * B * uk * (size_t)plan.hseg_n) : nullptr;
+    b->sp_data = b->dalloc(nz * es);
+    b->sp_q = b->dalloc(nz * es);
+    b->sp_idx32 = (int *)b->dalloc(sizeof(int) * nz);
+    b->csc_rows32 = (int *)b->dalloc(sizeof(int) * nz);
+    b->csc_perm32 = (int *)b->dalloc(sizeof(int) * nz);
+    b->sp_blkptr = (int64_t *)b->dalloc(sizeof(int64_t) * B * un * (size_t)(plan.sp_cb + 1));
+    b->csc_blkptr = (int64_t *)b->dalloc(sizeof(int64_t) * B * uf * (size_t)(plan.sp_rb + 1));
+    b->sp_loss_part = (double *)b->dalloc(sizeof(double) * B * (size_t)plan.sp_cb * un);
+    b->sp_G = b->dalloc(B * (size_t)plan.sp_cb * un * uk * es);
+    b->sp_NT = b->dalloc(B * (size_t)plan.sp_rb * uf * uk * es);
+    b->sp_wpart = (double *)b->dalloc(sizeof(double) * B * (size_t)plan.sp_nblk * uk);
+    b->sp_prod = (double *)b->dalloc(sizeof(double) * B * uk);
+    b->sp_bad = (int *)b->dalloc(sizeof(int));
+    b->u_indptr = (int64_t *)b->dalloc(sizeof(int64_t) * (un + 1));
+    b->u_indices = (int64_t *)b->dalloc(sizeof(int64_t) * mz);
+    b->u_csc_indptr = (int64_t *)b->dalloc(sizeof(int64_t) * (uf + 1));
+    b->u_csc_rows = (int64_t *)b->dalloc(sizeof(int64_t) * mz);
+    b->u_csc_perm = (int64_t *)b->dalloc(sizeof(int64_t) * mz);
+    int64_t work = 0;
+    for (int p = 0; p < b->count; ++p) work = std::max(work, csr_csc_work_elems(nnz[p]));
+    b->u_work = (int64_t *)b->dalloc(sizeof(int64_t) * (size_t)work);
+    start_states(b);
+}
+
+// problem p of a CSR batch as the shared upload steps see it: the upload's own arrays, and p's part of the batch's
+CsrParts csr_parts(klnmf_batch *b, int p) {
+    const ProblemPlan &pl = b->plan;
+    const int64_t o = b->off[(size_t)p];
+    return CsrParts{b->n, b->f, b->nnz[(size_t)p], b->prec, b->u_indptr, b->u_indices, b->u_csc_indptr, b->u_csc_rows, b->u_csc_perm, b->u_work,
+                    (char *)b->sp_data + (size_t)o * b->esize(), pl.sp_cb, pl.sp_rb, pl.sp_cb_cols, pl.sp_rb_rows,
+                    b->sp_blkptr + (int64_t)p * b->n * (pl.sp_cb + 1), b->csc_blkptr + (int64_t)p * b->f * (pl.sp_rb + 1), b->sp_idx32 + o,
+                    b->csc_rows32 + o, b->csc_perm32 + o, b->sp_bad};
+}
+
+void need_sparse(klnmf_batch *b, int p, const char *who) {
+    need_p(b, p);
+    if (!b->sparse) fail(KLNMF_ERR_ARG, std::string(who) + " needs klnmf_batch_set_problem_sparse");
+}
+
+// the device tail of an upload into problem p: CSC order, block pointers and int32 copies by the context's steps on the problem's
+// own positions, then the positions moved to the concatenated arrays
+void csr_finish_upload(klnmf_batch *b, int p, const CsrParts &v, const std::string &msg) {
+    csr_csc_build(b->stream, v);
+    csr_blocked_setup(b->stream, v, msg);
+    const int64_t o = b->off[(size_t)p], nb = b->n * (v.cb + 1), ncb = b->f * (v.rb + 1);
+    if (o > 0) {
+        hipLaunchKernelGGL(k_spb_shift, dim3(grid_for(nb, 256, 8192)), dim3(256), 0, b->stream, v.blkptr, nb, o);
+        hipLaunchKernelGGL(k_spb_shift, dim3(grid_for(ncb, 256, 8192)), dim3(256), 0, b->stream, v.cblkptr, ncb, o);
+        hipLaunchKernelGGL(k_spb_shift32, dim3(grid_for(v.nnz, 256, 8192)), dim3(256), 0, b->stream, v.perm32, v.nnz, (int)o);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(b->stream));
+    b->has_V[(size_t)p] = 1;
+}
+
+// the state every loop starts from, and the problems' states set to it
+void start_states(klnmf_batch *b) {
+    const size_t B = (size_t)b->count;
     // what k_reset_state leaves (common.hip.h), once: a loop's entry copies it over the problems' states
     DevState init{};
     init.prev_err = std::numeric_limits<double>::infinity();
@@ -294,6 +494,7 @@ void set_problem(klnmf_batch *b, int64_t n, int64_t f, int64_t k, int64_t cap) {
 
 // the shared argument checks of a mask upload (a batch holds no weights)
 void presence_check_all(klnmf_batch *b, const std::string &who, int64_t rows, int64_t row0, bool rows_ok, const int64_t *col_bounds, int n_mod) {
+    if (b->sparse) fail(KLNMF_ERR_UNSUPP, who + ": CSR problems have no masked kernels (the ratio lives on the stored entries only)");
     presence_check_args(who, b->mask_dims(), rows, row0, rows_ok, col_bounds, n_mod);
     presence_check_bounds(*b, who, "batch", col_bounds, n_mod);
 }
@@ -342,7 +543,7 @@ int klnmf_batch_destroy(klnmf_batch *b) {
 
 int klnmf_batch_set_problem(klnmf_batch *b, int64_t n, int64_t f, int64_t k, int64_t cap) {
     return guarded([&] {
-        use(b);
+        use(b);      // (a CSR problem before it goes with free_all, as a dense one before klnmf_batch_set_problem_sparse)
         if (cap < 0) fail(KLNMF_ERR_ARG, "n, f, k must be positive");
         set_problem(b, n, f, k, cap > 0 ? cap : 1);
     });
@@ -352,6 +553,7 @@ int klnmf_batch_upload_V(klnmf_batch *b, int p, const void *src, int dtype, int6
                          int64_t col0, double scale) {
     return guarded([&] {
         need_p(b, p);
+        if (b->sparse) fail(KLNMF_ERR_ARG, "klnmf_batch_upload_V: a CSR batch holds no dense V (klnmf_batch_upload_csr_rows)");
         if (!src) fail(KLNMF_ERR_ARG, "null source");
         check_dtype(dtype);
         check_block(b->n, b->f, rows, cols, ld, row0, col0);
@@ -366,6 +568,7 @@ int klnmf_batch_upload_V_device_rows_dt(klnmf_batch *b, int p, const void *dsrc,
                                         int64_t cols, int64_t ld, int64_t row0, int64_t col0, double scale) {
     return guarded([&] {
         need_p(b, p);
+        if (b->sparse) fail(KLNMF_ERR_ARG, "klnmf_batch_upload_V_device_rows_dt: a CSR batch holds no dense V (klnmf_batch_upload_csr_device_rows)");
         if (!dsrc) fail(KLNMF_ERR_ARG, "null source");
         check_dtype(dtype);
         check_block(b->n, b->f, rows, cols, ld, row0, col0);
@@ -411,7 +614,10 @@ int klnmf_batch_init_W(klnmf_batch *b) {
     return guarded([&] {
         need_problem(b);
         reset_states(b);
-        BATCH_CALL(b, batch_W, b->V, 0);
+        if (b->sparse) {      // W0 = X . H0^T over the stored entries (klnmf_init_W on a CSR context): H^T, the SPB_INIT pass, the W rule
+            BATCH_CALL(b, csr_transpose_H);
+            BATCH_CALL(b, csr_W, 0);
+        } else BATCH_CALL(b, batch_W, b->V, 0);
         b->cur ^= 1;
     });
 }
@@ -490,10 +696,53 @@ int klnmf_batch_query(klnmf_batch *b, int what, int64_t *value) {
         if (!value) fail(KLNMF_ERR_ARG, "null destination");
         if (what == KLNMF_Q_BATCH_COUNT) { *value = b->count; return; }
         if (what == KLNMF_Q_PRESENCE) { *value = (b->have_problem && b->presence()) ? b->pres_M : 0; return; }
+        if (what == KLNMF_Q_SP_COL_BLOCKS || what == KLNMF_Q_SP_ROW_BLOCKS) {
+            *value = 0;
+            if (b->have_problem) plan_answer(b->plan, what, value);
+            return;
+        }
         if (what != KLNMF_Q_EX_ROW_CHUNKS && what != KLNMF_Q_EX_W_CHUNKS && what != KLNMF_Q_EX_H_SEGMENTS && what != KLNMF_Q_EX_H_FROM_SLABS)
             fail(KLNMF_ERR_ARG, "klnmf_batch_query: unknown item");
         if (!b->have_problem) { *value = 0; return; }
         plan_answer(b->plan, what, value);
+    });
+}
+
+// ---- klnmf_batch_csr.h ---------------------------------------------------------------------------------------------------------
+int klnmf_batch_set_problem_sparse(klnmf_batch *b, int64_t n, int64_t f, int64_t k, int64_t cap, const int64_t *nnz) {
+    return guarded([&] {
+        use(b);
+        if (cap < 0) fail(KLNMF_ERR_ARG, "n, f, k must be positive, nnz >= 0");
+        set_problem_sparse(b, n, f, k, cap > 0 ? cap : 1, nnz);
+    });
+}
+
+// klnmf_upload_csr_rows for problem p
+int klnmf_batch_upload_csr_rows(klnmf_batch *b, int p, int dtype, const int64_t *indptr, const int64_t *indices, const void *data) {
+    return guarded([&] {
+        need_sparse(b, p, "klnmf_batch_upload_csr_rows");
+        if (!indptr || !indices || !data) fail(KLNMF_ERR_ARG, "null pointer");
+        check_dtype(dtype);
+        const CsrParts v = csr_parts(b, p);
+        if (indptr[0] != 0 || indptr[b->n] != v.nnz) fail(KLNMF_ERR_ARG, "klnmf_batch_upload_csr_rows: the row pointers do not match n, nnz[p]");
+        b->has_V[(size_t)p] = 0;
+        HIPCHK(hipMemcpyAsync(v.indptr, indptr, sizeof(int64_t) * (b->n + 1), hipMemcpyHostToDevice, b->stream));
+        HIPCHK(hipMemcpyAsync(v.indices, indices, sizeof(int64_t) * v.nnz, hipMemcpyHostToDevice, b->stream));
+        set_matrix(b, v.data, data, dtype, 1, v.nnz);      // (the values: a 1 x nnz matrix through the dtype conversion)
+        csr_finish_upload(b, p, v, "klnmf_batch_upload_csr_rows: the column indices of every row must be sorted");
+    });
+}
+
+// klnmf_upload_csr_device_rows for problem p
+int klnmf_batch_upload_csr_device_rows(klnmf_batch *b, int p, int n_mod, const int64_t *const *indptr, const int32_t *const *indices,
+                                       const void *const *data, const int *dtype, const int64_t *col_bounds, const double *scale,
+                                       int64_t src_rows, const int64_t *drow_idx, int64_t rows) {
+    return guarded([&] {
+        need_sparse(b, p, "klnmf_batch_upload_csr_device_rows");
+        const CsrParts v = csr_parts(b, p);
+        csr_gather_rows(*b, v, "klnmf_batch_upload_csr_device_rows", n_mod, indptr, indices, data, dtype, col_bounds, scale, src_rows,
+                        drow_idx, rows, [&] { b->has_V[(size_t)p] = 0; });
+        csr_finish_upload(b, p, v, "klnmf_batch_upload_csr_device_rows: the column indices of every source row must be sorted");
     });
 }
 

@@ -527,81 +527,159 @@ int klnmf_release_problem(klnmf_ctx *c) {
 
 }  // extern "C"
 
-namespace {
+namespace klnmf_host {
 
 // The blocked regime's structures of an uploaded CSR problem (sparseb.hip.h): block pointers by binary search in the sorted rows /
 // columns, int32 copies of the indices.  Refuses (`msg`) unsorted rows or columns.
-static void csr_blocked_setup(klnmf_ctx *c, const char *msg) {
-    if (!c->sp_blocked) return;
-    HIPCHK(hipMemsetAsync(c->sp_bad, 0, sizeof(int), c->stream));
-    hipLaunchKernelGGL(k_spb_blkptr, dim3(grid_for(c->n * (c->sp_cb + 1), 256, 1 << 20)), dim3(256), 0, c->stream,
-                       (const int64_t *)c->sp_indptr, (const int64_t *)c->sp_indices, c->n, c->sp_cb, c->sp_cb_cols, c->sp_blkptr, c->sp_bad);
-    hipLaunchKernelGGL(k_spb_blkptr, dim3(grid_for(c->f * (c->sp_rb + 1), 256, 1 << 20)), dim3(256), 0, c->stream,
-                       (const int64_t *)c->csc_indptr, (const int64_t *)c->csc_rows, c->f, c->sp_rb, c->sp_rb_rows, c->csc_blkptr, c->sp_bad);
-    hipLaunchKernelGGL(k_spb_narrow, dim3(grid_for(c->nnz, 256, 8192)), dim3(256), 0, c->stream, (const int64_t *)c->sp_indices, c->sp_idx32, c->nnz);
-    hipLaunchKernelGGL(k_spb_narrow, dim3(grid_for(c->nnz, 256, 8192)), dim3(256), 0, c->stream, (const int64_t *)c->csc_rows, c->csc_rows32, c->nnz);
-    hipLaunchKernelGGL(k_spb_narrow, dim3(grid_for(c->nnz, 256, 8192)), dim3(256), 0, c->stream, (const int64_t *)c->csc_perm, c->csc_perm32, c->nnz);
+void csr_blocked_setup(hipStream_t stream, const CsrParts &v, const std::string &msg) {
+    if (!v.blkptr) return;
+    HIPCHK(hipMemsetAsync(v.bad, 0, sizeof(int), stream));
+    hipLaunchKernelGGL(k_spb_blkptr, dim3(grid_for(v.n * (v.cb + 1), 256, 1 << 20)), dim3(256), 0, stream,
+                       (const int64_t *)v.indptr, (const int64_t *)v.indices, v.n, v.cb, v.cb_cols, v.blkptr, v.bad);
+    hipLaunchKernelGGL(k_spb_blkptr, dim3(grid_for(v.f * (v.rb + 1), 256, 1 << 20)), dim3(256), 0, stream,
+                       (const int64_t *)v.csc_indptr, (const int64_t *)v.csc_rows, v.f, v.rb, v.rb_rows, v.cblkptr, v.bad);
+    hipLaunchKernelGGL(k_spb_narrow, dim3(grid_for(v.nnz, 256, 8192)), dim3(256), 0, stream, (const int64_t *)v.indices, v.idx32, v.nnz);
+    hipLaunchKernelGGL(k_spb_narrow, dim3(grid_for(v.nnz, 256, 8192)), dim3(256), 0, stream, (const int64_t *)v.csc_rows, v.rows32, v.nnz);
+    hipLaunchKernelGGL(k_spb_narrow, dim3(grid_for(v.nnz, 256, 8192)), dim3(256), 0, stream, (const int64_t *)v.csc_perm, v.perm32, v.nnz);
     HIPCHK(hipGetLastError());
     int bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, c->sp_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpyAsync(&bad, v.bad, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
     if (bad) fail(KLNMF_ERR_ARG, msg);
 }
 
+int64_t csr_csc_work_elems(int64_t nnz) { return CscWork(nnz).elems; }
+
 // A refused upload leaves every row and column of the problem empty: no kernel reads the refused indices.
-static void csr_leave_empty(klnmf_ctx *c) {
-    HIPCHK(hipMemsetAsync(c->sp_indptr, 0, sizeof(int64_t) * (c->n + 1), c->stream));
-    HIPCHK(hipMemsetAsync(c->csc_indptr, 0, sizeof(int64_t) * (c->f + 1), c->stream));
-    if (c->sp_blocked) {
-        HIPCHK(hipMemsetAsync(c->sp_blkptr, 0, sizeof(int64_t) * c->n * (c->sp_cb + 1), c->stream));
-        HIPCHK(hipMemsetAsync(c->csc_blkptr, 0, sizeof(int64_t) * c->f * (c->sp_rb + 1), c->stream));
+void csr_leave_empty(hipStream_t stream, const CsrParts &v) {
+    HIPCHK(hipMemsetAsync(v.indptr, 0, sizeof(int64_t) * (v.n + 1), stream));
+    HIPCHK(hipMemsetAsync(v.csc_indptr, 0, sizeof(int64_t) * (v.f + 1), stream));
+    if (v.blkptr) {
+        HIPCHK(hipMemsetAsync(v.blkptr, 0, sizeof(int64_t) * v.n * (v.cb + 1), stream));
+        HIPCHK(hipMemsetAsync(v.cblkptr, 0, sizeof(int64_t) * v.f * (v.rb + 1), stream));
     }
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(stream));
 }
 
 // csc_indptr / csc_rows / csc_perm from the CSR structure already on the device (csc.hip.h), after checking it there.  Bad input is
 // refused before any pass runs, and leaves every row and column of the problem empty (no kernel reads the refused indices).
-static void csc_build(klnmf_ctx *c) {
-    const CscWork wk(c->nnz);
-    int64_t *counts = c->csc_work, *parts = c->csc_work + wk.m, *flag = c->csc_work + wk.flag_at();
-    HIPCHK(hipMemsetAsync(flag, 0, sizeof(int64_t), c->stream));
-    hipLaunchKernelGGL(k_csc_check, dim3(grid_for(std::max(c->n, c->nnz), 256, 8192)), dim3(256), 0, c->stream,
-                       (const int64_t *)c->sp_indptr, (const int64_t *)c->sp_indices, c->n, c->f, c->nnz, flag);
+void csr_csc_build(hipStream_t stream, const CsrParts &v) {
+    const CscWork wk(v.nnz);
+    int64_t *counts = v.csc_work, *parts = v.csc_work + wk.m, *flag = v.csc_work + wk.flag_at();
+    HIPCHK(hipMemsetAsync(flag, 0, sizeof(int64_t), stream));
+    hipLaunchKernelGGL(k_csc_check, dim3(grid_for(std::max(v.n, v.nnz), 256, 8192)), dim3(256), 0, stream,
+                       (const int64_t *)v.indptr, (const int64_t *)v.indices, v.n, v.f, v.nnz, flag);
     HIPCHK(hipGetLastError());
     int64_t bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, flag, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpyAsync(&bad, flag, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
     if (bad) {
-        csr_leave_empty(c);
+        csr_leave_empty(stream, v);
         fail(KLNMF_ERR_ARG, "klnmf_upload_csr_rows: the row pointers must not decrease, and the column indices of every row must be "
                             "sorted and lie in [0, f)");
     }
-    if (c->nnz > 0) {
+    if (v.nnz > 0) {
         int bits = 0;
-        while (bits < 62 && ((c->f - 1) >> bits) != 0) ++bits;
+        while (bits < 62 && ((v.f - 1) >> bits) != 0) ++bits;
         const int passes = std::max(1, (bits + kCscBits - 1) / kCscBits);
         const int64_t *src = nullptr;
         for (int p = 0; p < passes; ++p) {
             // the last pass writes csc_perm; csc_rows is the other buffer until k_csc_rows fills it
-            int64_t *dst = ((passes - 1 - p) & 1) == 0 ? c->csc_perm : c->csc_rows;
+            int64_t *dst = ((passes - 1 - p) & 1) == 0 ? v.csc_perm : v.csc_rows;
             const int shift = p * kCscBits;
-            hipLaunchKernelGGL(k_csc_hist, dim3((unsigned)wk.tiles), dim3(kCscThreads), 0, c->stream, src,
-                               (const int64_t *)c->sp_indices, c->nnz, shift, wk.tiles, counts);
-            hipLaunchKernelGGL(k_csc_scan_tiles, dim3((unsigned)wk.nparts), dim3(kCscThreads), 0, c->stream, counts, wk.m, parts);
-            hipLaunchKernelGGL(k_csc_scan_part, dim3(1), dim3(kCscThreads), 0, c->stream, parts, wk.nparts);
-            hipLaunchKernelGGL(k_csc_scan_add, dim3(grid_for(wk.m, 256, 8192)), dim3(256), 0, c->stream, counts, wk.m, (const int64_t *)parts);
-            hipLaunchKernelGGL(k_csc_scatter, dim3((unsigned)wk.tiles), dim3(kCscThreads), 0, c->stream, src,
-                               (const int64_t *)c->sp_indices, c->nnz, shift, wk.tiles, (const int64_t *)counts, dst);
+            hipLaunchKernelGGL(k_csc_hist, dim3((unsigned)wk.tiles), dim3(kCscThreads), 0, stream, src,
+                               (const int64_t *)v.indices, v.nnz, shift, wk.tiles, counts);
+            hipLaunchKernelGGL(k_csc_scan_tiles, dim3((unsigned)wk.nparts), dim3(kCscThreads), 0, stream, counts, wk.m, parts);
+            hipLaunchKernelGGL(k_csc_scan_part, dim3(1), dim3(kCscThreads), 0, stream, parts, wk.nparts);
+            hipLaunchKernelGGL(k_csc_scan_add, dim3(grid_for(wk.m, 256, 8192)), dim3(256), 0, stream, counts, wk.m, (const int64_t *)parts);
+            hipLaunchKernelGGL(k_csc_scatter, dim3((unsigned)wk.tiles), dim3(kCscThreads), 0, stream, src,
+                               (const int64_t *)v.indices, v.nnz, shift, wk.tiles, (const int64_t *)counts, dst);
             HIPCHK(hipGetLastError());
             src = dst;
         }
-        hipLaunchKernelGGL(k_csc_rows, dim3(grid_for(c->nnz, 256, 8192)), dim3(256), 0, c->stream, (const int64_t *)c->csc_perm,
-                           (const int64_t *)c->sp_indptr, c->n, c->nnz, c->csc_rows);
+        hipLaunchKernelGGL(k_csc_rows, dim3(grid_for(v.nnz, 256, 8192)), dim3(256), 0, stream, (const int64_t *)v.csc_perm,
+                           (const int64_t *)v.indptr, v.n, v.nnz, v.csc_rows);
     }
-    hipLaunchKernelGGL(k_csc_indptr, dim3(grid_for(c->f + 1, 256, 8192)), dim3(256), 0, c->stream, (const int64_t *)c->csc_perm,
-                       (const int64_t *)c->sp_indices, c->nnz, c->f, c->csc_indptr);
+    hipLaunchKernelGGL(k_csc_indptr, dim3(grid_for(v.f + 1, 256, 8192)), dim3(256), 0, stream, (const int64_t *)v.csc_perm,
+                       (const int64_t *)v.indices, v.nnz, v.f, v.csc_indptr);
     HIPCHK(hipGetLastError());
 }
+
+// The CSR of hstack([scale[m] * X_m[rows] ...]) gathered on the device from device-resident CSR modalities (csrgather.hip.h) into
+// v.indptr / v.indices / v.data.  Nothing of nnz length crosses the bus: the host reads back two words (the gathered total and the
+// flag) -- before the copy kernel runs, because its stores are in range only if the total is the problem's nnz.
+void csr_gather_rows(DeviceBlocks &a, const CsrParts &v, const std::string &who, int n_mod, const int64_t *const *indptr,
+                     const int32_t *const *indices, const void *const *data, const int *dtype, const int64_t *col_bounds,
+                     const double *scale, int64_t src_rows, const int64_t *drow_idx, int64_t rows,
+                     const std::function<void()> &before_write) {
+    if (n_mod < 1 || n_mod > KLNMF_MAX_MODALITIES)
+        fail(KLNMF_ERR_ARG, who + ": 1 <= n_mod <= KLNMF_MAX_MODALITIES (" + std::to_string(KLNMF_MAX_MODALITIES) + ")");
+    if (rows != v.n) fail(KLNMF_ERR_ARG, who + ": `rows` must be the problem's n");
+    if (src_rows < 0) fail(KLNMF_ERR_ARG, who + ": src_rows < 0");
+    if (!indptr || !indices || !data || !dtype || !col_bounds || !scale || !drow_idx) fail(KLNMF_ERR_ARG, who + ": null pointer");
+    if (col_bounds[0] != 0 || col_bounds[n_mod] != v.f) fail(KLNMF_ERR_ARG, who + ": the column bounds must run from 0 to f");
+    CsrSources S{};
+    S.src_rows = src_rows;
+    S.n_mod = n_mod;
+    for (int m = 0; m < n_mod; ++m) {
+        if (col_bounds[m] > col_bounds[m + 1]) fail(KLNMF_ERR_ARG, who + ": the column bounds must not decrease");
+        if (col_bounds[m + 1] - col_bounds[m] > (int64_t)std::numeric_limits<int32_t>::max())
+            fail(KLNMF_ERR_ARG, who + ": a modality of 2^31 columns or more (int32 source indices)");
+        check_dtype(dtype[m], who + ": " + kDtypeMsg);
+        if (!indptr[m] || (v.nnz > 0 && (!indices[m] || !data[m]))) fail(KLNMF_ERR_ARG, who + ": null pointer");
+        S.indptr[m] = indptr[m];
+        S.indices[m] = indices[m];
+        S.data[m] = data[m];
+        S.col0[m] = col_bounds[m];
+        S.scale[m] = scale[m];
+        if (dtype[m] == KLNMF_DT_F64) S.f64_mask |= 1u << m;
+    }
+    before_write();      // (every argument check is behind us: from here the problem's arrays change)
+    // row lengths -> exclusive scan in place (csc.hip.h's scan: fixed order, exact integers) -> indptr
+    const int64_t m1 = v.n + 1, nparts = (m1 + kCscScanTile - 1) / kCscScanTile;
+    void *tmp = a.dalloc(sizeof(int64_t) * (size_t)(nparts + 1));      // the scan's tile sums, then the flag (zero-filled)
+    int64_t *parts = (int64_t *)tmp, *flag = parts + nparts;
+    hipLaunchKernelGGL(k_csrg_len, dim3(grid_for(m1, kCsrgThreads, 8192)), dim3(kCsrgThreads), 0, a.stream, S, drow_idx, rows,
+                       v.indptr, flag);
+    hipLaunchKernelGGL(k_csc_scan_tiles, dim3((unsigned)nparts), dim3(kCscThreads), 0, a.stream, v.indptr, m1, parts);
+    hipLaunchKernelGGL(k_csc_scan_part, dim3(1), dim3(kCscThreads), 0, a.stream, parts, nparts);
+    hipLaunchKernelGGL(k_csc_scan_add, dim3(grid_for(m1, 256, 8192)), dim3(256), 0, a.stream, v.indptr, m1, (const int64_t *)parts);
+    HIPCHK(hipGetLastError());
+    int64_t bad = 0, total = -1;
+    HIPCHK(hipMemcpyAsync(&bad, flag, sizeof(int64_t), hipMemcpyDeviceToHost, a.stream));
+    HIPCHK(hipMemcpyAsync(&total, v.indptr + v.n, sizeof(int64_t), hipMemcpyDeviceToHost, a.stream));
+    HIPCHK(hipStreamSynchronize(a.stream));
+    a.dfree(tmp);
+    if (bad || total != v.nnz) {
+        csr_leave_empty(a.stream, v);
+        if (bad) fail(KLNMF_ERR_ARG, who + ": a row index outside [0, src_rows), or source row pointers that decrease");
+        fail(KLNMF_ERR_ARG, who + ": the rows hold " + std::to_string(total) + " stored entries, the problem was set for " +
+                            std::to_string(v.nnz));
+    }
+    if (v.nnz > 0) {
+        const int grid = grid_for(rows * kCsrgTrip, kCsrgThreads, 1 << 16);
+        if (v.prec == KLNMF_PREC_F64)
+            hipLaunchKernelGGL((k_csrg_copy<double>), dim3(grid), dim3(kCsrgThreads), 0, a.stream, S, drow_idx, rows,
+                               (const int64_t *)v.indptr, v.indices, (double *)v.data);
+        else
+            hipLaunchKernelGGL((k_csrg_copy<float>), dim3(grid), dim3(kCsrgThreads), 0, a.stream, S, drow_idx, rows,
+                               (const int64_t *)v.indptr, v.indices, (float *)v.data);
+        HIPCHK(hipGetLastError());
+    }
+}
+
+}  // namespace klnmf_host
+
+namespace {
+
+// a context's CSR problem as the shared upload steps see it
+CsrParts csr_parts(klnmf_ctx *c) {
+    return CsrParts{c->n, c->f, c->nnz, c->prec, c->sp_indptr, c->sp_indices, c->csc_indptr, c->csc_rows, c->csc_perm, c->csc_work,
+                    c->sp_data, c->sp_cb, c->sp_rb, c->sp_cb_cols, c->sp_rb_rows, c->sp_blocked ? c->sp_blkptr : nullptr, c->csc_blkptr,
+                    c->sp_idx32, c->csc_rows32, c->csc_perm32, c->sp_bad};
+}
+void csr_blocked_setup(klnmf_ctx *c, const char *msg) { csr_blocked_setup(c->stream, csr_parts(c), msg); }
+void csc_build(klnmf_ctx *c) { csr_csc_build(c->stream, csr_parts(c)); }
 
 }  // namespace
 
@@ -662,71 +740,16 @@ int klnmf_upload_csr_rows(klnmf_ctx *c, int dtype, const int64_t *indptr, const 
     });
 }
 
-// The CSR of hstack([scale[m] * X_m[rows] ...]) gathered on the device from device-resident CSR modalities (csrgather.hip.h), then
-// the device tail of klnmf_upload_csr_rows.  Nothing of nnz length crosses the bus: the host reads back two words (the gathered
-// total and the flag) -- before the copy kernel runs, because its stores are in range only if the total is the problem's nnz.
+// The CSR of hstack([scale[m] * X_m[rows] ...]) gathered on the device from device-resident CSR modalities (csr_gather_rows), then
+// the device tail of klnmf_upload_csr_rows.
 int klnmf_upload_csr_device_rows(klnmf_ctx *c, int n_mod, const int64_t *const *indptr, const int32_t *const *indices,
                                  const void *const *data, const int *dtype, const int64_t *col_bounds, const double *scale,
                                  int64_t src_rows, const int64_t *drow_idx, int64_t rows) {
     return guarded([&] {
         need_problem(c);
         if (!c->sparse) fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows needs klnmf_set_problem_sparse");
-        if (n_mod < 1 || n_mod > KLNMF_MAX_MODALITIES)
-            fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: 1 <= n_mod <= KLNMF_MAX_MODALITIES (" + std::to_string(KLNMF_MAX_MODALITIES) + ")");
-        if (rows != c->n) fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: `rows` must be the problem's n");
-        if (src_rows < 0) fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: src_rows < 0");
-        if (!indptr || !indices || !data || !dtype || !col_bounds || !scale || !drow_idx)
-            fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: null pointer");
-        if (col_bounds[0] != 0 || col_bounds[n_mod] != c->f)
-            fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: the column bounds must run from 0 to f");
-        CsrSources S{};
-        S.src_rows = src_rows;
-        S.n_mod = n_mod;
-        for (int m = 0; m < n_mod; ++m) {
-            if (col_bounds[m] > col_bounds[m + 1]) fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: the column bounds must not decrease");
-            if (col_bounds[m + 1] - col_bounds[m] > (int64_t)std::numeric_limits<int32_t>::max())
-                fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: a modality of 2^31 columns or more (int32 source indices)");
-            check_dtype(dtype[m], std::string("klnmf_upload_csr_device_rows: ") + kDtypeMsg);
-            if (!indptr[m] || (c->nnz > 0 && (!indices[m] || !data[m]))) fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: null pointer");
-            S.indptr[m] = indptr[m];
-            S.indices[m] = indices[m];
-            S.data[m] = data[m];
-            S.col0[m] = col_bounds[m];
-            S.scale[m] = scale[m];
-            if (dtype[m] == KLNMF_DT_F64) S.f64_mask |= 1u << m;
-        }
-        c->v_uploaded = false;
-        // row lengths -> exclusive scan in place (csc.hip.h's scan: fixed order, exact integers) -> sp_indptr
-        const int64_t m1 = c->n + 1, nparts = (m1 + kCscScanTile - 1) / kCscScanTile;
-        void *tmp = c->dalloc(sizeof(int64_t) * (size_t)(nparts + 1));      // the scan's tile sums, then the flag (zero-filled)
-        int64_t *parts = (int64_t *)tmp, *flag = parts + nparts;
-        hipLaunchKernelGGL(k_csrg_len, dim3(grid_for(m1, kCsrgThreads, 8192)), dim3(kCsrgThreads), 0, c->stream, S, drow_idx, rows,
-                           c->sp_indptr, flag);
-        hipLaunchKernelGGL(k_csc_scan_tiles, dim3((unsigned)nparts), dim3(kCscThreads), 0, c->stream, c->sp_indptr, m1, parts);
-        hipLaunchKernelGGL(k_csc_scan_part, dim3(1), dim3(kCscThreads), 0, c->stream, parts, nparts);
-        hipLaunchKernelGGL(k_csc_scan_add, dim3(grid_for(m1, 256, 8192)), dim3(256), 0, c->stream, c->sp_indptr, m1, (const int64_t *)parts);
-        HIPCHK(hipGetLastError());
-        int64_t bad = 0, total = -1;
-        HIPCHK(hipMemcpyAsync(&bad, flag, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(&total, c->sp_indptr + c->n, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        c->dfree(tmp);
-        if (bad || total != c->nnz) {
-            csr_leave_empty(c);
-            if (bad) fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: a row index outside [0, src_rows), or source row pointers that decrease");
-            fail(KLNMF_ERR_ARG, "klnmf_upload_csr_device_rows: the rows hold " + std::to_string(total) + " stored entries, the problem was set for " +
-                                std::to_string(c->nnz));
-        }
-        if (c->nnz > 0) {
-            const int grid = grid_for(rows * kCsrgTrip, kCsrgThreads, 1 << 16);
-            if (c->prec == KLNMF_PREC_F64)
-                hipLaunchKernelGGL((k_csrg_copy<double>), dim3(grid), dim3(kCsrgThreads), 0, c->stream, S, drow_idx, rows,
-                                   (const int64_t *)c->sp_indptr, c->sp_indices, (double *)c->sp_data);
-            else
-                hipLaunchKernelGGL((k_csrg_copy<float>), dim3(grid), dim3(kCsrgThreads), 0, c->stream, S, drow_idx, rows,
-                                   (const int64_t *)c->sp_indptr, c->sp_indices, (float *)c->sp_data);
-            HIPCHK(hipGetLastError());
-        }
+        csr_gather_rows(*c, csr_parts(c), "klnmf_upload_csr_device_rows", n_mod, indptr, indices, data, dtype, col_bounds, scale, src_rows,
+                        drow_idx, rows, [&] { c->v_uploaded = false; });
         csc_build(c);
         csr_blocked_setup(c, "klnmf_upload_csr_device_rows: the column indices of every source row must be sorted");
         HIPCHK(hipStreamSynchronize(c->stream));      // (drow_idx and the sources are the caller's: free to go from here)

@@ -21,8 +21,10 @@
 // h_product, block_sum, decide_here -- over the same chunk counts, so a problem in a batch has the bits of the same problem alone.
 // Stop state: one DevState per problem; the blocks of a stopped problem return at their first instruction, as every block of a
 // stopped context does, and nothing waits on anything.
+// CSR problems on a batch -- the batched forms of the sparse loop's kernels and their layout: batch_sparse.hip.h, included below.
 #pragma once
 #include "presence.hip.h"
+#include "batch_sparse.hip.h"
 
 namespace klnmf {
 

@@ -10,11 +10,12 @@
 //                    exchange of group.hip.h between their streams, the loop of klnmf_group_run
 //   api_batch.hip    a batch of dense problems of one shape in KLNMF_PREC_F64 / F32, unweighted or all under presence masks
 //                    (klnmf_batch_*): the [B] layout, the loop's stages as one launch each for all of them (batch.hip.h), the plan
-//                    of one problem for its share of the CUs
+//                    of one problem for its share of the CUs; and of CSR problems of one shape, each with its own stored entries
+//                    (klnmf_batch_csr.h, batch_sparse.hip.h)
 // This header: error handling, the type dispatch of the host-facing kernels, the device block cache and the arena over it
 // (DeviceBlocks), the staged host upload, the development switches, the mask state (PresenceState) and the context itself -- its
 // state in four groups, one per lifetime (ContextState, ProblemState, LoopState, LoopRecord) -- and what contexts and batches share
-// (defined once, in api_context.hip: the mask helpers, place_rows, copy_2d_any, fill_ones).  plan.hip.h: the launch plan of a
+// (defined once, in api_context.hip: the mask helpers, the steps of a CSR upload, place_rows, copy_2d_any, fill_ones).  plan.hip.h: the launch plan of a
 // problem, the value ProblemState is built on; stage_chunks.h: the chunk arithmetic of staged_upload, free of HIP.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,6 +27,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <map>
 #include <mutex>
@@ -585,6 +587,27 @@ void presence_rows_check(DeviceBlocks &a, const std::string &who, const int64_t 
 void presence_gather(DeviceBlocks &a, PresenceState &ps, const MaskDims &d, int p, const void *dP, int dtype, int64_t ld,
                      const int64_t *drow_idx, int64_t rows, int64_t row0, const PresenceCols &cols);
 void presence_drop(DeviceBlocks &a, PresenceState &ps);
+// ... the upload of ONE CSR problem (a context's, or problem p of a CSR batch): its arrays on the device and the steps both owners
+// run on them.  indptr .. csc_work hold the problem's own positions 0 .. nnz; blkptr == nullptr: no blocked regime.  A batch points
+// idx32 / rows32 / perm32 and the block pointers at problem p's part of its concatenated arrays and moves the positions afterwards.
+struct CsrParts {
+    int64_t n, f, nnz;
+    int prec;
+    int64_t *indptr, *indices, *csc_indptr, *csc_rows, *csc_perm, *csc_work;
+    void *data;
+    int cb, rb;
+    int64_t cb_cols, rb_rows;
+    int64_t *blkptr, *cblkptr;
+    int *idx32, *rows32, *perm32, *bad;
+};
+int64_t csr_csc_work_elems(int64_t nnz);      // int64 elements of csc_work for a problem of nnz stored entries (csc.hip.h, CscWork)
+void csr_leave_empty(hipStream_t stream, const CsrParts &v);
+void csr_csc_build(hipStream_t stream, const CsrParts &v);
+void csr_blocked_setup(hipStream_t stream, const CsrParts &v, const std::string &msg);
+void csr_gather_rows(DeviceBlocks &a, const CsrParts &v, const std::string &who, int n_mod, const int64_t *const *indptr,
+                     const int32_t *const *indices, const void *const *data, const int *dtype, const int64_t *col_bounds,
+                     const double *scale, int64_t src_rows, const int64_t *drow_idx, int64_t rows,
+                     const std::function<void()> &before_write);
 void reset_state(klnmf_ctx *c);
 void fast_pack_H(klnmf_ctx *c, const unsigned *wmax = nullptr);
 void measure_and_pack(klnmf_ctx *c, bool from_init = false);

@@ -21,11 +21,9 @@ namespace klnmf {
 template <typename T>
 __global__ void k_sp_transpose_H(const T *H, T *HT, int64_t k, int64_t f, const DevState *st) {
     if (st && st->stop) return;
-    const int64_t total = k * f;
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t j = e / k, a = e % k;
-        HT[e] = H[a * f + j];
-    }
+#define KL_SP_BODY_TRANSPOSE
+#include "sparse_body.hip.h"
+#undef KL_SP_BODY_TRANSPOSE
 }
 
 // Lane u of the wave receives the value lane u holds in `v`, as a wave-uniform (scalar) number.
@@ -173,24 +171,18 @@ constexpr int kSpColsumRows = 32;
 template <typename T>
 __global__ __launch_bounds__(256) void k_sp_colsum_part(const T *W, double *part, int64_t n, int64_t k, const DevState *st) {
     if (st && st->stop) return;
-    const int64_t r0 = blockIdx.x * (int64_t)kSpColsumRows, r1 = min(n, r0 + kSpColsumRows);
-    for (int64_t a = threadIdx.x; a < k; a += blockDim.x) {
-        double s = 0;
-        for (int64_t i = r0; i < r1; ++i) s += (double)W[i * k + a];
-        part[blockIdx.x * k + a] = s;
-    }
+#define KL_SP_BODY_COLSUM
+#include "sparse_body.hip.h"
+#undef KL_SP_BODY_COLSUM
 }
 
 // Row sums of H in S segments (long rows: one block per component walked 880 KB at f = 110 000): hpart[a][s].
 template <typename T>
 __global__ __launch_bounds__(256) void k_sp_hsum_part(const T *H, int64_t f, int64_t seg, double *hpart, const DevState *st) {
     if (st && st->stop) return;
-    __shared__ double red[16];
-    const int64_t a = blockIdx.y, j0 = blockIdx.x * seg, j1 = min(f, j0 + seg);
-    double hs = 0;
-    for (int64_t j = j0 + threadIdx.x; j < j1; j += blockDim.x) hs += (double)H[a * f + j];
-    const double t = block_sum(hs, red);
-    if (threadIdx.x == 0) hpart[a * gridDim.x + blockIdx.x] = t;
+#define KL_SP_BODY_HSUM
+#include "sparse_body.hip.h"
+#undef KL_SP_BODY_HSUM
 }
 
 // prod[a] = colsum(W)_a * rowsum(H)_a ; one block per component, fixed order.  hpart != nullptr: the row sum from its S
@@ -199,17 +191,9 @@ template <typename T>
 __global__ __launch_bounds__(256) void k_sp_dots(const double *wpart, int64_t nblk, const T *H, int64_t k, int64_t f,
                                                   double *prod, const DevState *st, const double *hpart = nullptr, int S = 0) {
     if (st && st->stop) return;
-    __shared__ double red[16];
-    const int64_t a = blockIdx.x;
-    double hs = 0, ws = 0;
-    if (hpart != nullptr) {
-        if (threadIdx.x == 0) for (int z = 0; z < S; ++z) hs += hpart[a * S + z];
-    } else
-    for (int64_t j = threadIdx.x; j < f; j += blockDim.x) hs += (double)H[a * f + j];
-    for (int64_t b = threadIdx.x; b < nblk; b += blockDim.x) ws += wpart[b * k + a];
-    const double hsum = block_sum(hs, red);
-    const double wsum = block_sum(ws, red);
-    if (threadIdx.x == 0) prod[a] = hsum * wsum;
+#define KL_SP_BODY_DOTS
+#include "sparse_body.hip.h"
+#undef KL_SP_BODY_DOTS
 }
 
 // loss = sum_i row_loss[i] + sum_a prod[a] ; one block, fixed order.
@@ -217,12 +201,9 @@ KL_GLOBAL __launch_bounds__(1024) void k_sp_loss(const double *row_loss, int64_t
                                                    double *out, const DevState *st,
                                                    DecideArgs dec = DecideArgs{0, nullptr, 0.0, nullptr, 0}) {
     if (st && st->stop) return;
-    __shared__ double red[16];
-    double s = 0;
-    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) s += row_loss[i];
-    for (int64_t a = threadIdx.x; a < k; a += blockDim.x) s += prod[a];
-    const double t = block_sum(s, red);
-    if (threadIdx.x == 0) { out[0] = t; out[1] = 0; decide_here(dec, t); }
+#define KL_SP_BODY_LOSS
+#include "sparse_body.hip.h"
+#undef KL_SP_BODY_LOSS
 }
 
 }  // namespace klnmf

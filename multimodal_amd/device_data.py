@@ -50,6 +50,16 @@ def csr_rows_plan(indptrs, rows, coefs, minima):
     return nnz, use_device
 
 
+class _ProblemOf(object):
+    """Problem p of a `_native.Batch` with a context's upload methods: what `DeviceDataset._sparse_uploader`'s upload calls."""
+
+    def __init__(self, batch, p):
+        self.batch, self.p = batch, p
+
+    def upload_csr_device_rows(self, *args):
+        self.batch.upload_csr_device_rows(self.p, *args)
+
+
 def check_presence(presence, n_samples, n_modalities):
     """`presence` of `DeviceDataset` as it is kept: (P, masked) -- P the float64 [n_samples, n_modalities] mask, the column of a
     modality without an array all 1, and masked[m] whether modality m came with an array; (None, [False ...]) where no entry is
@@ -242,8 +252,7 @@ class DeviceDataset(object):
 
     def _fit_sparse(self, nmf, which, rows, coefs, _fit):
         upload, n, nnz, use_device = self._sparse_uploader(which, rows, coefs)
-        all32 = all(not self.csr[w].f64 for w in which)
-        out_dtype_of = lambda H: np.float32 if (all32 and H.dtype == np.float32) else np.float64      # (as `_fit_blocks` on CSR)
+        out_dtype_of = self._sparse_out_dtype(which)
         if use_device:
             return nmf._fit_uploaded(n, sum(self.dims[w] for w in which), upload, out_dtype_of, _fit=_fit, sparse_nnz=nnz)
         X = self._host_csr(which, rows, coefs)
@@ -382,9 +391,37 @@ class DeviceDataset(object):
             return None
         return batch_precision(nmfs, len(rows_list[0]), n_features, weighted=masked)
 
+    def _batch_route_sparse(self, which, rows_list, coefs_list, nmfs, n_features):
+        """(precision, uploads, nnzs) if the calls on `rows_list` can run as one CSR batch (klnmf_batch_csr.h): the selection runs
+        the sparse branch without a mask, the row lists have one length, every problem's `csr_rows_plan` allows the device gather
+        and finds stored entries, and the models are as `batch_precision(sparse=True)` asks (k <= 512 among it).  uploads[p](batch, p)
+        gathers problem p on the device (`Batch.upload_csr_device_rows`).  None: the loop over the single calls -- ONE problem that
+        needs the host path (a coefficient of 0) sends the whole call there.  ValueError for a masked selection that includes a
+        CSR modality (`presence_route`)."""
+        if not nmfs or len(set(len(r) for r in rows_list)) != 1:
+            return None
+        if self.presence_route(which) or not self.sparse_route(which):
+            return None
+        prec = batch_precision(nmfs, len(rows_list[0]), n_features, sparse=True)
+        if prec is None:
+            return None
+        uploads, nnzs = [], []
+        for rows, coefs in zip(rows_list, coefs_list):
+            upload, _, nnz, use_device = self._sparse_uploader(which, rows, coefs)
+            if not use_device or nnz == 0:
+                return None
+            uploads.append(lambda batch, p, upload=upload: upload(_ProblemOf(batch, p)))
+            nnzs.append(nnz)
+        return prec, uploads, nnzs
+
+    def _sparse_out_dtype(self, which):
+        all32 = all(not self.csr[w].f64 for w in which)
+        return lambda H: np.float32 if (all32 and H.dtype == np.float32) else np.float64      # (as `_fit_blocks` on CSR)
+
     def train_many(self, learners, rows_list, iterations, init_dictionaries=None):
-        """[self.train(l, rows, iterations, init) for l, rows, init in ...] -- as ONE batch where all row lists have one length,
-        all learners share k and no modality is kept as CSR; the loop over `train` otherwise.  With a presence mask on the
+        """[self.train(l, rows, iterations, init) for l, rows, init in ...] -- as ONE batch where all row lists have one length and
+        all learners share k: the dense batch, or where a modality is kept as CSR the CSR batch (`_batch_route_sparse`); the loop
+        over `train` otherwise.  With a presence mask on the
         dataset the batch is the masked one: `last_weights_route` 'presence' here and on every `learner.nmf_train`."""
         learners, rows_list = list(learners), [list(r) for r in rows_list]
         inits = list(init_dictionaries) if init_dictionaries is not None else [None] * len(learners)
@@ -397,6 +434,16 @@ class DeviceDataset(object):
             nmfs.append(nmf)
         plain = all(l.sparseness is None and self.dims == list(l.dim) for l in learners)
         prec = self._batch_route(which, rows_list, nmfs, sum(self.dims)) if plain else None
+        csr = self._batch_route_sparse(which, rows_list, [list(l.coef) for l in learners], nmfs, sum(self.dims)) \
+            if plain and prec is None else None
+        if csr is not None:
+            fit_uploaded_batch(nmfs, csr[0], len(rows_list[0]), sum(self.dims), csr[1], [self._sparse_out_dtype(which)] * len(nmfs),
+                               _fit=True, sparse_nnzs=csr[2])
+            self.last_weights_route = None
+            for learner, nmf in zip(learners, nmfs):
+                learner.nmf_train = nmf
+                learner.dico = nmf.components_
+            return learners
         if prec is None:
             return [self.train(l, rows, iterations, init_dictionary=init) for l, rows, init in zip(learners, rows_list, inits)]
         masked = self.presence_route(which)
@@ -426,6 +473,12 @@ class DeviceDataset(object):
         same = all([l.get_index(m) for m in orig_mods] == which and list(l.dim) == self.dims for l in learners)
         n_features = sum(self.dims[w] for w in which)
         prec = self._batch_route(which, rows_list, nmfs, n_features) if same else None
+        csr = self._batch_route_sparse(which, rows_list, [[l.coef[w] for w in which] for l in learners], nmfs, n_features) \
+            if same and prec is None else None
+        if csr is not None:
+            self.last_weights_route = None
+            return fit_uploaded_batch(nmfs, csr[0], len(rows_list[0]), n_features, csr[1], [self._sparse_out_dtype(which)] * len(nmfs),
+                                      _fit=False, sparse_nnzs=csr[2])
         if prec is None:
             return [self.reconstruct_internal_multi(l, orig_mods, rows, iterations) for l, rows in zip(learners, rows_list)]
         masked = self.presence_route(which)
@@ -502,8 +555,8 @@ class DeviceEvaluation(object):
     @staticmethod
     def internal_many(evaluations, mods, rows_list):
         """[ev.internal(mods, rows) for ev, rows in ...] for the evaluations of a sweep's runs -- as ONE batch where they share the
-        dataset, k, the iteration count and the number of rows, no selected modality is kept as CSR and the shape runs in
-        f64 / f32 (a masked selection: the masked batch, `last_weights_route` 'presence' on every evaluation): the dictionaries go
+        dataset, k, the iteration count and the number of rows and the shape runs in f64 / f32 -- with a selected modality kept as
+        CSR: the CSR batch, `DeviceDataset._batch_route_sparse` -- (a masked selection: the masked batch, `last_weights_route` 'presence' on every evaluation): the dictionaries go
         in by klnmf_batch_set_H_device, the coefficients stay on the device (klnmf_batch_get_W_device).  The loop over `internal`
         otherwise."""
         evaluations, rows_list = list(evaluations), list(rows_list)
@@ -517,6 +570,22 @@ class DeviceEvaluation(object):
                    for ev in evaluations)
         n, f = len(rows_list[0]), sum(lr.dim[w] for w in which)
         prec = ds._batch_route(which, rows_list, models, f) if same else None
+        csr = ds._batch_route_sparse(which, rows_list, [[ev.learner.coef[w] for w in which] for ev in evaluations], models, f) \
+            if same and prec is None else None
+        if csr is not None:      # the CSR batch: gathered on the device, dictionaries and coefficients as below
+            outs = [torch.empty((n, ev.k), dtype=torch.float64, device=ev.dev) for ev in evaluations]
+            with _native.Batch(csr[0], len(evaluations), device=models[0].device) as batch:
+                batch.set_problem_sparse(n, f, first.k, first.iter_test, csr[2])
+                for p, ev in enumerate(evaluations):
+                    csr[1][p](batch, p)
+                    ev._set_dictionary(batch, which, p)
+                    ev.last_weights_route = models[p].last_weights_route = None
+                batch.init_W()
+                batch.run(first.iter_test, False, 0.0)
+                for p, out in enumerate(outs):
+                    batch.get_W_device(p, out.data_ptr(), True, first.k)
+            torch.cuda.synchronize(first.dev)
+            return outs
         if prec is None:
             return [ev.internal(mods, rows) for ev, rows in zip(evaluations, rows_list)]
         masked = ds.presence_route(which)

@@ -318,7 +318,8 @@ def run_sweep(data_matrices, labels, modalities, ks, n_runs, iter_train=50, iter
     stay 1 / the mean row sum over all samples, absent ones included.
     batch: each worker runs its (k, run) pairs of equal k in batches of at most `batch` (`sweep_batches`): the trainings and the
     evaluations' internal transforms of a batch as one launch sequence (klnmf_batch_*) where the shapes allow it (dense
-    modalities, f64 / f32; with `presence`: the masked batch, every run its own rows of the mask); 1 (default): one pair after
+    modalities, f64 / f32; with `presence`: the masked batch, every run its own rows of the mask; with `keep_sparse`: the CSR
+    batch, every run its own stored entries, k <= 512); 1 (default): one pair after
     another, as before."""
     import torch
     if keep_sparse:

@@ -785,11 +785,16 @@ def _exact_loop_report(precision, device):
     return copy.deepcopy(_EXACT_LOOP_REPORT[key])
 
 
-def batch_precision(models, n, f, weighted=False):
+CSR_BATCH_MAX_K = 512      # klnmf_batch_set_problem_sparse refuses more components (csrc/sparseb.hip.h: the blocked regime's limit)
+
+
+def batch_precision(models, n, f, weighted=False, sparse=False):
     """'f64' / 'f32' if `models` can run as ONE batch of dense n x f problems (klnmf_batch_*): they agree in n_components, tol,
     max_iter and precision, that precision resolves to f64 or f32 for the shape (`resolve_precision`), and every model is on
     one and the same single device.  None otherwise.  weighted: a batch of masked problems -- the arithmetic is
-    `weighted_precision`'s, which is what the single masked call runs in ('auto' -> f64, the 16-bit modes -> f32)."""
+    `weighted_precision`'s, which is what the single masked call runs in ('auto' -> f64, the 16-bit modes -> f32).  sparse: a
+    batch of CSR problems -- `sparse_precision`'s arithmetic, with its stderr note, and k <= CSR_BATCH_MAX_K (the blocked sparse
+    kernels; beyond, a context runs the unblocked ones)."""
     first = models[0]
     same = all((m.n_components, m.tol, m.max_iter, m.precision, m.devices) ==
                (first.n_components, first.tol, first.max_iter, first.precision, first.devices) for m in models)
@@ -797,15 +802,20 @@ def batch_precision(models, n, f, weighted=False):
         return None
     if weighted:
         return weighted_precision(first.precision)
+    if sparse:
+        return sparse_precision(first.precision) if (first.n_components or f) <= CSR_BATCH_MAX_K else None
     prec = resolve_precision(first.precision, n, f, first.n_components or f)
     return prec if _native.PRECISIONS[prec] in (_native.PREC_F64, _native.PREC_F32) else None
 
 
-def fit_uploaded_batch(models, precision, n_samples, n_features, uploads, out_dtype_ofs, _fit=True, return_errors=False, masked=False):
+def fit_uploaded_batch(models, precision, n_samples, n_features, uploads, out_dtype_ofs, _fit=True, return_errors=False, masked=False,
+                       sparse_nnzs=None):
     """`KLdivNMF._fit_uploaded` for len(models) dense problems of one shape as one `_native.Batch`: problem p is placed by
     `uploads[p](batch, p)`; model p ends as its own `_fit_uploaded` would leave it, with `last_batch_size` set.  masked: the
     uploads place a presence mask behind every V (`Batch.upload_presence*`, one set of bounds) and the loop is the masked one;
-    every model ends with `last_weights_route` 'presence' (None otherwise).  Returns the list of the calls' results."""
+    every model ends with `last_weights_route` 'presence' (None otherwise).  sparse_nnzs: the problems are CSR ones of
+    sparse_nnzs[p] stored entries (`Batch.set_problem_sparse`) that the uploads fill with `Batch.upload_csr_rows` /
+    `upload_csr_device_rows`.  Returns the list of the calls' results."""
     B = len(models)
     max_iter = int(models[0].max_iter)
     H_inits = []
@@ -817,7 +827,10 @@ def fit_uploaded_batch(models, precision, n_samples, n_features, uploads, out_dt
     k = models[0].n_components
     tol_abs = models[0].tol * n_samples * n_features      # nmf.py:207
     with _native.Batch(precision, B, device=models[0].device) as batch:
-        batch.set_problem(n_samples, n_features, k, max_iter)
+        if sparse_nnzs is not None:
+            batch.set_problem_sparse(n_samples, n_features, k, max_iter, sparse_nnzs)
+        else:
+            batch.set_problem(n_samples, n_features, k, max_iter)
         for p in range(B):
             uploads[p](batch, p)
             batch.set_H(p, H_inits[p])
@@ -854,7 +867,12 @@ def fit_transform_batch(models, Xs, weights=None, _fit=True, return_errors=False
     then one launch for all problems (csrc/batch.hip.h); each model stops on its own loss record.  Otherwise (an entry that
     routes to 'array' among them) the models run one after another through `fit_transform`, unchanged.  Each model gets
     `last_batch_size`: the batch's size, or 1.  The initial dictionaries are drawn in list order (or taken from
-    `_init_dictionary`), so the global numpy stream is consumed exactly as by the sequential calls."""
+    `_init_dictionary`), so the global numpy stream is consumed exactly as by the sequential calls.
+
+    CSR input: every X scipy-sparse, of one shape, each with stored entries, k <= CSR_BATCH_MAX_K, no array `weights` and models as
+    `batch_precision` asks run as ONE CSR batch (csrc/batch_sparse.hip.h) -- the reference's sparse branch in the arithmetic
+    `sparse_precision` names, validation and output dtype as `_fit_blocks` on CSR.  A mix of dense and sparse Xs runs one after
+    another."""
     models, Xs = list(models), list(Xs)
     if len(models) != len(Xs):
         raise ValueError("fit_transform_batch: one X per model expected (%d models, %d Xs)" % (len(models), len(Xs)))
@@ -862,6 +880,11 @@ def fit_transform_batch(models, Xs, weights=None, _fit=True, return_errors=False
         weights = list(weights)
         if len(weights) != len(models):
             raise ValueError("fit_transform_batch: one weights entry per model expected (%d models, %d entries)" % (len(models), len(weights)))
+    if Xs and all(sp.issparse(X) for X in Xs) and len(set(X.shape for X in Xs)) == 1 and \
+            (weights is None or all(w is None or np.ndim(w) == 0 for w in weights)):
+        outs = _fit_transform_batch_csr(models, Xs, _fit, return_errors)
+        if outs is not None:
+            return outs
     dense = bool(Xs) and not any(sp.issparse(X) for X in Xs)
     if dense:
         Xs = [atleast2d_or_csr(X) for X in Xs]
@@ -895,3 +918,22 @@ def fit_transform_batch(models, Xs, weights=None, _fit=True, return_errors=False
         uploads = [lambda batch, p, b=b: batch.upload_V(p, b) for b in blocks]
     out_dtype_ofs = [lambda H_init, b=b: _out_dtype(H_init, b) for b in blocks]
     return fit_uploaded_batch(models, precision, n, f, uploads, out_dtype_ofs, _fit=_fit, return_errors=return_errors, masked=masked)
+
+
+def _fit_transform_batch_csr(models, Xs, _fit, return_errors):
+    """`fit_transform_batch`'s CSR batch for scipy-sparse Xs of one shape; None where the sequential route has to run (the models
+    do not agree, k > CSR_BATCH_MAX_K, an X without stored entries)."""
+    n, f = Xs[0].shape
+    for X in Xs:                       # (`fit_transform`'s validation, `_fit_blocks`'s stack of one block)
+        check_non_negative(atleast2d_or_csr(X), "NMF.fit")
+    mats = [_native.csr_canonical(_csr_of([atleast2d_or_csr(X)], [1.])) for X in Xs]
+    if any(X.nnz == 0 for X in mats) or not 1 <= len(models) <= _native.BATCH_MAX:
+        return None
+    precision = batch_precision(models, n, f, sparse=True)
+    if precision is None:
+        return None
+    uploads = [lambda batch, p, X=X: batch.upload_csr_rows(p, X) for X in mats]
+    out_dtype_ofs = [lambda H_init, X=X: np.float32 if (X.dtype == np.float32 and H_init.dtype == np.float32) else np.float64
+                     for X in mats]
+    return fit_uploaded_batch(models, precision, n, f, uploads, out_dtype_ofs, _fit=_fit, return_errors=return_errors,
+                              sparse_nnzs=[int(X.nnz) for X in mats])

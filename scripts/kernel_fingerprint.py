@@ -56,7 +56,7 @@ def main():
         if cur is None or not line.startswith('\t'):
             continue
         ins = line.strip().split('//')[0].strip()
-        if ins:
+        if ins and ins != '...':      # ('...': the disassembler's mark for zero padding behind a kernel -- where the linker put it, no instruction)
             body[cur].append(ins)
     for name in sorted(body):
         short = re.sub(r'\(.*$', '', name).replace('void klnmf::', '').replace('klnmf::', '')
