@@ -183,6 +183,15 @@ BATCH_CSR_SIGNATURES = {
                                                       _c.POINTER(_c.c_double), _i64, _c.c_void_p, _i64]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/klnmf_beta.h (the beta-divergence cost on a context), which the
+# same library exports
+BETA_SIGNATURES = {
+    'klnmf_set_divergence': (_c.c_int, [_ctx_p, _c.c_double]),
+    'klnmf_get_divergence': (_c.c_int, [_ctx_p, _c.POINTER(_c.c_double)]),
+    'klnmf_beta_loss': (_c.c_int, [_ctx_p, _c.POINTER(_c.c_double)]),
+    'klnmf_beta_step': (_c.c_int, [_ctx_p, _c.c_int]),
+}
+
 _lib = None
 
 
@@ -207,7 +216,7 @@ def load():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(BATCH_MASK_SIGNATURES.items()) \
-            + list(BATCH_CSR_SIGNATURES.items()):
+            + list(BATCH_CSR_SIGNATURES.items()) + list(BETA_SIGNATURES.items()):
         fn = getattr(lib, name)     # AttributeError if a symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -769,6 +778,29 @@ class Context(object):
 
     def step_H(self):
         _check(self._lib.klnmf_step_H(self._h))
+
+    # -- the beta-divergence cost (include/klnmf_beta.h) --
+    def set_divergence(self, beta):
+        """The cost function of the current problem (klnmf_set_divergence): after `set_problem` and the uploads, before a loop;
+        dense problems in 'f64' / 'f32' only.  beta = 1 is the KL loop again."""
+        _check(self._lib.klnmf_set_divergence(self._h, float(beta)))
+
+    def get_divergence(self):
+        out = _c.c_double(0)
+        _check(self._lib.klnmf_get_divergence(self._h, ctypes.byref(out)))
+        return out.value
+
+    def beta_loss(self):
+        """The beta cost of the current V, W, H and weights (klnmf_beta_loss)."""
+        out = _c.c_double(0)
+        _check(self._lib.klnmf_beta_loss(self._h, ctypes.byref(out)))
+        return out.value
+
+    def beta_step(self, which):
+        """One rule from a freshly formed A and B (klnmf_beta_step): 0 / 'W' the W rule, 1 / 'H' the H rule with its
+        normalisation and the compensation on W's columns."""
+        which = {'W': 0, 'H': 1}.get(which, which)
+        _check(self._lib.klnmf_beta_step(self._h, int(which)))
 
     def generalized_kl(self, x, y, eps):
         x = _as_float_array(x).ravel()

@@ -264,7 +264,11 @@ int klnmf_exchange_layout(klnmf_ctx *c, int64_t *row_stride, int64_t *valid_coun
 int klnmf_bind_exchange(klnmf_ctx *c, void *loss_ptr, void *numer_ptr) {
     return guarded([&] {
         need_problem(c);
+        if (c->beta_on() && (loss_ptr || numer_ptr))
+            fail(KLNMF_ERR_UNSUPP, "klnmf_bind_exchange: the context runs a beta divergence (klnmf_set_divergence) and an exchange between row "
+                                   "shards carries no denominator of the beta H rule; klnmf_set_divergence(ctx, 1.0) first");
         HIPCHK(hipStreamSynchronize(c->stream));
+        if (loss_ptr || numer_ptr) c->exchange_bound = true;
         if (loss_ptr) c->loss_xchg = (double *)loss_ptr;
         if (numer_ptr) {
             if (c->is_exact()) c->numer = numer_ptr;

@@ -863,15 +863,19 @@ int klnmf_upload_weights(klnmf_ctx *c, const void *src, int dtype, int64_t rows,
         if (!c->weighted()) {
             HIPCHK(hipStreamSynchronize(c->stream));
             void *om = nullptr;
+            const bool have_den = c->beta_on();      // (klnmf_set_divergence took the denominators' slabs and sums: they stay its)
             try {
                 om = c->dalloc(n * f * es, false);
-                c->Dpart = c->dalloc((size_t)c->nsplit * k * f * es);
-                c->denom = c->dalloc(k * f * es);
-                if (c->wsplit > 1) c->WDpart = c->dalloc((size_t)c->wsplit * n * k * es);
+                if (!have_den) {
+                    c->Dpart = c->dalloc((size_t)c->nsplit * k * f * es);
+                    c->denom = c->dalloc(k * f * es);
+                    if (c->wsplit > 1) c->WDpart = c->dalloc((size_t)c->wsplit * n * k * es);
+                }
                 fill_ones(c->stream, om, c->prec == KLNMF_PREC_F64, c->n * c->f);
             } catch (...) {                     // all or nothing: a failed first upload leaves the problem unweighted
                 (void)hipStreamSynchronize(c->stream);
-                c->dfree(c->Dpart); c->dfree(c->denom); c->dfree(c->WDpart); c->dfree(om);
+                if (!have_den) { c->dfree(c->Dpart); c->dfree(c->denom); c->dfree(c->WDpart); }
+                c->dfree(om);
                 throw;
             }
             c->Om = om;
@@ -898,6 +902,8 @@ static void presence_check_all(klnmf_ctx *c, const std::string &who, int64_t row
                                int n_mod) {
     presence_check_args(who, mask_dims(c), rows, row0, rows_ok, col_bounds, n_mod);
     if (c->weighted()) fail(KLNMF_ERR_ARG, who + ": the problem holds weights (klnmf_upload_weights); klnmf_clear_weights first");
+    if (c->beta_on()) fail(KLNMF_ERR_UNSUPP, who + ": the problem runs a beta divergence (klnmf_set_divergence), which has no masked form; "
+                                                   "upload the mask as weights (klnmf_upload_weights) or klnmf_set_divergence(ctx, 1.0) first");
     presence_check_bounds(*c, who, "problem", col_bounds, n_mod);
 }
 
@@ -954,7 +960,8 @@ int klnmf_clear_weights(klnmf_ctx *c) {
         }
         if (!c->weighted()) return;
         HIPCHK(hipStreamSynchronize(c->stream));
-        c->dfree(c->Om); c->dfree(c->Dpart); c->dfree(c->denom); c->dfree(c->WDpart);
+        c->dfree(c->Om);
+        if (!c->beta_on()) { c->dfree(c->Dpart); c->dfree(c->denom); c->dfree(c->WDpart); }      // (a beta problem keeps its denominators)
     });
 }
 

@@ -184,6 +184,8 @@ static void group_loop_entry(klnmf_group *g) {
         raise_refusals(g->ctxs[r], refs[r]);          // (passes: the state is clean, the entry below reads nothing back)
         const int rc = klnmf_loop_begin_agreed(g->ctxs[r], sum_v, cells, nnz, shape_all);
         if (rc != KLNMF_OK) fail(rc, "shard " + std::to_string(r) + ": " + g_err);
+        g->ctxs[r]->pieces_open = false;       // (the pieces are klnmf_group_run's own, not a caller's: nothing stays open behind
+                                               // it, whichever way it ends)
     }
 }
 
@@ -237,6 +239,7 @@ int klnmf_group_create(klnmf_group **out, klnmf_ctx *const *ctxs, int n) {
         } catch (...) {
             for (int r = 0; r < (int)g->own_loss.size(); ++r) {
                 ctxs[r]->loss_xchg = (double *)g->own_loss[r];
+                ctxs[r]->exchange_bound = false;
                 if (ctxs[r]->is_exact()) ctxs[r]->numer = g->own_numer[r]; else ctxs[r]->numerF = (float *)g->own_numer[r];
             }
             group_free(g);
@@ -255,7 +258,7 @@ int klnmf_group_destroy(klnmf_group *g) {
             klnmf_ctx *c = g->ctxs[r];
             (void)hipSetDevice(c->device);
             (void)hipStreamSynchronize(c->stream);
-            if (c->loss_xchg == g->loss[r]) c->loss_xchg = (double *)g->own_loss[r];
+            if (c->loss_xchg == g->loss[r]) { c->loss_xchg = (double *)g->own_loss[r]; c->exchange_bound = false; }
             if (c->is_exact() && c->numer == g->numer[r]) c->numer = g->own_numer[r];
             if (!c->is_exact() && c->numerF == g->numer[r]) c->numerF = (float *)g->own_numer[r];
         }

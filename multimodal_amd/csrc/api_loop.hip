@@ -326,8 +326,8 @@ void exact_W(klnmf_ctx *c, const void *qsrc, int multiply) {
     auto contract = [&](auto epi, auto x3) {
         typedef decltype(epi) Epi;
 #define KL_W_ARGS (int)c->n, (int)c->k, (int)c->f, (const T *)qsrc, (int64_t)c->f, (int64_t)1, (const T *)c->H, (int64_t)1, (int64_t)c->f
-        if constexpr (Epi::sets == 2)      // numerator and denominator: form A of k_gemm_dual (R.H^T, Om.H^T), the tile of H^T shared
-            hipLaunchKernelGGL((k_gemm_dual<T, Epi, true>), grid, dim3(256), 0, c->stream, KL_W_ARGS, (const T *)c->Om, chunk,
+        if constexpr (Epi::sets == 2)      // numerator and denominator: form A of k_gemm_dual (R.H^T, Om.H^T; beta: A.H^T, B.H^T), the tile of H^T shared
+            hipLaunchKernelGGL((k_gemm_dual<T, Epi, true>), grid, dim3(256), 0, c->stream, KL_W_ARGS, (const T *)c->den_matrix(), chunk,
                                (const DevState *)c->st, epi);
         else if constexpr (decltype(x3)::value)
             KL_GEMM_TT(T, Epi, grid, c->stream, KL_W_ARGS, chunk, (const DevState *)c->st, epi);
@@ -349,7 +349,8 @@ void exact_W(klnmf_ctx *c, const void *qsrc, int multiply) {
         hipLaunchKernelGGL((k_wrule_exact<T, Fac>), dim3(grid_for(count)), dim3(256), 0, c->stream, part, (const DevState *)c->st, epi);
         HIPCHK(hipGetLastError());
     };
-    if (c->weighted() && multiply) rule(FacDen{}, std::false_type{});      // (the start W0 = V.H0^T is unweighted under every policy)
+    if (c->beta_on() && multiply) rule(FacBeta<T>{(T)c->beta_gamma()}, std::false_type{});      // (qsrc: A of beta_ratio)
+    else if (c->weighted() && multiply) rule(FacDen{}, std::false_type{});      // (the start W0 = V.H0^T is unweighted under every policy)
     else if (c->presence() && multiply) {
         presence_S<T>(c);
         rule(FacPresW<T>{(const T *)c->Pm, (const T *)c->pres_S, c->k, c->pres_M}, std::false_type{});
@@ -391,8 +392,8 @@ void exact_N(klnmf_ctx *c, int widx, bool sum_slabs = true) {
     EventPair ev{};
     if (c->prof_now) ev = begin_event(c, c->ev_col);
 #define KL_N_ARGS (int)c->k, (int)c->f, (int)c->n, (const T *)c->W[widx], (int64_t)1, (int64_t)c->k, (const T *)c->Q, (int64_t)c->f, (int64_t)1
-    if (c->weighted())         // (W^T.R, W^T.Om): form B of k_gemm_dual, the tile of W^T shared
-        hipLaunchKernelGGL((k_gemm_dual<T, EpiN<T, 2>, false>), grid, dim3(256), 0, c->stream, KL_N_ARGS, (const T *)c->Om, c->kchunk,
+    if (c->dual())             // (W^T.R, W^T.Om; beta: W^T.A, W^T.B): form B of k_gemm_dual, the tile of W^T shared
+        hipLaunchKernelGGL((k_gemm_dual<T, EpiN<T, 2>, false>), grid, dim3(256), 0, c->stream, KL_N_ARGS, (const T *)c->den_matrix(), c->kchunk,
                            (const DevState *)c->st, EpiN<T, 2>{{(T *)c->Npart, (T *)c->Dpart}, c->f, count});
     else if (c->x3_fused() && c->x3_ready && widx == (c->cur ^ 1)) x3_colpass(c);
     else KL_GEMM_TT(T, EpiN<T>, grid, c->stream, KL_N_ARGS, c->kchunk, (const DevState *)c->st, EpiN<T>{{(T *)c->Npart}, c->f, count});
@@ -400,7 +401,7 @@ void exact_N(klnmf_ctx *c, int widx, bool sum_slabs = true) {
     HIPCHK(hipGetLastError());
     if (c->prof_now) HIPCHK(hipEventRecord(ev.b, c->stream));
     if (!sum_slabs) return;
-    if (c->weighted())
+    if (c->dual())
         hipLaunchKernelGGL((k_sum_partials<T, 2>), dim3(grid_for(count)), dim3(256), 0, c->stream,
                            NumArray<T, 2>{{(const T *)c->Npart, (const T *)c->Dpart}}, OutSets<T, 2>{{(T *)c->numer, (T *)c->denom}},
                            count, c->nsplit, (const DevState *)c->st);
@@ -412,8 +413,9 @@ void exact_N(klnmf_ctx *c, int widx, bool sum_slabs = true) {
 
 // from_slabs (dense, short rows): the rule sums the row chunks' slabs itself -- the same bits, one launch less; else from their
 // sums: one block per row, or (long rows) S segments per row in two launches (exact.hip.h)
+// beta_widx (a beta problem only): the W whose columns take the rows' sums -- the one the numerator was formed with
 template <typename T>
-void exact_H(klnmf_ctx *c, bool from_slabs = false) {
+void exact_H(klnmf_ctx *c, bool from_slabs = false, int beta_widx = 0) {
     auto rule = [&](auto fac) {
         typedef decltype(fac) Fac;
         typedef NumArray<T, Fac::S> Arr;
@@ -435,9 +437,71 @@ void exact_H(klnmf_ctx *c, bool from_slabs = false) {
         }
         HIPCHK(hipGetLastError());
     };
-    if (c->weighted()) rule(FacDen{});
+    // a beta problem: the same three routes under FacBeta, each leaving the rows' sums (one per segment) in hpart, and the
+    // compensation W[widx][:, a] *= sum[a] behind them (beta.hip.h)
+    auto beta_rule = [&](FacBeta<T> fac) {
+        typedef FacBeta<T> Fac;
+        typedef NumArray<T, 2> Arr;
+        typedef NumSlabs<T, 2> Slabs;
+        const Arr sums{{(const T *)c->numer, (const T *)c->denom}}, slab0{{(const T *)c->Npart, (const T *)c->Dpart}};
+        const int nseg = (!from_slabs && c->hseg_n > 1) ? c->hseg_n : 1;
+        if (from_slabs) {
+            hipLaunchKernelGGL((k_update_H_sums<T, Slabs, Fac>), dim3((unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
+                               RuleIn<Slabs, Fac>{Slabs{slab0, c->nsplit, c->k * c->f}, fac}, c->f, c->hpart, (const DevState *)c->st);
+        } else if (nseg > 1) {
+            hipLaunchKernelGGL((k_update_H_part<T, Fac>), dim3((unsigned)c->hseg_n, (unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
+                               RuleIn<Arr, Fac>{sums, fac}, c->f, c->hseg, c->hpart, (const DevState *)c->st);
+            hipLaunchKernelGGL((k_update_H_norm<T>), dim3((unsigned)c->hseg_n, (unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
+                               c->f, c->hseg, (const double *)c->hpart, (const DevState *)c->st);
+        } else {
+            hipLaunchKernelGGL((k_update_H_sums<T, Arr, Fac>), dim3((unsigned)c->k), dim3(256), 0, c->stream, (T *)c->H,
+                               RuleIn<Arr, Fac>{sums, fac}, c->f, c->hpart, (const DevState *)c->st);
+        }
+        HIPCHK(hipGetLastError());
+        const int64_t count = c->n * c->k;
+        hipLaunchKernelGGL((k_scale_W_cols<T>), dim3(grid_for(count)), dim3(256), 0, c->stream, (T *)c->W[beta_widx], count, c->k,
+                           (const double *)c->hpart, nseg, (const DevState *)c->st);
+        HIPCHK(hipGetLastError());
+    };
+    if (c->beta_on()) beta_rule(FacBeta<T>{(T)c->beta_gamma()});
+    else if (c->weighted()) rule(FacDen{});
     else if (c->presence()) rule(FacPresH<T>{(const T *)c->pres_D, (const unsigned char *)c->pres_mod, c->pres_M});
     else rule(FacNum{});
+}
+
+// A = Om o x o y^(beta-2) into Q and B = Om o y^(beta-1) into Bt at (W[widx], H), x = V + eps, y = W.H + eps (beta.hip.h); `loss`: the
+// cost's partials and their one-block sum into loss_xchg, with the stop rule where dec.on
+template <typename T>
+void beta_AB(klnmf_ctx *c, int widx, bool loss, DecideArgs dec) {
+    dim3 grid((unsigned)((c->f + GT - 1) / GT), (unsigned)((c->n + GT - 1) / GT), 1);
+    EventPair ev{};
+    if (c->prof_now) ev = begin_event(c, c->ev_row);
+    auto launch = [&](auto epi) {
+        typedef decltype(epi) Epi;
+        hipLaunchKernelGGL((k_gemm<T, Epi, 4, true>), grid, dim3(256), 0, c->stream, (int)c->n, (int)c->f, (int)c->k, (const T *)c->W[widx],
+                           (int64_t)c->k, (int64_t)1, (const T *)c->H, (int64_t)c->f, (int64_t)1, (int)c->k + GK, (const DevState *)c->st, epi);
+    };
+    auto with_kind = [&](auto weight, auto with_loss) {
+        typedef decltype(weight) Weight;
+        constexpr bool L = decltype(with_loss)::value;
+#define KL_BETA_EPI(KIND) launch(EpiBeta<T, Weight, L, KIND>{(const T *)c->V, weight, (T *)c->Q, (T *)c->Bt, c->f, c->loss_part, 0.0, \
+                                                              (T)kEpsRatio, (T)c->beta})
+        if (c->beta == 2.0) KL_BETA_EPI(BETA_TWO);
+        else if (c->beta == 0.0) KL_BETA_EPI(BETA_ZERO);
+        else KL_BETA_EPI(BETA_GEN);
+#undef KL_BETA_EPI
+    };
+    auto with_weight = [&](auto with_loss) {
+        if (c->weighted()) with_kind(ElemWeight<T>{(const T *)c->Om}, with_loss);
+        else with_kind(NoWeight{}, with_loss);
+    };
+    if (loss) with_weight(std::true_type{}); else with_weight(std::false_type{});
+    HIPCHK(hipGetLastError());
+    if (c->prof_now) HIPCHK(hipEventRecord(ev.b, c->stream));
+    if (!loss) return;
+    hipLaunchKernelGGL(k_sum_doubles, dim3(1), dim3(1024), 0, c->stream, (const double *)c->loss_part, (int64_t)grid.x * grid.y,
+                       c->loss_xchg, (const DevState *)c->st, dec);
+    HIPCHK(hipGetLastError());
 }
 
 #define EXACT_CALL(c, fn, ...)                                         \
@@ -447,6 +511,20 @@ void exact_H(klnmf_ctx *c, bool from_slabs = false) {
     } while (0)
 
 }  // namespace
+
+// ---- the pieces of a beta iteration (klnmf_set_divergence: dense, KLNMF_PREC_F64 / F32; api_beta.hip has the entry points) ----
+void beta_ratio(klnmf_ctx *c, int widx, bool loss, const double *fused_tol) {
+    DecideArgs dec{0, nullptr, 0.0, nullptr, 0};
+    if (loss && fused_tol) dec = DecideArgs{1, c->st, *fused_tol, c->errors, c->cap};
+    EXACT_CALL(c, beta_AB, widx, loss, dec);
+}
+
+void beta_rule_W(klnmf_ctx *c) { EXACT_CALL(c, exact_W, c->Q, 1); }
+
+void beta_rule_H(klnmf_ctx *c, int widx, bool from_slabs) {
+    EXACT_CALL(c, exact_N, widx, !from_slabs);
+    EXACT_CALL(c, exact_H, from_slabs, widx);
+}
 
 // behind the row pass (and the conversion of the e4m3 W image) of a fit iteration on fp8 tiles, before its column pass
 void launch_monitor(klnmf_ctx *c, bool use8) {
@@ -688,6 +766,11 @@ void piece_rowpass(klnmf_ctx *c, int fit, const double *fused_tol, bool defer_to
         // fused_tol (single-context loops): the stop rule in the loss reduction's launch, no k_decide
         DecideArgs dec{0, nullptr, 0.0, nullptr, 0};
         if (fused_tol) dec = DecideArgs{1, c->st, *fused_tol, c->errors, c->cap};
+        if (c->beta_on()) {      // the beta cost: A, B and the loss at (W, H), the W rule from them
+            beta_ratio(c, c->cur, true, fused_tol);
+            beta_rule_W(c);
+            return;
+        }
         if (c->x3_fused()) {
             x3_rowpass(c, fit, kEpsRatio, dec);
             return;
@@ -725,6 +808,10 @@ void piece_rowpass(klnmf_ctx *c, int fit, const double *fused_tol, bool defer_to
 
 // loops whose exchange carries the H numerator alone (communicator, group): a weighted context is refused at their entries
 void refuse_weighted(const klnmf_ctx *c, const char *who) {
+    if (c->beta_on())
+        fail(KLNMF_ERR_UNSUPP, std::string(who) + ": the context runs a beta divergence (klnmf_set_divergence) and the exchange between "
+                                   "row shards carries no denominator of the beta H rule; run the problem in one context or "
+                                   "klnmf_set_divergence(ctx, 1.0) first");
     if (c->presence())
         fail(KLNMF_ERR_UNSUPP, std::string(who) + ": the context holds a presence mask (klnmf_upload_presence) and the exchange between "
                                    "row shards carries no W^T.P of the masked H rule; run the masked problem in one context or "
@@ -742,7 +829,11 @@ void piece_decide(klnmf_ctx *c, double tol_abs) {
 }
 
 void piece_colpass(klnmf_ctx *c) {
-    if (c->is_exact()) { EXACT_CALL(c, exact_N, c->cur ^ 1); return; }
+    if (c->is_exact()) {
+        if (c->beta_on()) beta_ratio(c, c->cur ^ 1, false);      // (the second ratio pass: A and B at (W_new, H), no loss)
+        EXACT_CALL(c, exact_N, c->cur ^ 1);
+        return;
+    }
     // (the pieces of a loop sequenced by the caller: the numerator is summed here, exchanged by the caller, applied by
     // piece_update_H; the loss was left in loss_xchg by piece_rowpass)
     const bool use8 = fused_w8_stage(c);
@@ -771,7 +862,7 @@ void piece_colpass_part(klnmf_ctx *c, int p) {
 }
 
 void piece_update_H(klnmf_ctx *c) {
-    if (c->is_exact()) EXACT_CALL(c, exact_H);
+    if (c->is_exact()) EXACT_CALL(c, exact_H, false, c->cur ^ 1);
     else if (c->piece_split) launch_post(c, POST_RULE, c->parts, c->nparts_cfg, kNoLoss, false, false, false);
     else launch_post(c, POST_RULE, &c->whole, 1, kNoLoss, false, false, false);
     c->piece_split = false;
@@ -785,8 +876,9 @@ void piece_fit_tail(klnmf_ctx *c) {
         // scale: one launch less of 7); beyond, one block per row walking the slabs is slower than the wide sum kernel
         // (1000 x 2000, k = 50, 16 slabs: 97 vs 73 us per iteration)
         const bool slabs = h_from_slabs(c);
+        if (c->beta_on()) beta_ratio(c, c->cur ^ 1, false);      // (the second ratio pass: the H rule is a majorise-minimise step of its own)
         EXACT_CALL(c, exact_N, c->cur ^ 1, !slabs);
-        EXACT_CALL(c, exact_H, slabs);
+        EXACT_CALL(c, exact_H, slabs, c->cur ^ 1);
         return;
     }
     const LossArgs la = c->pending_loss;
@@ -992,6 +1084,7 @@ int klnmf_loop_begin(klnmf_ctx *c) {
             begin_fp8_loop(c);
         }
         loop_open(c);
+        c->pieces_open = true;
     });
 }
 
@@ -1012,6 +1105,7 @@ int klnmf_loop_begin_agreed(klnmf_ctx *c, double sum_x_all, double cells_all, do
         begin_fp8_loop(c, sum_x_all * c->v_scale, cells_all, nnz_all, fp8_shape_all);      // (the caller's sums are in the data's own units)
         c->sharded_loop = true;
         loop_open(c);
+        c->pieces_open = true;
     });
 }
 
@@ -1082,6 +1176,7 @@ int klnmf_loop_end(klnmf_ctx *c, double *errors_out, int64_t *n_done, int *stopp
         need_problem(c);
         fetch_results(c, errors_out, n_done, stopped);
         c->sharded_loop = false;
+        c->pieces_open = false;
     });
 }
 
@@ -1105,6 +1200,7 @@ int klnmf_run(klnmf_ctx *c, int64_t max_iter, int fit, double tol_abs, double *e
 int klnmf_error(klnmf_ctx *c, double *loss) {
     return guarded([&] {
         need_problem(c);
+        if (c->beta_on()) fail(KLNMF_ERR_UNSUPP, "klnmf_error: the context runs a beta divergence; its cost is klnmf_beta_loss");
         check_v_overflow(c);
         reset_state(c);
         if (c->is_exact()) {
@@ -1169,6 +1265,7 @@ int klnmf_step_Q(klnmf_ctx *c) {
     return guarded([&] {
         need_problem(c);
         if (!c->is_exact()) fail(KLNMF_ERR_UNSUPP, "the ratio Q is never materialised in the bf16 modes");
+        if (c->beta_on()) fail(KLNMF_ERR_UNSUPP, "klnmf_step_Q: the context runs a beta divergence; its steps are klnmf_beta_step");
         reset_state(c);
         EXACT_CALL(c, exact_Q, 1, c->ratio_eps);
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -1179,6 +1276,7 @@ int klnmf_step_W(klnmf_ctx *c) {
     return guarded([&] {
         need_problem(c);
         if (!c->is_exact()) fail(KLNMF_ERR_UNSUPP, "step API needs KLNMF_PREC_F64/F32/BF16X3/F16X3");
+        if (c->beta_on()) fail(KLNMF_ERR_UNSUPP, "the context runs a beta divergence; its steps are klnmf_beta_step");
         reset_state(c);
         EXACT_CALL(c, exact_W, c->sparse ? c->sp_q : c->Q, 1);
         c->cur ^= 1;
@@ -1190,6 +1288,7 @@ int klnmf_step_H(klnmf_ctx *c) {
     return guarded([&] {
         need_problem(c);
         if (!c->is_exact()) fail(KLNMF_ERR_UNSUPP, "step API needs KLNMF_PREC_F64/F32/BF16X3/F16X3");
+        if (c->beta_on()) fail(KLNMF_ERR_UNSUPP, "the context runs a beta divergence; its steps are klnmf_beta_step");
         reset_state(c);
         EXACT_CALL(c, exact_N, c->cur);
         EXACT_CALL(c, exact_H);

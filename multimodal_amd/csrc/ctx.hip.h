@@ -12,6 +12,8 @@
 //                    (klnmf_batch_*): the [B] layout, the loop's stages as one launch each for all of them (batch.hip.h), the plan
 //                    of one problem for its share of the CUs; and of CSR problems of one shape, each with its own stored entries
 //                    (klnmf_batch_csr.h, batch_sparse.hip.h)
+//   api_beta.hip     the beta-divergence cost of a context's problem (include/klnmf_beta.h): its buffers and refusals, its loss and
+//                    single steps; the loop's pieces branch on it in api_loop.hip, on the policies of beta.hip.h
 // This header: error handling, the type dispatch of the host-facing kernels, the device block cache and the arena over it
 // (DeviceBlocks), the staged host upload, the development switches, the mask state (PresenceState) and the context itself -- its
 // state in four groups, one per lifetime (ContextState, ProblemState, LoopState, LoopRecord) -- and what contexts and batches share
@@ -42,6 +44,7 @@
 #include "exact.hip.h"
 #include "weighted.hip.h"
 #include "presence.hip.h"
+#include "beta.hip.h"
 #include "split3.hip.h"
 #include "f16x3.hip.h"
 #include "sparseb.hip.h"
@@ -398,6 +401,15 @@ struct ProblemState : ProblemPlan, PresenceState {
     // by the first klnmf_upload_weights, dropped by klnmf_clear_weights -- and the denominators' slabs and sums, laid out as
     // Npart / numer / Wpart are.  Om != nullptr IS "the current problem is weighted" (klnmf_query KLNMF_Q_WEIGHTED).
     void *Om = nullptr, *Dpart = nullptr, *denom = nullptr, *WDpart = nullptr;
+    // a beta-divergence problem (beta.hip.h; dense, KLNMF_PREC_F64 / F32; klnmf_set_divergence): beta != 1 IS "the loop runs the
+    // beta rules"; B is the second n x f matrix of the ratio pass (A lives in Q); the sums of H's rows before their
+    // normalisation go to hpart [k][hseg_n] (taken by klnmf_set_divergence where the problem has one segment and holds none).  The denominators' slabs and sums are the weighted problem's (Dpart, denom, WDpart): taken by whichever
+    // of klnmf_upload_weights and klnmf_set_divergence comes first, dropped when neither needs them.
+    double beta = 1.0;
+    void *Bt = nullptr;
+    // the exchange buffers (loss_xchg, numer / numerF) are a caller's: klnmf_bind_exchange -- a group's member, a loop sequenced
+    // over torch.distributed -- until the group's end or the next klnmf_set_problem*
+    bool exchange_bound = false;
     // a masked problem: PresenceState, taken by the first klnmf_upload_presence*, dropped by klnmf_clear_weights; a problem holds
     // Om or P, never both
     float *x3_hs = nullptr, *x3_qr = nullptr;     // per-component H scales; per-row ratio scales of the column pass
@@ -486,6 +498,8 @@ struct LoopState {
     unsigned sr_launches = 0;        // row pass launches of the current loop (the seeds of the tiles' stochastic rounding)
     bool x3_ready = false;           // Q, x3_qr and x3_xmax are the last fused row pass's (its column pass may run)
     bool prof_now = false;           // this iteration's launches are bracketed (set by piece_rowpass)
+    bool pieces_open = false;        // klnmf_loop_begin* has opened a loop whose pieces the caller enqueues; until klnmf_loop_end,
+                                     // the problem's end (free_all) or the next loop entry; never behind klnmf_group_run
     bool sharded_loop = false;       // the open loop's pieces are exchanged between row shards by the caller (klnmf_loop_begin on a
                                      // communicator, klnmf_loop_begin_sharded / _agreed; until klnmf_loop_end): no weights may arrive
 };
@@ -517,6 +531,12 @@ struct klnmf_ctx : ContextState, ProblemState, LoopState, LoopRecord {
     bool x3_fused() const { return x3; }
     size_t esize() const { return prec_esize(prec); }
     bool weighted() const { return Om != nullptr; }
+    bool beta_on() const { return beta != 1.0; }
+    // both rules contract a numerator and a denominator matrix (k_gemm_dual): the weights, or B of a beta problem
+    bool dual() const { return weighted() || beta_on(); }
+    const void *den_matrix() const { return beta_on() ? Bt : Om; }
+    // the exponent of the beta rules' factor (majorise-minimise: <= 1)
+    double beta_gamma() const { return beta < 1.0 ? 1.0 / (2.0 - beta) : (beta <= 2.0 ? 1.0 : 1.0 / (beta - 1.0)); }
 
     // The problem ends: its blocks go back to the cache and its state to the defaults.  Callers have synchronised the stream: no
     // kernel of this context still touches the blocks.
@@ -528,6 +548,7 @@ struct klnmf_ctx : ContextState, ProblemState, LoopState, LoopRecord {
         }
         static_cast<ProblemState &>(*this) = ProblemState();
         sharded_loop = false;      // (a loop that was left open went with its problem)
+        pieces_open = false;
     }
 };
 
@@ -635,6 +656,12 @@ void raise_refusals(klnmf_ctx *c, const Refusals &r);
 void check_v_overflow(klnmf_ctx *c);
 void begin_fp8_loop(klnmf_ctx *c, double sum_x_global = -1.0, double cells_global = -1.0, double nnz_global = -1.0, int ok_all = -1);
 void refuse_weighted(const klnmf_ctx *c, const char *who);
+// ... the pieces of a beta iteration (api_beta.hip runs its entry points on them): A, B (and with `loss` the cost, into loss_xchg;
+// fused_tol: with the stop rule) at (W[widx], H); the W rule from them; the H rule with W[widx], its normalisation and the
+// compensation on W[widx]'s columns (from_slabs: as piece_fit_tail chooses)
+void beta_ratio(klnmf_ctx *c, int widx, bool loss, const double *fused_tol = nullptr);
+void beta_rule_W(klnmf_ctx *c);
+void beta_rule_H(klnmf_ctx *c, int widx, bool from_slabs);
 // api_comm.hip
 bool comm_multi(const klnmf_ctx *c);
 void comm_loop_entry(klnmf_ctx *c);

@@ -50,6 +50,16 @@ def csr_rows_plan(indptrs, rows, coefs, minima):
     return nnz, use_device
 
 
+def refuse_beta(*learners):
+    """The device-resident runs exist for the default cost alone: a learner with beta != 1 (`MultimodalLearner(beta=...)`) raises
+    ValueError here, before anything is gathered -- its host calls run `BetaNMF`."""
+    for learner in learners:
+        beta = getattr(learner, 'beta', 1.0)
+        if beta != 1.0:
+            raise ValueError("DeviceDataset runs the Kullback-Leibler cost only: this learner has beta = %g; call its own train / "
+                             "reconstruct_internal_multi on host matrices" % beta)
+
+
 class _ProblemOf(object):
     """Problem p of a `_native.Batch` with a context's upload methods: what `DeviceDataset._sparse_uploader`'s upload calls."""
 
@@ -321,6 +331,7 @@ class DeviceDataset(object):
         `init_dictionary`: the initial dictionary instead of a draw from the global numpy stream (nmf.py:149-155).
         With a presence mask on the dataset: learner.train(..., weights=[P_m[rows] ...]), `learner.nmf_train.last_weights_route`
         'presence'.  A row in which every modality is absent keeps its W0 and gives the dictionary nothing."""
+        refuse_beta(learner)
         if learner.sparseness is not None:
             raise NotImplemented
         which = list(range(len(self.blocks)))
@@ -342,6 +353,7 @@ class DeviceDataset(object):
         has a presence array: ... with weights=[P_m[rows] ...], the masked transform -- over all modalities it uses in every row
         whatever that row has; a row from which every selected modality is absent keeps its W0 = x . dico^T (factor 1 where the
         denominator is 0).  `self.last_weights_route` names the route."""
+        refuse_beta(learner)
         which = [learner.get_index(m) for m in orig_mods]
         coefs = [learner.coef[w] for w in which]
         dico = learner.get_stacked_dicos(orig_mods)
@@ -424,6 +436,7 @@ class DeviceDataset(object):
         over `train` otherwise.  With a presence mask on the
         dataset the batch is the masked one: `last_weights_route` 'presence' here and on every `learner.nmf_train`."""
         learners, rows_list = list(learners), [list(r) for r in rows_list]
+        refuse_beta(*learners)
         inits = list(init_dictionaries) if init_dictionaries is not None else [None] * len(learners)
         which = list(range(len(self.blocks)))
         nmfs = []
@@ -460,6 +473,7 @@ class DeviceDataset(object):
         """[self.reconstruct_internal_multi(l, orig_mods, rows, iterations) for l, rows in ...] -- as one batch under
         `train_many`'s conditions (here: on the selected modalities)."""
         learners, rows_list = list(learners), [list(r) for r in rows_list]
+        refuse_beta(*learners)
         if not learners:
             return []
         which = [learners[0].get_index(m) for m in orig_mods]
@@ -503,6 +517,7 @@ class DeviceEvaluation(object):
 
     def __init__(self, dataset, learner, iter_test):
         import torch
+        refuse_beta(learner)
         self.torch, self.ds, self.learner, self.iter_test = torch, dataset, learner, int(iter_test)
         self.dev = dataset.device
         self.dico = torch.from_numpy(np.ascontiguousarray(learner.get_dico(), dtype=np.float64)).to(self.dev)

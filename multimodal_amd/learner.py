@@ -28,19 +28,29 @@ def _checked(blocks):
     return checked
 
 
-def _coefficients_on(dictionary, blocks, scales, iter_nmf, weights=None):
+def _model(beta, **kw):
+    """The NMF of a learner: `KLdivNMF` for the default cost (beta = 1.0: today's code path, call for call), `BetaNMF` for every
+    other beta -- imported only then."""
+    if beta == 1.0:
+        return NMF(**kw)
+    from .lib.beta_nmf import BetaNMF
+    return BetaNMF(beta=beta, **kw)
+
+
+def _coefficients_on(dictionary, blocks, scales, iter_nmf, weights=None, beta=1.0):
     """tol=0 transform of the (virtually) stacked blocks on a fixed dictionary; `weights`: None or one entry per block
-    (`KLdivNMF._fit_blocks`)."""
-    model = NMF(n_components=dictionary.shape[0], max_iter=iter_nmf, tol=0)
+    (`KLdivNMF._fit_blocks`); `beta`: the cost (`_model`)."""
+    model = _model(beta, n_components=dictionary.shape[0], max_iter=iter_nmf, tol=0)
     model.components_ = dictionary
     return model._transform_blocks(_checked(blocks), scales, weights=weights)
 
 
-def fit_coefficients(data_obs, dictionary, iter_nmf=100, verbose=False, weights=None):
+def fit_coefficients(data_obs, dictionary, iter_nmf=100, verbose=False, weights=None, beta=1.0):
     """Non-negative coefficients of `data_obs` on `dictionary`
     (reference learner.py:11-15: tol=0 transform for iter_nmf iterations).  `weights`: None, or an array broadcastable to
-    `data_obs` -- weights on the cost function, 0 = a missing entry (`KLdivNMF.fit_transform`)."""
-    return _coefficients_on(dictionary, [data_obs], [1.], iter_nmf, weights=None if weights is None else [weights])
+    `data_obs` -- weights on the cost function, 0 = a missing entry (`KLdivNMF.fit_transform`).  `beta`: the beta divergence
+    of the cost (1.0: Kullback-Leibler, the reference's; `lib.beta_nmf.BetaNMF` otherwise)."""
+    return _coefficients_on(dictionary, [data_obs], [1.], iter_nmf, weights=None if weights is None else [weights], beta=beta)
 
 
 class MultimodalLearner(object):
@@ -49,17 +59,20 @@ class MultimodalLearner(object):
     modalities: names; dimensions: number of columns of each; coefficients:
     per-modality scale applied before stacking; k: number of atoms.
     `dico` ([k, sum(dimensions)] ndarray, None until trained) may also be
-    assigned from outside (the sample scripts do).
+    assigned from outside (the sample scripts do).  `beta`: the beta divergence of the cost function, 1.0 (Kullback-Leibler, the
+    reference's) by default; with another value `train`, `reconstruct_internal_multi` and what builds on them run
+    `lib.beta_nmf.BetaNMF` (2.0: Euclidean, 0: Itakura-Saito).
     """
 
     def __init__(self, modalities, dimensions, coefficients, k,
-                 sparseness=None, sp_coef=.1):
+                 sparseness=None, sp_coef=.1, beta=1.0):
         self.mod = modalities
         self.dim = dimensions
         self.coef = coefficients
         self.k = k
         self.sparseness = sparseness
         self.sp_coef = sp_coef
+        self.beta = float(beta)
         self.dico = None
 
     # ---- bookkeeping ----
@@ -94,7 +107,7 @@ class MultimodalLearner(object):
             assert(m.shape == (n_samples, d))
         if self.sparseness is not None:
             raise NotImplemented        # as the reference (learner.py:37-38)
-        self.nmf_train = NMF(n_components=self.k, max_iter=iterations, tol=0)
+        self.nmf_train = _model(self.beta, n_components=self.k, max_iter=iterations, tol=0)
         self.nmf_train._fit_blocks(_checked(data_matrices), self._scales(self.mod),
                                    _fit=True, weights=weights)
         self.dico = self.nmf_train.components_
@@ -116,7 +129,7 @@ class MultimodalLearner(object):
         for mod, data in zip(orig_mods, test_data):
             assert(data.shape[1] == self.dim[self.get_index(mod)])
         return _coefficients_on(self.get_stacked_dicos(orig_mods), test_data,
-                                self._scales(orig_mods), iterations, weights=weights)
+                                self._scales(orig_mods), iterations, weights=weights, beta=self.beta)
 
     def reconstruct_internal(self, orig_mod, test_data, iterations):
         return self.reconstruct_internal_multi([orig_mod], [test_data],

@@ -447,6 +447,10 @@ class KLdivNMF(object):
         self.last_weights_route = route if weights is not None else None
         return out
 
+    def _after_upload(self, ctx):
+        """Hook of `_fit_uploaded` behind the uploads, in front of the first dictionary: nothing here (subclasses with another
+        cost function name it to the context: `beta_nmf.BetaNMF`)."""
+
     def _note_weighted_on_one_device(self):
         """(the group's exchange carries the H numerator alone: a weighted fit stays in one context)"""
         if len(self.devices) > 1:
@@ -498,6 +502,7 @@ class KLdivNMF(object):
             else:
                 ctx.set_problem(n_samples, n_features, k, max_iter)
                 upload(ctx)
+            self._after_upload(ctx)
             ctx.set_H(H_init)
             ctx.init_W()                       # W0 = X . H_init^T (nmf.py:156)
             if _fit:
@@ -794,8 +799,11 @@ def batch_precision(models, n, f, weighted=False, sparse=False):
     one and the same single device.  None otherwise.  weighted: a batch of masked problems -- the arithmetic is
     `weighted_precision`'s, which is what the single masked call runs in ('auto' -> f64, the 16-bit modes -> f32).  sparse: a
     batch of CSR problems -- `sparse_precision`'s arithmetic, with its stderr note, and k <= CSR_BATCH_MAX_K (the blocked sparse
-    kernels; beyond, a context runs the unblocked ones)."""
+    kernels; beyond, a context runs the unblocked ones).  A model under another cost function (`beta_nmf.BetaNMF` with
+    beta != 1) never batches: the batch kernels run the Kullback-Leibler cost alone, and its own `fit_transform` runs it."""
     first = models[0]
+    if any(getattr(m, 'beta', 1.0) != 1.0 for m in models):
+        return None
     same = all((m.n_components, m.tol, m.max_iter, m.precision, m.devices) ==
                (first.n_components, first.tol, first.max_iter, first.precision, first.devices) for m in models)
     if not same or len(first.devices) != 1 or not 1 <= len(models) <= _native.BATCH_MAX:
