@@ -192,6 +192,14 @@ BETA_SIGNATURES = {
     'klnmf_beta_step': (_c.c_int, [_ctx_p, _c.c_int]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/klnmf_batch_beta.h (the beta-divergence cost on batches), which the
+# same library exports
+BATCH_BETA_SIGNATURES = {
+    'klnmf_batch_set_divergence': (_c.c_int, [_c.c_void_p, _c.c_double]),
+    'klnmf_batch_get_divergence': (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_double)]),
+    'klnmf_batch_upload_weights': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _i64, _i64, _i64, _i64, _i64]),
+}
+
 _lib = None
 
 
@@ -216,7 +224,7 @@ def load():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(BATCH_MASK_SIGNATURES.items()) \
-            + list(BATCH_CSR_SIGNATURES.items()) + list(BETA_SIGNATURES.items()):
+            + list(BATCH_CSR_SIGNATURES.items()) + list(BETA_SIGNATURES.items()) + list(BATCH_BETA_SIGNATURES.items()):
         fn = getattr(lib, name)     # AttributeError if a symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -959,7 +967,8 @@ class Batch(object):
     under presence masks that share their column bounds (`upload_presence`) -- that run the multiplicative-update loop together,
     every stage of an iteration one launch for all of them.  Each problem `p` keeps its own V, W, H, mask, loss record and stop
     state; its results are bit for bit those of the same problem alone in a `Context` whose chunk counts equal the batch's
-    (`exact_regime()`).  The methods mirror `Context`'s with the problem index in front."""
+    (`exact_regime()`).  The methods mirror `Context`'s with the problem index in front.  `set_divergence(beta)` makes the loop
+    the beta-divergence one for every problem (klnmf_batch_beta.h), with weights per problem (`upload_weights`)."""
 
     def __init__(self, precision, count, device=0):
         self._lib = load()
@@ -1091,6 +1100,33 @@ class Batch(object):
     def presence(self):
         """Modalities of the batch's presence masks (klnmf_batch_query KLNMF_Q_PRESENCE); 0 without one."""
         return self.query(Q_PRESENCE)
+
+    # ---- the beta-divergence cost (klnmf_batch_beta.h): one beta for every problem, weights per problem ----
+    def set_divergence(self, beta):
+        """The cost function of every problem of the batch (klnmf_batch_set_divergence), behind `set_problem` and in front of a
+        run: beta != 1 makes `run` the beta loop of `Context.set_divergence`; 1.0 gives the Kullback-Leibler loop back and drops the
+        weights.  Refused (NativeError, the batch stays as it was): a CSR batch, a batch with a presence mask, a beta that is not
+        finite, in 'f32' a beta that fp32 rounds to 1 or to 0 without being it."""
+        _check(self._lib.klnmf_batch_set_divergence(self._h, float(beta)))
+
+    def get_divergence(self):
+        v = _c.c_double(1.0)
+        _check(self._lib.klnmf_batch_get_divergence(self._h, ctypes.byref(v)))
+        return float(v.value)
+
+    def upload_weights(self, p, block, row0=0, col0=0):
+        """`Context.upload_weights` for problem p of a batch with beta != 1 (klnmf_batch_upload_weights): weights >= 0 on the cost
+        function.  The first call makes the whole batch weighted, every weight not uploaded equal to 1."""
+        a = np.asarray(block)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.ndim != 2:
+            raise ValueError("2-D block expected")
+        if a.strides[1] != a.itemsize or a.strides[0] % a.itemsize or a.strides[0] < a.shape[1] * a.itemsize:
+            a = np.ascontiguousarray(a)
+        ld = a.strides[0] // a.itemsize
+        _check(self._lib.klnmf_batch_upload_weights(self._h, int(p), a.ctypes.data, _np_dtype_code(a), a.shape[0], a.shape[1], ld,
+                                                    int(row0), int(col0)))
 
     def set_H(self, p, H):
         H = _as_float_array(H)

@@ -7,10 +7,14 @@
 // A CSR batch (klnmf_batch_csr.h; batch_sparse.hip.h has the kernels and the layout): B unweighted CSR problems of one shape, each
 // with its own stored entries, on the blocked sparse kernels; the plan is plan_csr's for the batch's mean entries per problem, the
 // launch sequence local_iteration's for a blocked CSR problem (sparse_Q, the blocked arms of exact_W and exact_N, exact_H).
+// A beta batch (klnmf_batch_beta.h): B dense problems under one beta != 1, weighted where klnmf_batch_upload_weights placed an Om;
+// the launch sequence is local_iteration's for a beta context (beta_ratio with the loss, the beta arm of exact_W, beta_ratio without
+// the loss, the dual arm of exact_N, the beta arm of exact_H with its column scale of W), stage for stage.
 #include "ctx.hip.h"
 #include "../../include/klnmf_batch.h"
 #include "../../include/klnmf_batch_mask.h"
 #include "../../include/klnmf_batch_csr.h"
+#include "../../include/klnmf_batch_beta.h"
 #include "batch.hip.h"
 
 struct klnmf_batch : DeviceBlocks, PresenceState {
@@ -36,12 +40,26 @@ struct klnmf_batch : DeviceBlocks, PresenceState {
     int64_t *u_indptr = nullptr, *u_indices = nullptr, *u_csc_indptr = nullptr, *u_csc_rows = nullptr, *u_csc_perm = nullptr, *u_work = nullptr;
     // (a masked batch: PresenceState, every problem's P, S, D and D's slabs and once per batch the bounds and the modality bytes --
     // taken by the first klnmf_batch_upload_presence*, dropped by klnmf_batch_clear_presence and with the problem)
+    // ---- a beta batch (klnmf_batch_beta.h; beta != 1): B [B][n][f] beside Q (= A), the denominators' slab sets and sums beside
+    // the numerators', the rows' sums of the H rule in hpart ([B][k] where the plan holds no segments: own_hpart) -- taken by
+    // klnmf_batch_set_divergence; Om [B][n][f] by the first klnmf_batch_upload_weights.  All go with the problem and at beta = 1
+    double beta = 1.0;
+    bool own_hpart = false;
+    void *Bt = nullptr, *Om = nullptr, *Dpart = nullptr, *denom = nullptr, *WDpart = nullptr;
 
     size_t esize() const { return prec_esize(prec); }
     MaskDims mask_dims() const { return {n, f, k, count, prec}; }
+    bool beta_on() const { return beta != 1.0; }
+    double beta_gamma() const { return beta < 1.0 ? 1.0 / (2.0 - beta) : (beta <= 2.0 ? 1.0 : 1.0 / (beta - 1.0)); }
+    void forget_beta() {      // (the blocks are released, or about to be)
+        beta = 1.0;
+        own_hpart = false;
+        Bt = Om = Dpart = denom = WDpart = nullptr;
+    }
     void free_all() {      // (callers have synchronised the stream)
         release_all();
         forget_presence();
+        forget_beta();
         have_problem = false;
         sparse = false;
     }
@@ -243,6 +261,121 @@ void batch_H(klnmf_batch *b, bool from_slabs) {
     else batch_H_rule<T>(b, from_slabs, FacNum{});
 }
 
+// ---- a beta batch's stages: api_loop.hip's beta_AB and the beta arms of exact_W / exact_N / exact_H for B problems ----------------
+// A = Om o x o y^(beta-2) into Q and B = Om o y^(beta-1) into Bt at (W[widx], H) of every problem; `loss`: the cost's partials, their
+// per-problem sum and the stop rule
+template <typename T>
+void beta_AB(klnmf_batch *b, int widx, bool loss, double tol_abs) {
+    const ProblemPlan &pl = b->plan;
+    const int ytiles = (int)((b->n + GT - 1) / GT);
+    const dim3 grid((unsigned)((b->f + GT - 1) / GT), (unsigned)(b->count * ytiles), 1);
+    auto launch = [&](auto epi) {
+        typedef decltype(epi) Epi;
+        hipLaunchKernelGGL((k_gemm_batch<T, Epi>), grid, dim3(256), 0, b->stream, (int)b->n, (int)b->f, (int)b->k, (const T *)b->W[widx],
+                           (int64_t)b->k, (int64_t)1, b->n * b->k, (const T *)b->H, (int64_t)b->f, (int64_t)1, b->k * b->f, (int)b->k + GK,
+                           (const DevState *)b->st, ytiles, epi);
+    };
+    auto with_kind = [&](auto weight, auto with_loss) {
+        typedef decltype(weight) Weight;
+        constexpr bool L = decltype(with_loss)::value;
+#define KL_BETA_EPI(KIND) launch(EpiBeta<T, Weight, L, KIND>{(const T *)b->V, weight, (T *)b->Q, (T *)b->Bt, b->f, b->loss_part, 0.0, \
+                                                              (T)kEpsRatio, (T)b->beta})
+        if (b->beta == 2.0) KL_BETA_EPI(BETA_TWO);
+        else if (b->beta == 0.0) KL_BETA_EPI(BETA_ZERO);
+        else KL_BETA_EPI(BETA_GEN);
+#undef KL_BETA_EPI
+    };
+    auto with_weight = [&](auto with_loss) {
+        if (b->Om) with_kind(ElemWeight<T>{(const T *)b->Om}, with_loss);
+        else with_kind(NoWeight{}, with_loss);
+    };
+    if (loss) with_weight(std::true_type{}); else with_weight(std::false_type{});
+    HIPCHK(hipGetLastError());
+    if (!loss) return;
+    hipLaunchKernelGGL(k_sum_doubles_batch, dim3((unsigned)b->count), dim3(1024), 0, b->stream, (const double *)b->loss_part,
+                       pl.loss_part_count, b->loss_xchg, b->st, 1, tol_abs, b->errors, b->cap);
+    HIPCHK(hipGetLastError());
+}
+
+// W_new = W * ((A.H^T) / (B.H^T))^gamma: form A of k_gemm_dual_batch (the tile of H^T shared) with the rule in its epilogue, or over
+// feature chunks into two slab sets and the rule from them
+template <typename T>
+void beta_W(klnmf_batch *b) {
+    const ProblemPlan &pl = b->plan;
+    typedef FacBeta<T> Fac;
+    const bool split = pl.wsplit > 1;
+    const int ytiles = (int)((b->n + GT - 1) / GT);
+    const dim3 grid((unsigned)((b->k + GT - 1) / GT), (unsigned)(b->count * ytiles), (unsigned)(split ? pl.wsplit : 1));
+    const int chunk = split ? pl.wchunk : (int)b->f + GK;
+    const int64_t count = b->n * b->k;
+    const EpiW<T, Fac> epi{(const T *)b->W[b->cur], (T *)b->W[b->cur ^ 1], b->k, Fac{(T)b->beta_gamma()}};
+#define KL_BBW_ARGS (int)b->n, (int)b->k, (int)b->f, (const T *)b->Q, (int64_t)b->f, (int64_t)1, b->n * b->f, (const T *)b->H, (int64_t)1, \
+                    (int64_t)b->f, b->k * b->f, (const T *)b->Bt, b->n * b->f, chunk, (const DevState *)b->st, ytiles
+    if (!split) {
+        hipLaunchKernelGGL((k_gemm_dual_batch<T, EpiW<T, Fac>, true>), grid, dim3(256), 0, b->stream, KL_BBW_ARGS, epi);
+        HIPCHK(hipGetLastError());
+        return;
+    }
+    hipLaunchKernelGGL((k_gemm_dual_batch<T, EpiWpart<T, 2>, true>), grid, dim3(256), 0, b->stream, KL_BBW_ARGS,
+                       EpiWpart<T, 2>{{(T *)b->Wpart, (T *)b->WDpart}, b->k, count});
+#undef KL_BBW_ARGS
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL((k_wrule_batch<T, Fac>), dim3(grid_for(count), (unsigned)b->count), dim3(256), 0, b->stream,
+                       NumSlabs<T, 2>{{{(const T *)b->Wpart, (const T *)b->WDpart}}, pl.wsplit, count}, (const DevState *)b->st, epi);
+    HIPCHK(hipGetLastError());
+}
+
+// the H numerator's and denominator's slabs (W[widx]^T.A, W[widx]^T.B) per row chunk: form B of k_gemm_dual_batch (the tile of
+// W^T shared); sum_slabs: and their sums
+template <typename T>
+void beta_N(klnmf_batch *b, int widx, bool sum_slabs) {
+    const ProblemPlan &pl = b->plan;
+    const int ytiles = (int)((b->k + GT - 1) / GT);
+    const dim3 grid((unsigned)((b->f + GT - 1) / GT), (unsigned)(b->count * ytiles), (unsigned)pl.nsplit);
+    const int64_t count = b->k * b->f;
+    hipLaunchKernelGGL((k_gemm_dual_batch<T, EpiN<T, 2>, false>), grid, dim3(256), 0, b->stream, (int)b->k, (int)b->f, (int)b->n,
+                       (const T *)b->W[widx], (int64_t)1, (int64_t)b->k, b->n * b->k, (const T *)b->Q, (int64_t)b->f, (int64_t)1,
+                       b->n * b->f, (const T *)b->Bt, b->n * b->f, pl.kchunk, (const DevState *)b->st, ytiles,
+                       EpiN<T, 2>{{(T *)b->Npart, (T *)b->Dpart}, b->f, count});
+    HIPCHK(hipGetLastError());
+    if (!sum_slabs) return;
+    hipLaunchKernelGGL((k_sum_partials_sets_batch<T, 2>), dim3(grid_for(count), (unsigned)b->count), dim3(256), 0, b->stream,
+                       NumArray<T, 2>{{(const T *)b->Npart, (const T *)b->Dpart}}, OutSets<T, 2>{{(T *)b->numer, (T *)b->denom}}, count,
+                       pl.nsplit, (const DevState *)b->st);
+    HIPCHK(hipGetLastError());
+}
+
+// the H rule under FacBeta on its three routes, each leaving the rows' sums (one per segment) in hpart, and behind it the
+// compensation W[widx][:, a] *= sum[a]
+template <typename T>
+void beta_H(klnmf_batch *b, bool from_slabs, int widx) {
+    const ProblemPlan &pl = b->plan;
+    typedef FacBeta<T> Fac;
+    typedef NumArray<T, 2> Arr;
+    typedef NumSlabs<T, 2> Slabs;
+    const Fac fac{(T)b->beta_gamma()};
+    const Arr sums{{(const T *)b->numer, (const T *)b->denom}}, slab0{{(const T *)b->Npart, (const T *)b->Dpart}};
+    const dim3 rows((unsigned)b->k, (unsigned)b->count), segs((unsigned)pl.hseg_n, (unsigned)b->k, (unsigned)b->count);
+    const int nseg = (!from_slabs && pl.hseg_n > 1) ? pl.hseg_n : 1;
+    if (from_slabs) {
+        hipLaunchKernelGGL((k_update_H_sums_batch<T, Slabs, Fac>), rows, dim3(256), 0, b->stream, (T *)b->H,
+                           RuleIn<Slabs, Fac>{Slabs{slab0, pl.nsplit, b->k * b->f}, fac}, b->f, b->hpart, (const DevState *)b->st);
+    } else if (nseg > 1) {
+        hipLaunchKernelGGL((k_update_H_part_batch<T, Fac>), segs, dim3(256), 0, b->stream, (T *)b->H, RuleIn<Arr, Fac>{sums, fac}, b->f,
+                           pl.hseg, b->hpart, (const DevState *)b->st);
+        hipLaunchKernelGGL((k_update_H_norm_batch<T>), segs, dim3(256), 0, b->stream, (T *)b->H, b->f, pl.hseg, (const double *)b->hpart,
+                           (const DevState *)b->st);
+    } else {
+        hipLaunchKernelGGL((k_update_H_sums_batch<T, Arr, Fac>), rows, dim3(256), 0, b->stream, (T *)b->H, RuleIn<Arr, Fac>{sums, fac},
+                           b->f, b->hpart, (const DevState *)b->st);
+    }
+    HIPCHK(hipGetLastError());
+    const int64_t count = b->n * b->k;
+    hipLaunchKernelGGL((k_scale_W_cols_batch<T>), dim3(grid_for(count), (unsigned)b->count), dim3(256), 0, b->stream, (T *)b->W[widx], count,
+                       b->k, (const double *)b->hpart, nseg, (const DevState *)b->st);
+    HIPCHK(hipGetLastError());
+}
+
 // ---- a CSR batch's stages: api_loop.hip's sparse_Q and the blocked arms of exact_W / exact_N for B problems ----------------------
 // k_spb_*<T, KC, ..>: KC = 1, 2, 4, 8 component chunks of 64 by k, as a context picks them
 #define KL_BATCH_KC(b, LAUNCH)                                   \
@@ -325,6 +458,18 @@ void batch_iteration(klnmf_batch *b, int fit, double tol_abs) {
         if (fit) {
             BATCH_CALL(b, csr_N, b->cur ^ 1);
             BATCH_CALL(b, batch_H, false);
+        }
+        b->cur ^= 1;
+        return;
+    }
+    if (b->beta_on()) {      // the beta cost: A, B and the loss at (W, H), the W rule from them; a fit: A, B at (W_new, H), the H rule
+        BATCH_CALL(b, beta_AB, b->cur, true, tol_abs);
+        BATCH_CALL(b, beta_W);
+        if (fit) {
+            const bool slabs = h_from_slabs(&b->plan);
+            BATCH_CALL(b, beta_AB, b->cur ^ 1, false, 0.0);
+            BATCH_CALL(b, beta_N, b->cur ^ 1, !slabs);
+            BATCH_CALL(b, beta_H, slabs, b->cur ^ 1);
         }
         b->cur ^= 1;
         return;
@@ -496,6 +641,9 @@ void start_states(klnmf_batch *b) {
 void presence_check_all(klnmf_batch *b, const std::string &who, int64_t rows, int64_t row0, bool rows_ok, const int64_t *col_bounds, int n_mod) {
     if (b->sparse) fail(KLNMF_ERR_UNSUPP, who + ": CSR problems have no masked kernels (the ratio lives on the stored entries only)");
     presence_check_args(who, b->mask_dims(), rows, row0, rows_ok, col_bounds, n_mod);
+    if (b->beta_on())
+        fail(KLNMF_ERR_UNSUPP, who + ": the batch runs a beta divergence (klnmf_batch_set_divergence), which has no masked form; upload the "
+                                     "mask as weights (klnmf_batch_upload_weights) or klnmf_batch_set_divergence(b, 1.0) first");
     presence_check_bounds(*b, who, "batch", col_bounds, n_mod);
 }
 
@@ -791,6 +939,92 @@ int klnmf_batch_clear_presence(klnmf_batch *b) {
     return guarded([&] {
         need_problem(b);
         presence_drop(*b, *b);
+    });
+}
+
+// ---- klnmf_batch_beta.h --------------------------------------------------------------------------------------------------------
+// klnmf_set_divergence for a batch: the refusals, then -- all or nothing -- what only the beta loop holds
+int klnmf_batch_set_divergence(klnmf_batch *b, double beta) {
+    return guarded([&] {
+        need_problem(b);
+        const std::string who = "klnmf_batch_set_divergence";
+        if (!std::isfinite(beta)) fail(KLNMF_ERR_ARG, who + ": beta must be finite");
+        if (beta == 1.0) {      // the KL loop again: nothing of the beta cost stays, the weights neither
+            if (!b->beta_on()) return;
+            HIPCHK(hipStreamSynchronize(b->stream));
+            b->dfree(b->Bt); b->dfree(b->Om); b->dfree(b->Dpart); b->dfree(b->denom); b->dfree(b->WDpart);
+            if (b->own_hpart) { void *h = b->hpart; b->dfree(h); b->hpart = nullptr; }
+            b->forget_beta();
+            return;
+        }
+        if (b->sparse) fail(KLNMF_ERR_UNSUPP, who + ": CSR problems have no beta kernels (the ratio lives on the stored entries only)");
+        if (b->prec == KLNMF_PREC_F32 && beta != 0.0 && ((float)beta == 1.0f || (float)beta == 0.0f))
+            fail(KLNMF_ERR_ARG, who + ": in KLNMF_PREC_F32 the kernels see beta rounded to fp32, and this beta rounds to 1 or to 0 "
+                                      "without being it (the general cost divides by beta (beta - 1)); give 1 or 0 itself");
+        if (b->presence())
+            fail(KLNMF_ERR_UNSUPP, who + ": the batch holds a presence mask (klnmf_batch_upload_presence), and the beta rules have no masked "
+                                         "form; klnmf_batch_clear_presence first and upload the mask as weights");
+        if (b->beta_on()) { b->beta = beta; return; }      // (the buffers are there)
+        HIPCHK(hipStreamSynchronize(b->stream));
+        const ProblemPlan &pl = b->plan;
+        const size_t B = (size_t)b->count, es = b->esize(), n = (size_t)b->n, f = (size_t)b->f, k = (size_t)b->k;
+        const bool have_sums = b->hpart != nullptr;         // (long rows: the problem holds [B][k][hseg_n] already)
+        void *bt = nullptr, *sums = nullptr, *dpart = nullptr, *denom = nullptr, *wdpart = nullptr;
+        try {
+            bt = b->dalloc(B * n * f * es);
+            if (!have_sums) sums = b->dalloc(sizeof(double) * B * k);
+            dpart = b->dalloc(B * (size_t)pl.nsplit * k * f * es);
+            denom = b->dalloc(B * k * f * es);
+            if (pl.wsplit > 1) wdpart = b->dalloc(B * (size_t)pl.wsplit * n * k * es);
+        } catch (...) {                                     // all or nothing: a failed call leaves the batch at beta = 1
+            (void)hipStreamSynchronize(b->stream);
+            b->dfree(bt); b->dfree(sums); b->dfree(dpart); b->dfree(denom); b->dfree(wdpart);
+            throw;
+        }
+        b->Bt = bt; b->Dpart = dpart; b->denom = denom; b->WDpart = wdpart;
+        if (!have_sums) { b->hpart = (double *)sums; b->own_hpart = true; }
+        b->beta = beta;
+    });
+}
+
+int klnmf_batch_get_divergence(klnmf_batch *b, double *beta) {
+    return guarded([&] {
+        need_problem(b);
+        if (!beta) fail(KLNMF_ERR_ARG, "klnmf_batch_get_divergence: null destination");
+        *beta = b->beta;
+    });
+}
+
+// klnmf_upload_weights for problem p of a beta batch: Om_p[row0 + i, col0 + j] = src[i, j]; the first call takes every problem's Om
+// filled with 1
+int klnmf_batch_upload_weights(klnmf_batch *b, int p, const void *src, int dtype, int64_t rows, int64_t cols, int64_t ld, int64_t row0,
+                               int64_t col0) {
+    return guarded([&] {
+        need_p(b, p);
+        if (!b->beta_on())
+            fail(KLNMF_ERR_UNSUPP, "klnmf_batch_upload_weights: the batch runs the Kullback-Leibler loop (beta = 1), which has no weighted "
+                                   "batch kernels; klnmf_batch_set_divergence first, or klnmf_batch_upload_presence for a mask");
+        if (!src) fail(KLNMF_ERR_ARG, "null source");
+        check_dtype(dtype);
+        check_block(b->n, b->f, rows, cols, ld, row0, col0);
+        if (!b->Om) {
+            HIPCHK(hipStreamSynchronize(b->stream));
+            void *om = b->dalloc((size_t)b->count * (size_t)b->n * (size_t)b->f * b->esize(), false);
+            try {
+                fill_ones(b->stream, om, b->prec == KLNMF_PREC_F64, (int64_t)b->count * b->n * b->f);
+                HIPCHK(hipStreamSynchronize(b->stream));
+            } catch (...) {
+                (void)hipStreamSynchronize(b->stream);
+                b->dfree(om);
+                throw;
+            }
+            b->Om = om;
+        }
+        if (rows * cols == 0) return;
+        staged_upload(b->stream, src, dt_size(dtype), rows, cols, ld, [&](const void *d, int64_t r0, int64_t rr) {
+            place_rows(b->stream, problem_ptr(b, b->Om, p, b->n * b->f), b->prec == KLNMF_PREC_F64, b->f, d, dtype == KLNMF_DT_F64, rr, cols, ld,
+                       row0 + r0, col0, 1.0, nullptr);
+        });
     });
 }
 

@@ -21,9 +21,16 @@
 // h_product, block_sum, decide_here -- over the same chunk counts, so a problem in a batch has the bits of the same problem alone.
 // Stop state: one DevState per problem; the blocks of a stopped problem return at their first instruction, as every block of a
 // stopped context does, and nothing waits on anything.
+// A beta batch (klnmf_batch_beta.h) -- every problem under one beta != 1, with its own weights Om where uploaded -- runs beta.hip.h's
+// loop on the same layout, with B [B][n][f] beside Q (= A), a denominator set beside every numerator set and the rows' sums in
+// hpart [B][k][segments]:
+//   k_gemm_batch<.., EpiBeta<..>>                     the ratio pass: A, B, (LOSS) the loss partials
+//   k_gemm_dual_batch<.., EpiW<T, FacBeta<T>> / EpiWpart<T, 2>, A>, <.., EpiN<T, 2>, B>   k_gemm_dual's own text (gemm_dual_body.hip.h)
+//   k_wrule_batch / k_update_H_part_batch under FacBeta, k_sum_partials_sets_batch<T, 2>, k_update_H_sums_batch, k_scale_W_cols_batch
 // CSR problems on a batch -- the batched forms of the sparse loop's kernels and their layout: batch_sparse.hip.h, included below.
 #pragma once
 #include "presence.hip.h"
+#include "beta.hip.h"
 #include "batch_sparse.hip.h"
 
 namespace klnmf {
@@ -80,6 +87,34 @@ __device__ __forceinline__ EpiN<T, 1> at_problem(EpiN<T, 1> e, int p, int, int) 
     return e;
 }
 
+// the beta policies: V, A (the Q buffer) and B of problem p; with weights also Om
+template <typename T, bool LOSS, int KIND>
+__device__ __forceinline__ EpiBeta<T, NoWeight, LOSS, KIND> at_problem(EpiBeta<T, NoWeight, LOSS, KIND> e, int p, int M, int N) {
+    const int64_t o = (int64_t)p * M * N;
+    e.V += o; e.A += o; e.Bm += o;      // (loss_part: indexed by blockIdx.y, which carries p)
+    return e;
+}
+template <typename T, bool LOSS, int KIND>
+__device__ __forceinline__ EpiBeta<T, ElemWeight<T>, LOSS, KIND> at_problem(EpiBeta<T, ElemWeight<T>, LOSS, KIND> e, int p, int M, int N) {
+    const int64_t o = (int64_t)p * M * N;
+    e.V += o; e.A += o; e.Bm += o;
+    e.wt.Om += o;
+    return e;
+}
+// numerator and denominator slabs side by side (EpiW<T, FacBeta<T>>: the generic EpiW above -- FacBeta holds no pointer)
+template <typename T>
+__device__ __forceinline__ EpiWpart<T, 2> at_problem(EpiWpart<T, 2> e, int p, int, int) {
+    const int64_t o = (int64_t)p * gridDim.z * e.slab;
+    e.P[0] += o; e.P[1] += o;
+    return e;
+}
+template <typename T>
+__device__ __forceinline__ EpiN<T, 2> at_problem(EpiN<T, 2> e, int p, int, int) {
+    const int64_t o = (int64_t)p * gridDim.z * e.slab;
+    e.Npart[0] += o; e.Npart[1] += o;
+    return e;
+}
+
 // k_gemm for B problems: grid (column tiles, B x ytiles, chunks); A and B `aps` / `bps` elements apart from problem to problem.
 // The tile loop is k_gemm's own text (gemm_body.hip.h) on problem p's operands, in the instantiation the exact modes run
 // (64 x 64 tiles on the fp64 / fp32 MFMA).
@@ -97,6 +132,22 @@ __global__ __launch_bounds__(256, 3) void k_gemm_batch(int M, int N, int K, cons
 #define KL_GEMM_ROW_TILE row_tile
 #include "gemm_body.hip.h"
 #undef KL_GEMM_ROW_TILE
+}
+
+// k_gemm_dual (weighted.hip.h) for B problems: the grid and the problem index of k_gemm_batch; A, B and X2 `aps` / `bps` / `xps`
+// elements apart from problem to problem.  The tile loop is k_gemm_dual's own text (gemm_dual_body.hip.h) on problem p's operands.
+template <typename T, typename Epi, bool SHARE_B>
+__global__ __launch_bounds__(256, 2) void k_gemm_dual_batch(int M, int N, int K, const T *A0, int64_t ars, int64_t acs, int64_t aps,
+                                                            const T *B0, int64_t brs, int64_t bcs, int64_t bps, const T *X20, int64_t xps,
+                                                            int kchunk, const DevState *st, int ytiles, Epi epi0) {
+    const int p = blockIdx.y / ytiles;
+    if (st[p].stop) return;
+    const T *A = A0 + p * aps, *B = B0 + p * bps, *X2 = X20 + p * xps;
+    Epi epi = at_problem(epi0, p, M, N);
+    const int row_tile = (int)blockIdx.y - p * ytiles;
+#define KL_GEMM_DUAL_ROW_TILE row_tile
+#include "gemm_dual_body.hip.h"
+#undef KL_GEMM_DUAL_ROW_TILE
 }
 
 // k_sum_doubles with the stop rule, block p for problem p: `count` partials each, the loss into out[2 p]
@@ -140,9 +191,22 @@ __global__ void k_sum_partials_batch(NumArray<T, 1> part, T *out, int64_t count,
         out[e] = slabs.get(e)[0];
 }
 
+// k_sum_partials<T, S>, grid (.., B): S slab sets into S sums (a beta batch: numerator and denominator)
+template <typename T, int S>
+__global__ void k_sum_partials_sets_batch(NumArray<T, S> part, OutSets<T, S> out, int64_t count, int nslab, const DevState *st) {
+    const int p = blockIdx.y;
+    if (st[p].stop) return;
+    const NumSlabs<T, S> slabs{part.at((int64_t)p * nslab * count), nslab, count};
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < count; e += (int64_t)gridDim.x * blockDim.x) {
+        const Sums<T, S> v = slabs.get(e);
+#pragma unroll
+        for (int s = 0; s < S; ++s) out.p[s][p * count + e] = v[s];
+    }
+}
+
 // elements from one problem's numerator source to the next's
-template <typename T> __device__ __forceinline__ int64_t problem_stride(const NumArray<T, 1> &, int64_t kf) { return kf; }
-template <typename T> __device__ __forceinline__ int64_t problem_stride(const NumSlabs<T, 1> &s, int64_t) { return s.nslab * s.slab; }
+template <typename T, int S> __device__ __forceinline__ int64_t problem_stride(const NumArray<T, S> &, int64_t kf) { return kf; }
+template <typename T, int S> __device__ __forceinline__ int64_t problem_stride(const NumSlabs<T, S> &s, int64_t) { return s.nslab * s.slab; }
 
 // k_update_H, grid (k, B); Fac: FacNum, or FacPresH with D [B][k][M]
 template <typename T, typename Num, typename Fac = FacNum>
@@ -162,9 +226,43 @@ __global__ __launch_bounds__(256) void k_update_H_batch(T *H, RuleIn<Num, Fac> i
     for (int64_t j = threadIdx.x; j < f; j += blockDim.x) row[j] = row[j] / d;
 }
 
+// k_update_H_sums (beta.hip.h), grid (k, B): k_update_H_batch that also leaves each row's sum in sums[p k + a]
+template <typename T, typename Num, typename Fac>
+__global__ __launch_bounds__(256) void k_update_H_sums_batch(T *H, RuleIn<Num, Fac> in, int64_t f, double *sums, const DevState *st) {
+    const int p = blockIdx.y;
+    if (st[p].stop) return;
+    __shared__ double red[16];
+    __shared__ double total;
+    const int64_t kf = (int64_t)gridDim.x * f;
+    T *row = H + p * kf + blockIdx.x * f;
+    const double s = h_product(row, in.num.at(p * problem_stride(in.num, kf) + blockIdx.x * f),
+                               fac_at_problem(in.fac, p, 0, (int64_t)gridDim.x), (int64_t)blockIdx.x, 0, f);
+    const double t = block_sum(s, red);
+    if (threadIdx.x == 0) { total = t; sums[(int64_t)p * gridDim.x + blockIdx.x] = t; }
+    __syncthreads();
+    const T d = (T)(kEpsNorm + total);
+    for (int64_t j = threadIdx.x; j < f; j += blockDim.x) row[j] = row[j] / d;
+}
+
+// k_scale_W_cols (beta.hip.h), grid (.., B): W_p[:, a] *= the sum of row a of H_p before its normalisation, part [B][k][nseg] re-added
+// z ascending (k_update_H_norm's order; nseg = 1: k_update_H_sums_batch's sums)
+template <typename T>
+__global__ __launch_bounds__(256) void k_scale_W_cols_batch(T *W0, int64_t count, int64_t k, const double *part0, int nseg, const DevState *st) {
+    const int p = blockIdx.y;
+    if (st[p].stop) return;
+    T *W = W0 + p * count;
+    const double *part = part0 + (int64_t)p * k * nseg;
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < count; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t a = e % k;
+        double total = 0;
+        for (int z = 0; z < nseg; ++z) total += part[a * nseg + z];
+        W[e] = W[e] * (T)total;
+    }
+}
+
 // k_update_H_part / k_update_H_norm, grid (segments, k, B); part [B][k][segments]
 template <typename T, typename Fac = FacNum>
-__global__ __launch_bounds__(256) void k_update_H_part_batch(T *H, RuleIn<NumArray<T, 1>, Fac> in, int64_t f, int64_t seg,
+__global__ __launch_bounds__(256) void k_update_H_part_batch(T *H, RuleIn<NumArray<T, Fac::S>, Fac> in, int64_t f, int64_t seg,
                                                              double *part, const DevState *st) {
     const int p = blockIdx.z;
     if (st[p].stop) return;

@@ -47,107 +47,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm_dual(int M, int N, int K, const
                                                       const T *B, int64_t brs, int64_t bcs, const T *X2, int kchunk,
                                                       const DevState *st, Epi epi) {
     if (st && st->stop) return;
-    __shared__ T As[GK][GT + 4];
-    __shared__ T Bs[GK][GT + 4];
-    __shared__ T Xs[GK][GT + 4];
-    const int tid = threadIdx.x;
-    const int m0 = blockIdx.y * GT, n0 = blockIdx.x * GT;
-    const int kbeg = blockIdx.z * kchunk;
-    const int kend = min(K, kbeg + kchunk);
-    typedef typename Acc4<T>::type acc_t;
-    acc_t acc1[4], acc2[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) { acc1[t] = acc_t{T(0), T(0), T(0), T(0)}; acc2[t] = acc_t{T(0), T(0), T(0), T(0)}; }
-
-    const bool a_k_contig = (acs == 1);
-    const bool b_n_contig = (bcs == 1);
-    const bool m_inside = m0 + GT <= M, n_inside = n0 + GT <= N;
-    constexpr int PER = GT * GK / 256;
-    T ra[PER], rb[PER], rx[PER];
-    auto fetch = [&](int k0) {
-        const bool k_inside = k0 + GK <= kend;
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            const int e = tid + 256 * u;
-            int m, kk;
-            if (a_k_contig) { kk = e % GK; m = e / GK; } else { m = e % GT; kk = e / GT; }
-            const int gm = m0 + m, gk = k0 + kk;
-            const int64_t o = (int64_t)gm * ars + (int64_t)gk * acs;
-            const bool ok = (m_inside && k_inside) || (gm < M && gk < kend);
-            ra[u] = ok ? A[o] : T(0);
-            if constexpr (SHARE_B) rx[u] = ok ? X2[o] : T(0);
-        }
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            const int e = tid + 256 * u;
-            int n, kk;
-            if (b_n_contig) { n = e % GT; kk = e / GT; } else { kk = e % GK; n = e / GK; }
-            const int gn = n0 + n, gk = k0 + kk;
-            const int64_t o = (int64_t)gk * brs + (int64_t)gn * bcs;
-            const bool ok = (n_inside && k_inside) || (gn < N && gk < kend);
-            rb[u] = ok ? B[o] : T(0);
-            if constexpr (!SHARE_B) rx[u] = ok ? X2[o] : T(0);
-        }
-    };
-    auto commit = [&]() {
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            const int e = tid + 256 * u;
-            int m, kk;
-            if (a_k_contig) { kk = e % GK; m = e / GK; } else { m = e % GT; kk = e / GT; }
-            As[kk][m] = ra[u];
-            if constexpr (SHARE_B) Xs[kk][m] = rx[u];
-        }
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            const int e = tid + 256 * u;
-            int n, kk;
-            if (b_n_contig) { n = e % GT; kk = e / GT; } else { kk = e % GK; n = e / GK; }
-            Bs[kk][n] = rb[u];
-            if constexpr (!SHARE_B) Xs[kk][n] = rx[u];
-        }
-    };
-    const int lane = tid & 63, wv = tid >> 6;
-    if (kbeg < kend) { fetch(kbeg); commit(); }
-    __syncthreads();
-    for (int k0 = kbeg; k0 < kend; k0 += GK) {
-        const bool more = k0 + GK < kend;
-        if (more) fetch(k0 + GK);
-#pragma unroll
-        for (int k4 = 0; k4 < GK / 4; ++k4) {
-            const int kr = 4 * k4 + (lane >> 4), ac = 16 * wv + (lane & 15);
-            const T av = As[kr][ac];
-            if constexpr (SHARE_B) {
-                const T xv = Xs[kr][ac];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const T bv = Bs[kr][16 * t + (lane & 15)];
-                    acc1[t] = mfma_16x16x4(av, bv, acc1[t]);
-                    acc2[t] = mfma_16x16x4(xv, bv, acc2[t]);
-                }
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const T bv = Bs[kr][16 * t + (lane & 15)];
-                    const T xv = Xs[kr][16 * t + (lane & 15)];
-                    acc1[t] = mfma_16x16x4(av, bv, acc1[t]);
-                    acc2[t] = mfma_16x16x4(av, xv, acc2[t]);
-                }
-            }
-        }
-        __syncthreads();
-        if (more) {
-            commit();
-            __syncthreads();
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            const int r = m0 + 16 * wv + (MfmaRow<T>::kLane * (lane >> 4) + MfmaRow<T>::kReg * rr), c = n0 + 16 * t + (lane & 15);
-            if (r < M && c < N) epi.apply(r, c, acc1[t][rr], acc2[t][rr]);
-        }
+#define KL_GEMM_DUAL_ROW_TILE blockIdx.y
+#include "gemm_dual_body.hip.h"      // (the tile loop and the epilogue calls: shared with k_gemm_dual_batch)
+#undef KL_GEMM_DUAL_ROW_TILE
 }
 
 // the weight buffer before its first block: all ones

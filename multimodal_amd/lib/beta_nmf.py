@@ -11,10 +11,12 @@ gamma = 1/(2-beta) below 1, 1 up to 2, 1/(beta-1) beyond; H's rows are normalise
 what the rules left.  Every half step forms its own A and B: the loss record never rises.
 """
 import numpy as np
+import scipy.sparse as sp
 
 from .. import _native
+from . import nmf
 from .array_utils import normalize_sum
-from .nmf import KLdivNMF, _dense, _note_once, _out_dtype, _scale, check_weights
+from .nmf import KLdivNMF, _dense, _note_once, _out_dtype, _scale, check_non_negative, check_weights
 from .sklearn_utils import atleast2d_or_csr
 
 
@@ -31,6 +33,70 @@ def beta_precision(precision):
     _note_once(('beta', precision), "BetaNMF: beta != 1 with precision=%r runs on the fp32 beta kernels (precision='f32'); "
                "the beta update exists in 'f64' and 'f32' only\n" % (precision,))
     return 'f32'
+
+
+def beta_batch_precision(models):
+    """'f64' / 'f32' if `models` can run as ONE beta batch (klnmf_batch_set_divergence): every model a `BetaNMF` of one and the same
+    beta != 1, the models agreeing as `nmf.batch_precision` asks -- n_components, tol, max_iter, precision, one and the same single
+    device -- with the arithmetic `beta_precision` names (what the single beta call runs in).  None otherwise."""
+    first = models[0]
+    if not all(isinstance(m, BetaNMF) and m.beta == first.beta for m in models) or first.beta == 1.0:
+        return None
+    same = all((m.n_components, m.tol, m.max_iter, m.precision, m.devices) ==
+               (first.n_components, first.tol, first.max_iter, first.precision, first.devices) for m in models)
+    if not same or len(first.devices) != 1 or not 1 <= len(models) <= _native.BATCH_MAX:
+        return None
+    return beta_precision(first.precision)
+
+
+def fit_transform_batch(models, Xs, weights=None, _fit=True, return_errors=False):
+    """[models[i].fit_transform(Xs[i], weights=weights[i], _fit=_fit, return_errors=return_errors) for i ...] as ONE beta batch
+    (csrc/batch.hip.h, include/klnmf_batch_beta.h) where that is possible: every model a `BetaNMF` of one and the same beta != 1, all
+    Xs dense and of one shape, the models as `beta_batch_precision` asks, and every `weights` entry None, a scalar or an array that
+    passes `check_weights` -- arrays are uploaded as the problems' weights (a model without one is weighted by ones) and the models
+    end with `last_weights_route` 'array'.  Every stage of a beta iteration is then one launch for all problems; each model stops
+    on its own loss record.  Everything else is `nmf.fit_transform_batch`'s, unchanged: beta = 1 throughout runs its batches, and
+    mixed betas, sparse Xs (which raise as in `fit_transform`), unequal shapes and device lists run one after another.  Each
+    model gets `last_batch_size`; the initial dictionaries are drawn in list order, so the global numpy stream ends where the
+    sequential calls leave it."""
+    models, Xs = list(models), list(Xs)
+    if weights is not None:
+        weights = list(weights)
+
+    def elsewhere():
+        return nmf.fit_transform_batch(models, Xs, weights=weights, _fit=_fit, return_errors=return_errors)
+    if not models or len(models) != len(Xs) or (weights is not None and len(weights) != len(models)):
+        return elsewhere()
+    precision = beta_batch_precision(models) if not any(sp.issparse(X) for X in Xs) else None
+    if precision is None:
+        return elsewhere()
+    Xs = [atleast2d_or_csr(X) for X in Xs]
+    if len(set(X.shape for X in Xs)) != 1:
+        return elsewhere()
+    try:
+        Oms = [None] * len(models) if weights is None else [check_weights(w, X.shape) for w, X in zip(weights, Xs)]
+    except ValueError:
+        return elsewhere()      # (the sequential calls raise it where they meet it)
+    blocks = []
+    for X in Xs:
+        check_non_negative(X, "NMF.fit")
+        blocks.append(_dense(X))
+    n, f = blocks[0].shape
+    beta = models[0].beta
+    weighted = any(w is not None for w in Oms)
+
+    def name_cost(batch):
+        batch.set_divergence(beta)
+        for p, w in enumerate(Oms):
+            if w is not None:
+                batch.upload_weights(p, w)
+    uploads = [lambda batch, p, b=b: batch.upload_V(p, b) for b in blocks]
+    out_dtype_ofs = [lambda H_init, b=b: _out_dtype(H_init, b) for b in blocks]
+    outs = nmf.fit_uploaded_batch(models, precision, n, f, uploads, out_dtype_ofs, _fit=_fit, return_errors=return_errors,
+                                  after_uploads=name_cost)
+    for m in models:
+        m.last_weights_route = 'array' if weighted else None
+    return outs
 
 
 class BetaNMF(KLdivNMF):

@@ -817,13 +817,15 @@ def batch_precision(models, n, f, weighted=False, sparse=False):
 
 
 def fit_uploaded_batch(models, precision, n_samples, n_features, uploads, out_dtype_ofs, _fit=True, return_errors=False, masked=False,
-                       sparse_nnzs=None):
+                       sparse_nnzs=None, after_uploads=None):
     """`KLdivNMF._fit_uploaded` for len(models) dense problems of one shape as one `_native.Batch`: problem p is placed by
     `uploads[p](batch, p)`; model p ends as its own `_fit_uploaded` would leave it, with `last_batch_size` set.  masked: the
     uploads place a presence mask behind every V (`Batch.upload_presence*`, one set of bounds) and the loop is the masked one;
     every model ends with `last_weights_route` 'presence' (None otherwise).  sparse_nnzs: the problems are CSR ones of
     sparse_nnzs[p] stored entries (`Batch.set_problem_sparse`) that the uploads fill with `Batch.upload_csr_rows` /
-    `upload_csr_device_rows`.  Returns the list of the calls' results."""
+    `upload_csr_device_rows`.  after_uploads: a hook `after_uploads(batch)` called behind every problem's upload and in front of the
+    dictionaries and `init_W` -- where another cost function is named to the batch (`beta_nmf.fit_transform_batch`); None: every
+    dictionary is set right behind its problem's upload, as ever.  Returns the list of the calls' results."""
     B = len(models)
     max_iter = int(models[0].max_iter)
     H_inits = []
@@ -841,8 +843,13 @@ def fit_uploaded_batch(models, precision, n_samples, n_features, uploads, out_dt
             batch.set_problem(n_samples, n_features, k, max_iter)
         for p in range(B):
             uploads[p](batch, p)
-            batch.set_H(p, H_inits[p])
-        batch.init_W()                        # W0 = X . H_init^T (nmf.py:156)
+            if after_uploads is None:
+                batch.set_H(p, H_inits[p])
+        if after_uploads is not None:
+            after_uploads(batch)
+            for p in range(B):
+                batch.set_H(p, H_inits[p])
+        batch.init_W()                       # W0 = X . H_init^T (nmf.py:156)
         for p, m in enumerate(models):
             if _fit:
                 m.components_ = H_inits[p]    # nmf.py:203-204
