@@ -200,6 +200,15 @@ BATCH_BETA_SIGNATURES = {
     'klnmf_batch_upload_weights': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _i64, _i64, _i64, _i64, _i64]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/klnmf_nearest.h (the fused nearest-example search), which the same
+# library exports
+NEAREST_SIGNATURES = {
+    'klnmf_nearest_work_bytes': (_c.c_int, [_i64, _i64, _c.POINTER(_c.c_uint64)]),
+    'klnmf_nearest_many_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _i64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                             _c.c_uint64]),
+    'klnmf_nearest': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _i64, _i64, _i64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+}
+
 _lib = None
 
 
@@ -224,7 +233,8 @@ def load():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(BATCH_MASK_SIGNATURES.items()) \
-            + list(BATCH_CSR_SIGNATURES.items()) + list(BETA_SIGNATURES.items()) + list(BATCH_BETA_SIGNATURES.items()):
+            + list(BATCH_CSR_SIGNATURES.items()) + list(BETA_SIGNATURES.items()) + list(BATCH_BETA_SIGNATURES.items()) \
+            + list(NEAREST_SIGNATURES.items()):
         fn = getattr(lib, name)     # AttributeError if a symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -323,6 +333,66 @@ def all_distances_device(dA, lda, dB, ldb, dout, na, nb, d, metric, f64=True, de
     """out[na, nb] = metric(A[i], B[j]) between DEVICE matrices: klnmf_all_distances_device."""
     _check(load().klnmf_all_distances_device(device, DT_F64 if f64 else DT_F32, int(metric), int(na), int(nb), int(d),
                                              _c.c_void_p(dA), int(lda), _c.c_void_p(dB), int(ldb), _c.c_void_p(dout)))
+
+
+DIST_MASK_ALL = 31
+NEAREST_MAX_JOBS = 1 << 20
+
+
+class NearestJob(_c.Structure):
+    """klnmf_nearest_job: A [na, d] against B [nb, d], device pointers, row strides in elements."""
+    _fields_ = [('A', _c.c_void_p), ('lda', _i64), ('B', _c.c_void_p), ('ldb', _i64), ('na', _i64), ('nb', _i64), ('d', _i64)]
+
+
+def metric_mask(metrics):
+    """The bit mask of the measures DIST_* in `metrics` (bit i = measure i)."""
+    mask = 0
+    for m in metrics:
+        mask |= 1 << int(m)
+    return mask
+
+
+def mask_metrics(mask):
+    """The measures of a mask in the order of a result row: ascending."""
+    return [m for m in range(5) if int(mask) >> m & 1]
+
+
+def nearest_work_bytes(count, total_rows):
+    """Bytes of device workspace `nearest_many_device` needs for `count` jobs of `total_rows` rows: klnmf_nearest_work_bytes."""
+    out = _c.c_uint64(0)
+    _check(load().klnmf_nearest_work_bytes(int(count), int(total_rows), _c.byref(out)))
+    return out.value
+
+
+def nearest_many_device(jobs, mask, d_idx, d_dist, d_work, work_bytes, f64=True, device=0):
+    """For every job (dA, lda, dB, ldb, na, nb, d) of DEVICE matrices and every row of its A: the index of the nearest row of B
+    under each measure of `mask`, int32 [sum na][M] at d_idx (and the distances at d_dist, or None) -- one launch:
+    klnmf_nearest_many_device."""
+    jobs = list(jobs)
+    table = (NearestJob * max(1, len(jobs)))()
+    for q, (dA, lda, dB, ldb, na, nb, d) in enumerate(jobs):
+        table[q] = NearestJob(dA or None, int(lda), dB or None, int(ldb), int(na), int(nb), int(d))
+    _check(load().klnmf_nearest_many_device(device, DT_F64 if f64 else DT_F32, int(mask), _c.cast(table, _c.c_void_p), len(jobs),
+                                            _c.c_void_p(d_idx), _c.c_void_p(d_dist), _c.c_void_p(d_work), int(work_bytes)))
+
+
+def nearest(A, B, mask, device=0, return_distances=False):
+    """[len(A), M] int32 indices of the nearest row of B for every row of A under each measure of `mask` (ascending) -- and the
+    distances with return_distances -- from host arrays: klnmf_nearest."""
+    A = np.asarray(A)
+    B = np.asarray(B)
+    if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1]:
+        raise ValueError('shapes %s and %s do not hold vectors of one length' % (A.shape, B.shape))
+    dt = np.float32 if (A.dtype == np.float32 and B.dtype == np.float32) else np.float64
+    A = np.ascontiguousarray(A, dtype=dt)
+    B = np.ascontiguousarray(B, dtype=dt)
+    M = len(mask_metrics(mask)) if 0 < int(mask) <= DIST_MASK_ALL else 1
+    idx = np.empty((A.shape[0], M), dtype=np.int32)
+    dist = np.empty((A.shape[0], M), dtype=dt) if return_distances else None
+    _check(load().klnmf_nearest(device, DT_F32 if dt == np.float32 else DT_F64, int(mask), A.shape[0], B.shape[0], A.shape[1],
+                                A.ctypes.data_as(_c.c_void_p), B.ctypes.data_as(_c.c_void_p), idx.ctypes.data_as(_c.c_void_p),
+                                dist.ctypes.data_as(_c.c_void_p) if return_distances else None))
+    return (idx, dist) if return_distances else idx
 
 
 def csr_rows_to_dense_device(d_indptr, d_indices, d_data, f64, src_rows, d_row_idx, rows, d, d_out, ld, device=0):

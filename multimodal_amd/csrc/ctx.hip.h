@@ -5,7 +5,8 @@
 //                    built from rowpass4_list.hip.h), stop rule, fp8 regime and its monitor; the loop driver every loop of
 //                    every unit runs on (loop_open, local_iteration, loop_advance, stop_fired)
 //   api_comm.hip     row shards over the GPUs of a node: the RCCL communicator, the agreed loop entry, the exchange (nmf.py:349)
-//   api_eval.hip     evaluation and introspection: reconstruction products (learner.py:80-84), distances, queries, profiling
+//   api_eval.hip     evaluation and introspection: reconstruction products (learner.py:80-84), distances, the fused nearest-example
+//                    search of include/klnmf_nearest.h (nearest.hip.h, included by this unit alone), queries, profiling
 //   api_group.hip    a group of contexts (row shards, one device each, a device may repeat) driven from one host thread: the
 //                    exchange of group.hip.h between their streams, the loop of klnmf_group_run
 //   api_batch.hip    a batch of dense problems of one shape in KLNMF_PREC_F64 / F32, unweighted or all under presence masks

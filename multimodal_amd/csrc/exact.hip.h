@@ -343,6 +343,34 @@ __global__ __launch_bounds__(256) void k_gkl(const T *x, const T *y, int64_t cou
 // evaluation.py:103-116 `all_distances`, which broadcasts [n_a,1,d] x [1,n_b,d]).  One wave per pair.
 enum DistMetric { DIST_KL = 0, DIST_REV_KL = 1, DIST_SYM_KL = 2, DIST_FROBENIUS = 3, DIST_COSINE_DIFF = 4 };
 
+// The terms of one element and the closing expression of a pair: the one text k_all_distances and k_nearest (nearest.hip.h) are
+// both compiled from, so that the two agree bit for bit.  Where the compiler's contraction decides by the code AROUND a
+// statement, the rounding is written out (fma / dist_mul_rounded): k_all_distances adds the term of every measure to s0 in one
+// shared instruction, so its Frobenius and x.y products are rounded before that add, while its x.x and y.y sums are fused --
+// those are the roundings it has always had.  A KL term has one product and its own subtraction behind it: fused in any context.
+__device__ __forceinline__ double dist_mul_rounded(double x, double y) {
+#pragma clang fp contract(off)
+    return x * y;
+}
+__device__ __forceinline__ void dist_term_kl(double x, double y, double eps, double &s0, double &s1) {
+    const double l = log((x + eps) / (y + eps));
+    s0 += x * l - x + y;                    // generalized_KL(a, b)
+    s1 += -y * l - y + x;                   // generalized_KL(b, a): log((y+eps)/(x+eps)) = -l
+}
+__device__ __forceinline__ void dist_term_frobenius(double x, double y, double &s0) { s0 += dist_mul_rounded(x - y, x - y); }
+__device__ __forceinline__ void dist_term_cosine(double x, double y, double &s0, double &s1, double &s2) {
+    s0 += dist_mul_rounded(x, y); s1 = fma(x, x, s1); s2 = fma(y, y, s2);
+}
+__device__ __forceinline__ double dist_close(int metric, double s0, double s1, double s2) {
+    switch (metric) {
+        case DIST_KL: return s0;
+        case DIST_REV_KL: return s1;
+        case DIST_SYM_KL: return 0.5 * (s0 + s1);
+        case DIST_FROBENIUS: return sqrt(s0);
+        default: return -(s0 / (sqrt(s1 * s2) + (s0 == 0.0 ? 1.0 : 0.0)));     // metrics.py:71-77
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_all_distances(const T *A, const T *B, T *out, int64_t na, int64_t nb,
                                                         int64_t d, int metric, double eps, int64_t lda = -1, int64_t ldb = -1) {
@@ -356,27 +384,13 @@ __global__ __launch_bounds__(256) void k_all_distances(const T *A, const T *B, T
     double s0 = 0, s1 = 0, s2 = 0;
     for (int64_t e = lane; e < d; e += 64) {
         const double x = (double)a[e], y = (double)b[e];
-        if (metric <= DIST_SYM_KL) {
-            const double l = log((x + eps) / (y + eps));
-            s0 += x * l - x + y;                    // generalized_KL(a, b)
-            s1 += -y * l - y + x;                   // generalized_KL(b, a): log((y+eps)/(x+eps)) = -l
-        } else if (metric == DIST_FROBENIUS) {
-            s0 += (x - y) * (x - y);
-        } else {
-            s0 += x * y; s1 += x * x; s2 += y * y;
-        }
+        if (metric <= DIST_SYM_KL) dist_term_kl(x, y, eps, s0, s1);
+        else if (metric == DIST_FROBENIUS) dist_term_frobenius(x, y, s0);
+        else dist_term_cosine(x, y, s0, s1, s2);
     }
     s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
     if (lane != 0) return;
-    double r;
-    switch (metric) {
-        case DIST_KL: r = s0; break;
-        case DIST_REV_KL: r = s1; break;
-        case DIST_SYM_KL: r = 0.5 * (s0 + s1); break;
-        case DIST_FROBENIUS: r = sqrt(s0); break;
-        default: r = -(s0 / (sqrt(s1 * s2) + (s0 == 0.0 ? 1.0 : 0.0))); break;     // metrics.py:71-77
-    }
-    out[pair] = (T)r;
+    out[pair] = (T)dist_close(metric, s0, s1, s2);
 }
 
 }  // namespace klnmf

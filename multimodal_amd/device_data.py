@@ -511,7 +511,8 @@ class DeviceEvaluation(object):
       * the test / example rows are gathered from the device-resident modalities by the upload kernel;
       * the coefficients stay on the device (klnmf_get_W_device), the reconstructions are products of device matrices
         (klnmf_matmul_device; learner.py:80-84), and the nearest-example search reads both sides from device memory
-        (klnmf_all_distances_device) -- only the [n_test, n_examples] distance matrix comes back.
+        (klnmf_all_distances_device) -- only the [n_test, n_examples] distance matrix comes back (`found_labels`), or, for
+        many searches and all their measures in one launch, only the indices (`found_labels_many`, klnmf_nearest_many_device).
 
     All intermediates are float64 (as the host path's); the loop itself runs in the learner's NMF precision."""
 
@@ -681,3 +682,29 @@ class DeviceEvaluation(object):
                                      device=self.dev.index or 0)
         nearest = np.argmin(out.cpu().numpy(), axis=1)
         return [labels_ex[j] for j in nearest]
+
+    def found_labels_many(self, searches, metrics):
+        """[{metric: found_labels(test, examples, labels_ex, metric)} for (test, examples, labels_ex) in searches] -- float64
+        device matrices of any shapes on this evaluation's device, of this run or of several -- by ONE launch
+        (klnmf_nearest_many_device) and one copy of the int32 indices: the distance matrices are never formed."""
+        torch = self.torch
+        searches, metrics = list(searches), [int(m) for m in metrics]
+        mask = _native.metric_mask(metrics)
+        slot = {m: s for s, m in enumerate(_native.mask_metrics(mask))}
+        for test, examples, _labels in searches:
+            if test.dtype != torch.float64 or examples.dtype != torch.float64 or test.shape[1] != examples.shape[1]:
+                raise ValueError("found_labels_many: float64 matrices of one row length, got %s %s and %s %s"
+                                 % (test.dtype, tuple(test.shape), examples.dtype, tuple(examples.shape)))
+        jobs = [(t.data_ptr(), t.stride(0), e.data_ptr(), e.stride(0), t.shape[0], e.shape[0], t.shape[1]) for t, e, _l in searches]
+        rows = sum(j[4] for j in jobs)
+        nbytes = _native.nearest_work_bytes(len(jobs), rows)
+        idx = torch.empty((rows, len(slot)), dtype=torch.int32, device=self.dev)
+        work = torch.empty((max(1, nbytes),), dtype=torch.uint8, device=self.dev)
+        _native.nearest_many_device(jobs, mask, idx.data_ptr(), None, work.data_ptr(), nbytes, f64=True, device=self.dev.index or 0)
+        nearest = idx.cpu().numpy()
+        out, row0 = [], 0
+        for (test, _examples, labels_ex) in searches:
+            mine = nearest[row0:row0 + test.shape[0]]
+            out.append({m: [labels_ex[j] for j in mine[:, slot[m]]] for m in metrics})
+            row0 += test.shape[0]
+        return out

@@ -116,12 +116,40 @@ def internal_sets(kind, n_modalities):
     return sets
 
 
-def evaluate_on_device(dataset, learner, rows_test, rows_ex, labels_test, labels_ex, iter_test, ev=None, internals=None):
-    """`evaluate` (TwoModalitiesExperiment._evaluate) without host round trips.  ev / internals: the run's `DeviceEvaluation`
-    and its internal coefficients {(set, 'test' | 'ex'): device tensor} where a batch computed them (`_sweep_batch`)."""
-    from .device_data import DeviceEvaluation
-    if ev is None:
-        ev = DeviceEvaluation(dataset, learner, iter_test)
+SEARCHES = ('matrix', 'fused')
+
+
+def _check_search(search):
+    if search not in SEARCHES:
+        raise ValueError("search=%r: expected one of %s" % (search, ', '.join(repr(s) for s in SEARCHES)))
+
+
+def _resolve_searches(ev, listed, search):
+    """[{suffix: found labels}] of the listed searches [(key of suffix, test, examples, labels_test, labels_ex)] -- of one run's
+    evaluation, or of several runs' on ev's device.  'matrix': `found_labels` per search and measure, in order; 'fused': ONE
+    `found_labels_many` call."""
+    if search == 'matrix':
+        return [{suffix: ev.found_labels(test, examples, labels_ex, metric) for metric, suffix in DEVICE_MEASURES}
+                for _key, test, examples, _labels_test, labels_ex in listed]
+    many = ev.found_labels_many([(test, examples, labels_ex) for _key, test, examples, _labels_test, labels_ex in listed],
+                                [metric for metric, _suffix in DEVICE_MEASURES])
+    return [{suffix: found[metric] for metric, suffix in DEVICE_MEASURES} for found in many]
+
+
+def _results_of(listed, found):
+    """{found_<key>: labels, score_<key>: score} of the listed searches, in their order (measures inner, as the reference)."""
+    results = {}
+    for (key_of, _test, _examples, labels_test, _labels_ex), by_suffix in zip(listed, found):
+        for _metric, suffix in DEVICE_MEASURES:
+            key = key_of(suffix)
+            results['found_' + key] = by_suffix[suffix]
+            results['score_' + key] = found_labels_to_score(labels_test, by_suffix[suffix])
+    return results
+
+
+def list_searches_on_device(dataset, learner, rows_test, rows_ex, labels_test, labels_ex, iter_test, ev=None, internals=None):
+    """The nearest-example searches of `evaluate_on_device`, in its order: [(key of suffix, test, examples, labels_test,
+    labels_ex)] with the matrices on the device."""
     M = len(learner.mod)
 
     def transformations(rows, side):
@@ -138,21 +166,14 @@ def evaluate_on_device(dataset, learner, rows_test, rows_ex, labels_test, labels
             out[i].append(coefficients[i])
         return out
     t_test, t_ex = transformations(rows_test, 'test'), transformations(rows_ex, 'ex')
-    results = {}
-    for mod1, mod2, mod_cmp in product(range(M), range(M), [INTERNAL] + list(range(M))):
-        for metric, suffix in DEVICE_MEASURES:
-            found = ev.found_labels(t_test[mod1][mod_cmp], t_ex[mod2][mod_cmp], labels_ex, metric)
-            key = exp_key(learner.mod, mod1, mod2, mod_cmp, suffix)
-            results['found_' + key] = found
-            results['score_' + key] = found_labels_to_score(labels_test, found)
-    return results
+    return [(lambda suffix, c=(mod1, mod2, mod_cmp): exp_key(learner.mod, c[0], c[1], c[2], suffix),
+             t_test[mod1][mod_cmp], t_ex[mod2][mod_cmp], labels_test, labels_ex)
+            for mod1, mod2, mod_cmp in product(range(M), range(M), [INTERNAL] + list(range(M)))]
 
 
-def evaluate_internal_on_device(dataset, learner, rows_test, rows_ex, labels_test, labels_ex, iter_test, ev=None, internals=None):
-    """`evaluate_internal` (ThreeModalitiesExperiment._evaluate) without host round trips.  ev / internals: as `evaluate_on_device`."""
-    from .device_data import DeviceEvaluation
-    if ev is None:
-        ev = DeviceEvaluation(dataset, learner, iter_test)
+def list_internal_searches_on_device(dataset, learner, rows_test, rows_ex, labels_test, labels_ex, iter_test, ev=None,
+                                     internals=None):
+    """The nearest-example searches of `evaluate_internal_on_device`, in its order (as `list_searches_on_device`)."""
     combos = tested_combinations(len(learner.mod))
 
     def internals_of(rows, side):
@@ -162,18 +183,41 @@ def evaluate_internal_on_device(dataset, learner, rows_test, rows_ex, labels_tes
                 got[mods] = internals[(mods, side)] if internals is not None else ev.internal([learner.mod[m] for m in mods], rows)
         return got
     t_test, t_ex = internals_of(rows_test, 'test'), internals_of(rows_ex, 'ex')
-    results = {}
-    for mods1, mods2 in combos:
-        for metric, suffix in DEVICE_MEASURES:
-            found = ev.found_labels(t_test[mods1], t_ex[mods2], labels_ex, metric)
-            key = combo_key(learner.mod, mods1, mods2, suffix)
-            results['found_' + key] = found
-            results['score_' + key] = found_labels_to_score(labels_test, found)
-    return results
+    return [(lambda suffix, c=(mods1, mods2): combo_key(learner.mod, c[0], c[1], suffix), t_test[mods1], t_ex[mods2], labels_test,
+             labels_ex) for mods1, mods2 in combos]
+
+
+def _evaluate_listed(lister, dataset, learner, rows_test, rows_ex, labels_test, labels_ex, iter_test, ev, internals, search):
+    from .device_data import DeviceEvaluation
+    _check_search(search)
+    if ev is None:
+        ev = DeviceEvaluation(dataset, learner, iter_test)
+    listed = lister(dataset, learner, rows_test, rows_ex, labels_test, labels_ex, iter_test, ev=ev, internals=internals)
+    return _results_of(listed, _resolve_searches(ev, listed, search))
+
+
+def evaluate_on_device(dataset, learner, rows_test, rows_ex, labels_test, labels_ex, iter_test, ev=None, internals=None,
+                       search='matrix'):
+    """`evaluate` (TwoModalitiesExperiment._evaluate) without host round trips.  ev / internals: the run's `DeviceEvaluation`
+    and its internal coefficients {(set, 'test' | 'ex'): device tensor} where a batch computed them (`_sweep_batch`).
+    search: 'matrix' (default) -- one distance matrix per comparison and measure comes back and np.argmin runs on the host
+    (`DeviceEvaluation.found_labels`); 'fused' -- the evaluation lists its searches and one launch returns their indices
+    (`DeviceEvaluation.found_labels_many`): the same keys, labels and scores."""
+    return _evaluate_listed(list_searches_on_device, dataset, learner, rows_test, rows_ex, labels_test, labels_ex, iter_test, ev,
+                            internals, search)
+
+
+def evaluate_internal_on_device(dataset, learner, rows_test, rows_ex, labels_test, labels_ex, iter_test, ev=None, internals=None,
+                                search='matrix'):
+    """`evaluate_internal` (ThreeModalitiesExperiment._evaluate) without host round trips.  ev / internals / search: as
+    `evaluate_on_device`."""
+    return _evaluate_listed(list_internal_searches_on_device, dataset, learner, rows_test, rows_ex, labels_test, labels_ex,
+                            iter_test, ev, internals, search)
 
 
 def perform_one_run(dataset, modalities, coefs, k, iter_train, iter_test, rows_train, rows_test, rows_ex,
-                    labels_test, labels_ex, init_dictionary=None, kind=None, on_device=True, keep_sparse=None, presence=None):
+                    labels_test, labels_ex, init_dictionary=None, kind=None, on_device=True, keep_sparse=None, presence=None,
+                    search='matrix'):
     """experiment.py:158-172 on a DeviceDataset: returns (learner, results) with results['dictionary'] as stored there.
     dataset: a `DeviceDataset`, or the modalities' matrices -- uploaded here as DeviceDataset(dataset, keep_sparse=keep_sparse):
     with keep_sparse scipy-sparse modalities stay CSR on the device and the run takes the reference's sparse branch.
@@ -184,8 +228,11 @@ def perform_one_run(dataset, modalities, coefs, k, iter_train, iter_test, rows_t
     None or the weights of that modality in every sample, 0 where it is absent); the training and every transform of the
     evaluation that selects a masked modality then run the masked loop on the rows' own part of the mask.  A row from which
     every selected modality is absent keeps its W0; which rows are scored stays the caller's choice.  With a `DeviceDataset`,
-    `presence` must be the mask it was built with (ValueError otherwise)."""
+    `presence` must be the mask it was built with (ValueError otherwise).
+    search: how the device evaluation finds the nearest examples, 'matrix' (default) or 'fused' (`evaluate_on_device`); the
+    host-array evaluations (on_device=False) use no device search and ignore it.  Another name: ValueError."""
     from .device_data import DeviceDataset
+    _check_search(search)
     if not isinstance(dataset, DeviceDataset):
         dataset = DeviceDataset(dataset, keep_sparse=bool(keep_sparse), presence=presence)
     elif keep_sparse is not None and bool(keep_sparse) != dataset.keep_sparse_asked:
@@ -201,7 +248,8 @@ def perform_one_run(dataset, modalities, coefs, k, iter_train, iter_test, rows_t
         ev = evaluate_on_device if kind == 'two' else evaluate_internal_on_device
     else:              # the host-array path of round 2 (every transform returns numpy arrays)
         ev = evaluate if kind == 'two' else evaluate_internal
-    results.update(ev(dataset, learner, rows_test, rows_ex, labels_test, labels_ex, iter_test))
+    extra = {'search': search} if on_device else {}
+    results.update(ev(dataset, learner, rows_test, rows_ex, labels_test, labels_ex, iter_test, **extra))
     return learner, results
 
 
@@ -220,20 +268,24 @@ def _sweep_split(dataset, examples, k, run, test_ratio, seed):
     return train, test, H0
 
 
-def _one_sweep_job(dataset, modalities, coefs, labels, examples, k, run, iter_train, iter_test, test_ratio, seed, kind):
+def _one_sweep_job(dataset, modalities, coefs, labels, examples, k, run, iter_train, iter_test, test_ratio, seed, kind,
+                   search='matrix'):
     """One job of the reference's sweep (samples/launcher.py:71-99: an experiment with run_mode 'single' = one random
     test_ratio split, experiment.py:131-133): seeded per (k, run), so that it does not matter which rank executes it."""
     train, test, H0 = _sweep_split(dataset, examples, k, run, test_ratio, seed)
     _, res = perform_one_run(dataset, modalities, coefs, k, iter_train, iter_test, train, test, list(examples),
-                             [labels[t] for t in test], [labels[e] for e in examples], init_dictionary=H0, kind=kind)
+                             [labels[t] for t in test], [labels[e] for e in examples], init_dictionary=H0, kind=kind, search=search)
     return {kk: float(v) for kk, v in res.items() if kk.startswith('score_')}
 
 
-def _sweep_batch(dataset, modalities, coefs, labels, examples, k, runs, iter_train, iter_test, test_ratio, seed, kind):
+def _sweep_batch(dataset, modalities, coefs, labels, examples, k, runs, iter_train, iter_test, test_ratio, seed, kind,
+                 search='matrix'):
     """The jobs (k, run) for run in `runs` as one batch: the trainings by `DeviceDataset.train_many`, every internal transform of
-    their evaluations by `DeviceEvaluation.internal_many`; reconstructions, distances and scores per run.  Seeds per (k, run), as
-    `_one_sweep_job`'s: which batch a run lands in does not matter."""
+    their evaluations by `DeviceEvaluation.internal_many`; reconstructions and scores per run; the nearest-example searches per
+    run, comparison and measure (search='matrix') or those of ALL runs of the batch in one launch (search='fused').  Seeds per
+    (k, run), as `_one_sweep_job`'s: which batch a run lands in does not matter."""
     from .device_data import DeviceEvaluation
+    _check_search(search)
     splits = [_sweep_split(dataset, examples, k, run, test_ratio, seed) for run in runs]
     learners = [MultimodalLearner(list(modalities), list(dataset.dims), list(coefs), k) for _ in runs]
     dataset.train_many(learners, [sp[0] for sp in splits], iter_train, init_dictionaries=[sp[2] for sp in splits])
@@ -246,6 +298,17 @@ def _sweep_batch(dataset, modalities, coefs, labels, examples, k, runs, iter_tra
         for side, rows_list in (('test', [sp[1] for sp in splits]), ('ex', [list(examples)] * len(runs))):
             for got, t in zip(internals, DeviceEvaluation.internal_many(evs, names, rows_list)):
                 got[(mods, side)] = t
+    if search == 'fused':      # every run lists its searches; one call resolves them all
+        lister = list_searches_on_device if kind == 'two' else list_internal_searches_on_device
+        listed = [lister(dataset, learner, test, list(examples), [labels[t] for t in test], [labels[e] for e in examples], iter_test,
+                         ev=ev, internals=got) for learner, ev, got, (_train, test, _H0) in zip(learners, evs, internals, splits)]
+        found = _resolve_searches(evs[0], [s for mine in listed for s in mine], search)
+        out, at = [], 0
+        for run, mine in zip(runs, listed):
+            res = _results_of(mine, found[at:at + len(mine)])
+            at += len(mine)
+            out.append((k, run, {kk: float(v) for kk, v in res.items() if kk.startswith('score_')}))
+        return out
     evaluate_ = evaluate_on_device if kind == 'two' else evaluate_internal_on_device
     out = []
     for run, learner, ev, got, (_train, test, _H0) in zip(runs, learners, evs, internals, splits):
@@ -270,7 +333,7 @@ def sweep_batches(pairs, batch):
 def _sweep_worker(job):
     """One process per GPU: uploads the modalities once, runs its share of the (k, run) grid, returns the scores."""
     (device, rank, world, data, modalities, coefs, labels, examples, ks, n_runs, iter_train, iter_test, test_ratio, seed, kind,
-     precision, keep_sparse, presence, batch) = job
+     precision, keep_sparse, presence, batch, search) = job
     import os
     import torch
     saved = {name: os.environ.get(name) for name in ('KLNMF_PRECISION', 'KLNMF_DEVICE', 'KLNMF_DEVICES')}
@@ -287,10 +350,10 @@ def _sweep_worker(job):
             if len(group) == 1:      # (batch = 1: today's path, call for call)
                 k, run = group[0]
                 out.append((k, run, _one_sweep_job(ds, modalities, coefs, labels, examples, k, run, iter_train, iter_test,
-                                                   test_ratio, seed, kind)))
+                                                   test_ratio, seed, kind, search=search)))
             else:
                 out.extend(_sweep_batch(ds, modalities, coefs, labels, examples, group[0][0], [run for _, run in group], iter_train,
-                                        iter_test, test_ratio, seed, kind))
+                                        iter_test, test_ratio, seed, kind, search=search))
         return out
     finally:   # a one-device sweep runs in the caller's process: leave its environment as it was
         for name, value in saved.items():
@@ -301,7 +364,8 @@ def _sweep_worker(job):
 
 
 def run_sweep(data_matrices, labels, modalities, ks, n_runs, iter_train=50, iter_test=50, coefs=None, examples=None,
-              test_ratio=.1, seed=0, devices=None, precision=None, kind=None, keep_sparse=False, presence=None, batch=1):
+              test_ratio=.1, seed=0, devices=None, precision=None, kind=None, keep_sparse=False, presence=None, batch=1,
+              search='matrix'):
     """The k sweep of the reference's launcher (samples/launcher.py:68-99, 122-126: Ks x N_RUN independent experiments,
     one OS process each) on the GPUs of this node: ONE process per device, each with the modalities resident on its GPU,
     executing `sweep_assignment`'s share of the (k, run) grid -- replica parallelism, no communication.  Returns
@@ -320,8 +384,12 @@ def run_sweep(data_matrices, labels, modalities, ks, n_runs, iter_train=50, iter
     evaluations' internal transforms of a batch as one launch sequence (klnmf_batch_*) where the shapes allow it (dense
     modalities, f64 / f32; with `presence`: the masked batch, every run its own rows of the mask; with `keep_sparse`: the CSR
     batch, every run its own stored entries, k <= 512); 1 (default): one pair after
-    another, as before."""
+    another, as before.
+    search: 'matrix' (default) -- every nearest-example search of an evaluation brings its distance matrix to the host, as
+    before; 'fused' -- the searches of a run (batch = 1) or of all runs of a batch are one launch that returns the indices
+    (klnmf_nearest_many_device): the same labels and scores.  Another name: ValueError."""
     import torch
+    _check_search(search)
     if keep_sparse:
         data = [m.tocsr() if hasattr(m, 'tocsr') else np.asarray(m) for m in data_matrices]
     else:
@@ -339,7 +407,8 @@ def run_sweep(data_matrices, labels, modalities, ks, n_runs, iter_train=50, iter
         devices = list(range(max(1, torch.cuda.device_count())))
     world = len(devices)
     jobs = [(dev, r, world, data, list(modalities), list(coefs), labels, list(examples), list(ks), int(n_runs), iter_train,
-             iter_test, test_ratio, seed, kind, precision, bool(keep_sparse), presence, int(batch)) for r, dev in enumerate(devices)]
+             iter_test, test_ratio, seed, kind, precision, bool(keep_sparse), presence, int(batch), search)
+            for r, dev in enumerate(devices)]
     if world == 1:
         parts = [_sweep_worker(jobs[0])]
     else:

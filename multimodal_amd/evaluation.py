@@ -59,6 +59,37 @@ def classify_NN(reco_data, ex_data, ex_labels, measure):
     return dists_to_found_labels(all_distances(reco_data, ex_data, measure), ex_labels)
 
 
+_DIST_OF = {'kl_div': 0, 'rev_kl_div': 1, 'sym_kl_div': 2, 'frobenius': 3, 'cosine_diff': 4}      # _native.DIST_*
+
+
+def _measure_code(measure):
+    """_native.DIST_* of a measure given as `all_distances` takes it (a function of a known name) or as that name."""
+    name = measure if isinstance(measure, str) else getattr(measure, '__name__', None)
+    if name not in _DIST_OF:
+        raise ValueError("measure %r has no GPU implementation (known: %s)" % (name, ', '.join(sorted(_DIST_OF))))
+    return _DIST_OF[name]
+
+
+def nearest_examples(reco_data, ex_data, measures):
+    """{measure: index of the nearest example of every row} for all `measures` in ONE search on the GPU (klnmf_nearest): what
+    np.argmin(all_distances(reco_data, ex_data, measure), axis=1) gives per measure (reference evaluation.py:74-77, 103-106),
+    without the distance matrices."""
+    from . import _native
+    measures = list(measures)
+    codes = [_measure_code(m) for m in measures]
+    if not codes:
+        return {}
+    mask = _native.metric_mask(codes)
+    idx = _native.nearest(np.asarray(todense(reco_data)), np.asarray(todense(ex_data)), mask)
+    slot = {c: s for s, c in enumerate(_native.mask_metrics(mask))}
+    return {m: idx[:, slot[c]].astype(np.intp) for m, c in zip(measures, codes)}
+
+
+def classify_NN_measures(reco_data, ex_data, ex_labels, measures):
+    """{measure: nearest example's label for every reconstructed sample}: `classify_NN` for several measures at once."""
+    return {m: [ex_labels[j] for j in nearest] for m, nearest in nearest_examples(reco_data, ex_data, measures).items()}
+
+
 def scores_from_dists(dists, true_labels_0, true_labels_1=None, verbose=False):
     """Deprecated in the reference too (evaluation.py:61-71)."""
     if true_labels_1 is None:
