@@ -209,6 +209,16 @@ NEAREST_SIGNATURES = {
     'klnmf_nearest': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _i64, _i64, _i64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/klnmf_information.h (the atom x label information matrix), which the
+# same library exports
+INFORMATION_SIGNATURES = {
+    'klnmf_information_work_bytes': (_c.c_int, [_i64, _i64, _c.c_int, _c.c_int, _c.POINTER(_c.c_uint64)]),
+    'klnmf_information_many_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _i64, _c.c_void_p, _c.c_void_p,
+                                                 _c.c_void_p, _c.c_uint64]),
+    'klnmf_information': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _i64, _i64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                     _c.c_void_p]),
+}
+
 _lib = None
 
 
@@ -234,7 +244,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(BATCH_MASK_SIGNATURES.items()) \
             + list(BATCH_CSR_SIGNATURES.items()) + list(BETA_SIGNATURES.items()) + list(BATCH_BETA_SIGNATURES.items()) \
-            + list(NEAREST_SIGNATURES.items()):
+            + list(NEAREST_SIGNATURES.items()) + list(INFORMATION_SIGNATURES.items()):
         fn = getattr(lib, name)     # AttributeError if a symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -393,6 +403,65 @@ def nearest(A, B, mask, device=0, return_distances=False):
                                 A.ctypes.data_as(_c.c_void_p), B.ctypes.data_as(_c.c_void_p), idx.ctypes.data_as(_c.c_void_p),
                                 dist.ctypes.data_as(_c.c_void_p) if return_distances else None))
     return (idx, dist) if return_distances else idx
+
+
+INFORMATION_LDS_BYTES = 32768      # KLNMF_INFORMATION_LDS_BYTES
+INFORMATION_ROWS = 1024            # rows of a workgroup's chunk (csrc/information.hip.h, kInfoRows)
+
+
+class InformationJob(_c.Structure):
+    """klnmf_information_job: A [n, k] (device pointer, rows lda elements apart) and its int32 labels [n]."""
+    _fields_ = [('A', _c.c_void_p), ('lda', _i64), ('labels', _c.c_void_p), ('n', _i64), ('k', _i64)]
+
+
+def information_route(n_labels, bins):
+    """(route, atom tile) of the histogram launch for (n_labels, bins) -- include/klnmf_information.h's rule: 'lds' with the full
+    tile of 64 atoms, 'lds-shrunk' with fewer, 'global' (tile 0) where not one atom's counters fit the LDS budget."""
+    tile = min(64, INFORMATION_LDS_BYTES // (4 * int(n_labels) * int(bins)))
+    return ('lds' if tile == 64 else 'lds-shrunk' if tile > 0 else 'global'), tile
+
+
+def information_work_bytes(count, total_atoms, n_labels, bins):
+    """Bytes of device workspace `information_many_device` needs for `count` jobs of `total_atoms` atoms in all:
+    klnmf_information_work_bytes."""
+    out = _c.c_uint64(0)
+    _check(load().klnmf_information_work_bytes(int(count), int(total_atoms), int(n_labels), int(bins), _c.byref(out)))
+    return out.value
+
+
+def information_many_device(jobs, n_labels, bins, d_info, d_counts, d_work, work_bytes, f64=True, device=0):
+    """For every job (dA, lda, d_labels, n, k) of DEVICE arrays: the (n_labels, k) information matrix, float64, at d_info behind the
+    jobs before it (and the int32 counts [k][n_labels][bins] at d_counts, or None) -- a fixed number of launches for all jobs:
+    klnmf_information_many_device."""
+    jobs = list(jobs)
+    table = (InformationJob * max(1, len(jobs)))()
+    for q, (dA, lda, d_labels, n, k) in enumerate(jobs):
+        table[q] = InformationJob(dA or None, int(lda), d_labels or None, int(n), int(k))
+    _check(load().klnmf_information_many_device(device, DT_F64 if f64 else DT_F32, int(n_labels), int(bins),
+                                                _c.cast(table, _c.c_void_p), len(jobs), _c.c_void_p(d_info), _c.c_void_p(d_counts),
+                                                _c.c_void_p(d_work), int(work_bytes)))
+
+
+def information(A, labels, n_labels, bins=10, device=0, return_counts=False):
+    """The (n_labels, k) float64 information matrix of the host matrix A [n, k] (float32 stays float32, anything else runs as
+    float64) and its int32 labels -- and the counts [k, n_labels, bins] with return_counts: klnmf_information."""
+    A = np.asarray(A)
+    if A.ndim != 2:
+        raise ValueError('a matrix [n, k] of coefficients, got shape %s' % (A.shape,))
+    dt = np.float32 if A.dtype == np.float32 else np.float64
+    A = np.ascontiguousarray(A, dtype=dt)
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    if labels.shape != (A.shape[0],):
+        raise ValueError('one label per row: %s labels for %d rows' % (labels.shape, A.shape[0]))
+    n, k = A.shape
+    shape_ok = n >= 1 and k >= 1 and 1 <= int(n_labels) <= 65536 and 1 <= int(bins) <= 256
+    info = np.empty((int(n_labels), k) if shape_ok else (1, 1), dtype=np.float64)
+    counts = np.empty((k, int(n_labels), int(bins)) if shape_ok else (1, 1, 1), dtype=np.int32) if return_counts else None
+    _check(load().klnmf_information(device, DT_F32 if dt == np.float32 else DT_F64, int(n_labels), int(bins), n, k,
+                                    A.ctypes.data_as(_c.c_void_p), labels.ctypes.data_as(_c.c_void_p),
+                                    info.ctypes.data_as(_c.c_void_p),
+                                    counts.ctypes.data_as(_c.c_void_p) if return_counts else None))
+    return (info, counts) if return_counts else info
 
 
 def csr_rows_to_dense_device(d_indptr, d_indices, d_data, f64, src_rows, d_row_idx, rows, d, d_out, ld, device=0):

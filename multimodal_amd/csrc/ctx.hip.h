@@ -15,6 +15,8 @@
 //                    (klnmf_batch_csr.h, batch_sparse.hip.h)
 //   api_beta.hip     the beta-divergence cost of a context's problem (include/klnmf_beta.h): its buffers and refusals, its loss and
 //                    single steps; the loop's pieces branch on it in api_loop.hip, on the policies of beta.hip.h
+//   api_info.hip     the atom x label information matrix of include/klnmf_information.h (samples/plot_info_matrix.py:66-90,
+//                    126-136): checks, workspace layout and the launches of information.hip.h, included by that unit alone
 // This header: error handling, the type dispatch of the host-facing kernels, the device block cache and the arena over it
 // (DeviceBlocks), the staged host upload, the development switches, the mask state (PresenceState) and the context itself -- its
 // state in four groups, one per lifetime (ContextState, ProblemState, LoopState, LoopRecord) -- and what contexts and batches share

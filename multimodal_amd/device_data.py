@@ -708,3 +708,41 @@ class DeviceEvaluation(object):
             out.append({m: [labels_ex[j] for j in mine[:, slot[m]]] for m in metrics})
             row0 += test.shape[0]
         return out
+
+    def information_matrix(self, mods, rows, labels, n_labels, bins=10):
+        """evaluation.information_matrix(self.internal(mods, rows), labels, n_labels, bins) with the coefficients left on the
+        device: the (n_labels, k) float64 matrix alone comes back (klnmf_information_many_device; the reference's
+        samples/plot_info_matrix.py:126-136 for one run)."""
+        return DeviceEvaluation.information_matrix_many([self], mods, [rows], [labels], n_labels, bins=bins)[0]
+
+    @staticmethod
+    def information_matrix_many(evaluations, mods, rows_list, labels_list, n_labels, bins=10):
+        """[ev.information_matrix(mods, rows, labels, n_labels, bins) for ...] for the evaluations of several runs on one device
+        (the loop over N_RUN of samples/plot_info_matrix.py:106-136): the internals by `internal_many`, then ONE
+        klnmf_information_many_device call for all runs and one copy of the matrices."""
+        from .evaluation import checked_labels
+        evaluations, rows_list = list(evaluations), [list(rows) for rows in rows_list]
+        if not evaluations:
+            return []
+        first = evaluations[0]
+        torch, dev = first.torch, first.dev
+        if not 1 <= int(bins) <= 256:
+            raise ValueError("bins must lie in [1, 256], got %r" % (bins,))
+        checked = [checked_labels(labels, len(rows), n_labels)[0] for labels, rows in zip(labels_list, rows_list)]
+        if len(checked) != len(evaluations) or len(rows_list) != len(evaluations):
+            raise ValueError("one list of rows and one of labels per evaluation")
+        internals = type(first).internal_many(evaluations, mods, rows_list)
+        d_labels = [torch.from_numpy(np.ascontiguousarray(l)).to(dev) for l in checked]
+        jobs = [(t.data_ptr(), t.stride(0), l.data_ptr(), t.shape[0], t.shape[1]) for t, l in zip(internals, d_labels)]
+        atoms = sum(j[4] for j in jobs)
+        nbytes = _native.information_work_bytes(len(jobs), atoms, n_labels, bins)
+        info = torch.empty((atoms * int(n_labels),), dtype=torch.float64, device=dev)
+        work = torch.empty((max(1, nbytes),), dtype=torch.uint8, device=dev)
+        _native.information_many_device(jobs, n_labels, bins, info.data_ptr(), None, work.data_ptr(), nbytes, f64=True,
+                                        device=dev.index or 0)
+        flat = info.cpu().numpy()
+        out, at = [], 0
+        for t in internals:
+            out.append(flat[at:at + int(n_labels) * t.shape[1]].reshape(int(n_labels), t.shape[1]).copy())
+            at += int(n_labels) * t.shape[1]
+        return out

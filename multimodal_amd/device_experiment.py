@@ -217,7 +217,7 @@ def evaluate_internal_on_device(dataset, learner, rows_test, rows_ex, labels_tes
 
 def perform_one_run(dataset, modalities, coefs, k, iter_train, iter_test, rows_train, rows_test, rows_ex,
                     labels_test, labels_ex, init_dictionary=None, kind=None, on_device=True, keep_sparse=None, presence=None,
-                    search='matrix'):
+                    search='matrix', information=False):
     """experiment.py:158-172 on a DeviceDataset: returns (learner, results) with results['dictionary'] as stored there.
     dataset: a `DeviceDataset`, or the modalities' matrices -- uploaded here as DeviceDataset(dataset, keep_sparse=keep_sparse):
     with keep_sparse scipy-sparse modalities stay CSR on the device and the run takes the reference's sparse branch.
@@ -230,7 +230,11 @@ def perform_one_run(dataset, modalities, coefs, k, iter_train, iter_test, rows_t
     every selected modality is absent keeps its W0; which rows are scored stays the caller's choice.  With a `DeviceDataset`,
     `presence` must be the mask it was built with (ValueError otherwise).
     search: how the device evaluation finds the nearest examples, 'matrix' (default) or 'fused' (`evaluate_on_device`); the
-    host-array evaluations (on_device=False) use no device search and ignore it.  Another name: ValueError."""
+    host-array evaluations (on_device=False) use no device search and ignore it.  Another name: ValueError.
+    information: with on_device, also results['information'] -- the (n_labels, k) information matrix between the internal
+    coefficients of the test rows (all modalities) and their labels (`DeviceEvaluation.information_matrix`; the reference's
+    samples/plot_info_matrix.py:126-136) -- and results['information_labels'], the sorted distinct labels of labels_test and
+    labels_ex that index its rows.  False (default): no further call and the keys of before."""
     from .device_data import DeviceDataset
     _check_search(search)
     if not isinstance(dataset, DeviceDataset):
@@ -250,6 +254,13 @@ def perform_one_run(dataset, modalities, coefs, k, iter_train, iter_test, rows_t
         ev = evaluate if kind == 'two' else evaluate_internal
     extra = {'search': search} if on_device else {}
     results.update(ev(dataset, learner, rows_test, rows_ex, labels_test, labels_ex, iter_test, **extra))
+    if information and on_device:
+        from .device_data import DeviceEvaluation
+        names = sorted(set(labels_test) | set(labels_ex))
+        index = {label: i for i, label in enumerate(names)}
+        results['information_labels'] = names
+        results['information'] = DeviceEvaluation(dataset, learner, iter_test).information_matrix(
+            list(learner.mod), rows_test, [index[label] for label in labels_test], len(names))
     return learner, results
 
 

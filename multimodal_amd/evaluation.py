@@ -90,6 +90,43 @@ def classify_NN_measures(reco_data, ex_data, ex_labels, measures):
     return {m: [ex_labels[j] for j in nearest] for m, nearest in nearest_examples(reco_data, ex_data, measures).items()}
 
 
+def checked_labels(labels, n_rows, n_labels=None):
+    """(int32 labels, n_labels) of `labels`, one integer in [0, n_labels) per row; n_labels defaults to max(labels) + 1.
+    ValueError otherwise."""
+    arr = np.asarray(labels)
+    if arr.shape != (n_rows,):
+        raise ValueError("one label per row: labels of shape %s for %d rows" % (arr.shape, n_rows))
+    if n_rows < 1:
+        raise ValueError("no sample: the information matrix of nothing is not defined")
+    if arr.dtype.kind not in 'iu':
+        if arr.dtype.kind != 'f' or not np.all(arr == np.floor(arr)):
+            raise ValueError("labels must be integers, got %s" % arr.dtype)
+    if n_labels is None:
+        n_labels = int(arr.max()) + 1
+    if int(n_labels) < 1 or arr.min() < 0 or arr.max() >= int(n_labels):
+        raise ValueError("labels outside [0, %d)" % int(n_labels))
+    return arr.astype(np.int32), int(n_labels)
+
+
+def information_matrix(internal, labels, n_labels=None, bins=10, return_counts=False):
+    """(n_labels, k) float64: the mutual information between each internal coefficient (a column of `internal` [n, k]), binned
+    into `bins` equal bins over its own [min, max], and the presence of each label -- np.array([mutual_information_by_label(
+    internal[:, i], by_label) for i in range(K)]).T of the reference's samples/plot_info_matrix.py:66-90, 126-136, on the GPU
+    (klnmf_information).  labels: one integer in [0, n_labels) per row; n_labels defaults to max(labels) + 1.  return_counts:
+    also the int32 histograms [k, n_labels, bins] (np.histogram's own counts).  ValueError for labels that are not integers in
+    range, for an empty input and for coefficients that are not finite (np.histogram's own refusal)."""
+    from . import _native
+    internal = np.asarray(todense(internal))
+    if internal.ndim != 2 or internal.shape[0] < 1 or internal.shape[1] < 1:
+        raise ValueError("a non-empty matrix [n, k] of coefficients, got shape %s" % (internal.shape,))
+    labels, n_labels = checked_labels(labels, internal.shape[0], n_labels)
+    if not 1 <= int(bins) <= 256:
+        raise ValueError("bins must lie in [1, 256], got %r" % (bins,))
+    if not np.all(np.isfinite(internal)):
+        raise ValueError("coefficients that are not finite: their range is not finite")
+    return _native.information(internal, labels, n_labels, bins=int(bins), return_counts=return_counts)
+
+
 def scores_from_dists(dists, true_labels_0, true_labels_1=None, verbose=False):
     """Deprecated in the reference too (evaluation.py:61-71)."""
     if true_labels_1 is None:

@@ -96,3 +96,47 @@ def cosine_diff(a, b, axis=-1):
 
 def cosine_similarity(a, b, axis=-1):
     return -cosine_diff(a, b, axis=axis)
+
+
+# ---- statistics of small arrays (reference metrics.py:23-55, 89-97) -----------------------------------
+# Plain numpy on the host: a joint table of a few cells, a coefficient matrix looked at once.  The GPU
+# form of the information analysis built on `mutual_information` is `evaluation.information_matrix`.
+
+def hoyer_sparseness(X, axis=-1, eps=EPSILON):
+    """Hoyer's sparseness along `axis`, from the mean ratio of the 1-norm to the 2-norm over the other
+    axes (reference metrics.py:23-30)."""
+    root = np.sqrt(X.shape[axis])
+    l1 = np.abs(X).sum(axis=axis) + eps
+    l2 = np.sqrt(np.square(X).sum(axis=axis)) + eps
+    return (root - np.average(l1 / l2)) / (root - 1)
+
+
+def entropy(vect):
+    """-sum(p log p), a zero entry contributing 0 (reference metrics.py:33-34)."""
+    safe = vect + (vect == 0)                      # log(1) = 0 where p = 0
+    return -np.sum(vect * np.log(safe))
+
+
+def mutual_information(histo):
+    """sum(p log(p / (p_row p_column))) of a joint table that sums to 1, an empty cell contributing 0
+    (reference metrics.py:37-43)."""
+    assert(histo.ndim == 2)
+    assert(np.allclose(histo.sum(), 1.))
+    empty = (histo == 0) * 1
+    independent = histo.sum(axis=0)[np.newaxis, :] * histo.sum(axis=1)[:, np.newaxis]
+    return (histo * np.log((histo + empty) / (independent + empty))).sum()
+
+
+def conditional_entropy(histo, axis=0):
+    """H(rest | variable on `axis`) = H(joint) - H(marginal of `axis`) (reference metrics.py:46-55)."""
+    assert(np.allclose(histo.sum(), 1.))
+    last = histo.swapaxes(axis, -1)
+    marginal = last.reshape((int(np.prod(last.shape[:-1])), last.shape[-1])).sum(axis=0)
+    return entropy(histo) - entropy(marginal)
+
+
+def real_sparsity(X):
+    """The share of zero coefficients of a dense or scipy-sparse matrix (reference metrics.py:89-97)."""
+    import scipy.sparse as sp
+    stored = len(X.nonzero()[0]) if sp.issparse(X) else (X != 0).sum()
+    return 1 - float(stored) / np.prod(X.shape)
