@@ -36,10 +36,11 @@ TILE = 64         # columns of f per row-pass tile
 
 
 def pow2_scale(amax):
-    """2^(TOP - e) with 2^(e-1) <= amax < 2^e (1 for amax = 0): amax * scale < 2^TOP, exact in fp32."""
+    """2^(TOP - e) with 2^(e-1) <= amax < 2^e (1 for amax = 0): amax * scale < 2^TOP, exact in fp32; the exponent clamped to
+    [-126, 126] as f3_scale clamps it (the scale and its inverse stay normal fp32 numbers)."""
     amax = np.asarray(amax, dtype=np.float64)
     e = np.where(amax > 0, np.floor(np.log2(np.where(amax > 0, amax, 1.0))) + 1, TOP)
-    return np.ldexp(1.0, (TOP - e).astype(np.int32)).astype(np.float32)
+    return np.ldexp(1.0, np.clip(TOP - e, -126, 126).astype(np.int32)).astype(np.float32)
 
 
 def split16(x):
@@ -84,7 +85,8 @@ def wtq(W, Q):
     Wp = (W * qr[:, None]).astype(np.float32)
     wj = pow2_scale(np.abs(Wp).max(axis=0))
     qsc = np.float32(2.0 ** (TOP - 1))
-    return (prod3(np.ascontiguousarray((Wp * wj[None, :]).T), Q / qr[:, None] * qsc) / (wj[:, None] * qsc)).astype(np.float32)
+    # (the inverse scales one after the other, as k_colpass_x3 applies them: wj qsc is beyond fp32's range for wj >= 2^114)
+    return (prod3(np.ascontiguousarray((Wp * wj[None, :]).T), Q / qr[:, None] * qsc) / qsc / wj[:, None]).astype(np.float32)
 
 
 def run(X, H0, iters, store='v32q32'):

@@ -1069,6 +1069,7 @@ int klnmf_set_Q(klnmf_ctx *c, const void *src, int dtype) {
         if (!src) fail(KLNMF_ERR_ARG, "null source");
         if (c->sparse) fail(KLNMF_ERR_UNSUPP, "klnmf_set_Q: the ratio of a CSR problem lives on X's structure");
         set_matrix(c, src, dtype, c->n, c->f, c->Q, nullptr, 0);
+        c->x3_ready = false;      // (the fused row pass's qr no longer bounds these ratios: the column pass takes the fp32 kernel)
     });
 }
 

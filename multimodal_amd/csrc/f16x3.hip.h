@@ -289,7 +289,8 @@ KL_GLOBAL __launch_bounds__(256, 2) void k_colpass_x3(int64_t n, int64_t f, int 
             const bool in = r < rend;
             const float q2 = in ? qr[r] : 1.f;
             ra[u] = (in && j0 + jj < k) ? W[r * k + j0 + jj] * q2 * wsc[jj] : 0.f;
-            rb[u] = (in && c0 + jj < f) ? Q[r * f + c0 + jj] * (qsc / q2) : 0.f;
+            // (Q / qr first, below 1; qsc / qr is beyond fp32's range at the smallest qr, 2^-126)
+            rb[u] = (in && c0 + jj < f) ? Q[r * f + c0 + jj] / q2 * qsc : 0.f;
         }
     };
     auto commit = [&]() {
@@ -327,12 +328,15 @@ KL_GLOBAL __launch_bounds__(256, 2) void k_colpass_x3(int64_t n, int64_t f, int 
         }
     }
     const int64_t slab = (int64_t)k * f;
+    const float qinv = ldexpf(1.f, 1 - F3_TOP);
+    // the two inverse scales one after the other: their product wsc qsc is beyond fp32's range for a component whose largest
+    // W_new qr is below 2^-98 (the slab would be 0), and the sum over wsc alone for one above 2^98
 #pragma unroll
     for (int g = 0; g < 16; ++g) {
         const int jj = 32 * wm + (g & 3) + 8 * (g >> 2) + 4 * (lane >> 5);
         const int64_t c = c0 + bc;
         if (j0 + jj < k && c < f)
-            Npart[blockIdx.z * slab + (int64_t)(j0 + jj) * f + c] = (hh[g] + xx[g]) / (wsc[jj] * qsc);
+            Npart[blockIdx.z * slab + (int64_t)(j0 + jj) * f + c] = (hh[g] + xx[g]) * qinv / wsc[jj];
     }
 }
 
