@@ -219,6 +219,18 @@ INFORMATION_SIGNATURES = {
                                      _c.c_void_p]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/klnmf_hac.h (the windowed co-occurrence histograms), which the same
+# library exports
+HAC_SIGNATURES = {
+    'klnmf_hac_work_bytes': (_c.c_int, [_c.c_int, _i64, _c.c_int, _i64, _c.POINTER(_c.c_uint64)]),
+    'klnmf_hac_count_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _i64, _c.c_void_p, _c.c_int, _c.c_void_p, _i64,
+                                          _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.POINTER(_i64)]),
+    'klnmf_hac_fill_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _i64, _c.c_void_p, _c.c_int, _c.c_void_p, _i64,
+                                         _c.c_void_p, _c.c_uint64, _i64, _c.c_void_p, _c.c_void_p]),
+    'klnmf_hac': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _i64, _c.c_void_p, _c.c_int, _c.c_void_p, _i64,
+                             _c.c_void_p, _i64, _c.c_void_p, _c.c_void_p, _c.POINTER(_i64)]),
+}
+
 _lib = None
 
 
@@ -244,7 +256,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(BATCH_MASK_SIGNATURES.items()) \
             + list(BATCH_CSR_SIGNATURES.items()) + list(BETA_SIGNATURES.items()) + list(BATCH_BETA_SIGNATURES.items()) \
-            + list(NEAREST_SIGNATURES.items()) + list(INFORMATION_SIGNATURES.items()):
+            + list(NEAREST_SIGNATURES.items()) + list(INFORMATION_SIGNATURES.items()) + list(HAC_SIGNATURES.items()):
         fn = getattr(lib, name)     # AttributeError if a symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -462,6 +474,99 @@ def information(A, labels, n_labels, bins=10, device=0, return_counts=False):
                                     info.ctypes.data_as(_c.c_void_p),
                                     counts.ctypes.data_as(_c.c_void_p) if return_counts else None))
     return (info, counts) if return_counts else info
+
+
+HAC_MAX_STREAMS, HAC_MAX_LAGS = 8, 8     # KLNMF_HAC_MAX_STREAMS, KLNMF_HAC_MAX_LAGS
+HAC_SORT_MAX = 4096                      # KLNMF_HAC_SORT_MAX: pair codes of a segment the sort route takes
+HAC_DENSE_MAX_K = 192                    # KLNMF_HAC_DENSE_MAX_K: codebook units of the dense route (K^2 int32 counters in LDS)
+
+
+class HacStream(_c.Structure):
+    """klnmf_hac_stream: frames [T, d] and a codebook [K, d], pointers, row strides in elements."""
+    _fields_ = [('frames', _c.c_void_p), ('ld', _i64), ('codebook', _c.c_void_p), ('ldc', _i64), ('d', _i64), ('K', _i64)]
+
+
+def hac_route(n_codes, K):
+    """The route of a segment of `n_codes` pair codes over a codebook of K units -- include/klnmf_hac.h's rule: 'none' (no code:
+    the window is no longer than the lag), 'sort' up to HAC_SORT_MAX codes, beyond that 'dense' up to HAC_DENSE_MAX_K units and
+    'refused' (KLNMF_ERR_UNSUPP) above."""
+    if int(n_codes) <= 0:
+        return 'none'
+    if int(n_codes) <= HAC_SORT_MAX:
+        return 'sort'
+    return 'dense' if int(K) <= HAC_DENSE_MAX_K else 'refused'
+
+
+def hac_work_bytes(n_streams, T, n_lags, n_windows):
+    """Bytes of device workspace a `hac_count_device` / `hac_fill_device` pair needs: klnmf_hac_work_bytes."""
+    out = _c.c_uint64(0)
+    _check(load().klnmf_hac_work_bytes(int(n_streams), int(T), int(n_lags), int(n_windows), _c.byref(out)))
+    return out.value
+
+
+def _hac_host_args(lags, windows):
+    lags = np.ascontiguousarray(lags, dtype=np.int32).reshape(-1)
+    windows = np.ascontiguousarray(windows, dtype=np.int64).reshape(-1, 2)
+    return lags, windows
+
+
+def hac_count_device(streams, T, lags, windows, d_work, work_bytes, d_indptr, f64=True, device=0):
+    """Quantises the streams (d_frames, ld, d_codebook, ldc, d, K) of DEVICE matrices with T frames each, counts and scans: the
+    int64 row pointers [len(windows) + 1] at d_indptr; returns nnz -- klnmf_hac_count_device.  `lags`, `windows` [(t0, t1) ...]:
+    host."""
+    streams = list(streams)
+    table = (HacStream * max(1, len(streams)))()
+    for s, (dx, ld, dc, ldc, d, K) in enumerate(streams):
+        table[s] = HacStream(dx or None, int(ld), dc or None, int(ldc), int(d), int(K))
+    lags, windows = _hac_host_args(lags, windows)
+    nnz = _i64(-1)
+    _check(load().klnmf_hac_count_device(device, DT_F64 if f64 else DT_F32, _c.cast(table, _c.c_void_p), len(streams), int(T),
+                                         lags.ctypes.data_as(_c.c_void_p), len(lags), windows.ctypes.data_as(_c.c_void_p),
+                                         len(windows), _c.c_void_p(d_work), int(work_bytes), _c.c_void_p(d_indptr), _c.byref(nnz)))
+    return int(nnz.value)
+
+
+def hac_fill_device(Ks, T, lags, windows, d_work, work_bytes, nnz, d_indices, d_values, f64=True, device=0):
+    """The int32 column indices at d_indices and the counts (float64, or float32 with f64=False) at d_values of the matrix the
+    preceding `hac_count_device` call on the same arguments and workspace measured: klnmf_hac_fill_device."""
+    Ks = np.ascontiguousarray(Ks, dtype=np.int64).reshape(-1)
+    lags, windows = _hac_host_args(lags, windows)
+    _check(load().klnmf_hac_fill_device(device, DT_F64 if f64 else DT_F32, Ks.ctypes.data_as(_c.c_void_p), len(Ks), int(T),
+                                        lags.ctypes.data_as(_c.c_void_p), len(lags), windows.ctypes.data_as(_c.c_void_p),
+                                        len(windows), _c.c_void_p(d_work), int(work_bytes), int(nnz), _c.c_void_p(d_indices),
+                                        _c.c_void_p(d_values)))
+
+
+def hac(streams, codebooks, lags, windows, dtype=np.float64, device=0):
+    """(indptr int64, indices int32, values `dtype`) of the windowed co-occurrence CSR matrix of HOST streams [T, d_s] and
+    codebooks [K_s, d_s] (float32 if all are float32, float64 otherwise): klnmf_hac."""
+    f32 = all(np.asarray(a).dtype == np.float32 for a in list(streams) + list(codebooks))
+    dt = np.float32 if f32 else np.float64
+    streams = [np.ascontiguousarray(x, dtype=dt) for x in streams]
+    codebooks = [np.ascontiguousarray(c, dtype=dt) for c in codebooks]
+    vdt = np.dtype(dtype)
+    if vdt not in (np.float32, np.float64):
+        raise TypeError("values are float32 or float64, got %s" % vdt)
+    lags, windows = _hac_host_args(lags, windows)
+    T = streams[0].shape[0] if streams else 0
+    table = (HacStream * max(1, len(streams)))()
+    for s, (x, c) in enumerate(zip(streams, codebooks)):
+        table[s] = HacStream(x.ctypes.data or None, x.shape[1], c.ctypes.data or None, c.shape[1], x.shape[1], c.shape[0])
+    # (an upper bound of nnz from the windows alone: a segment stores at most min(n_codes, K^2) entries)
+    length = (windows[:, 1] - windows[:, 0]) if len(windows) else np.zeros(0, dtype=np.int64)
+    capacity = 0
+    for c in codebooks:
+        for lag in lags:
+            capacity += int(np.minimum(np.maximum(length - int(lag), 0), c.shape[0] ** 2).sum())
+    indptr = np.zeros(len(windows) + 1, dtype=np.int64)
+    indices = np.empty(max(1, capacity), dtype=np.int32)
+    values = np.empty(max(1, capacity), dtype=vdt)
+    nnz = _i64(-1)
+    p = lambda a: a.ctypes.data_as(_c.c_void_p)
+    _check(load().klnmf_hac(device, DT_F32 if f32 else DT_F64, DT_F32 if vdt == np.float32 else DT_F64, _c.cast(table, _c.c_void_p),
+                            len(streams), int(T), p(lags), len(lags), p(windows), len(windows), p(indptr), capacity, p(indices),
+                            p(values), _c.byref(nnz)))
+    return indptr, indices[:nnz.value].copy(), values[:nnz.value].copy()
 
 
 def csr_rows_to_dense_device(d_indptr, d_indices, d_data, f64, src_rows, d_row_idx, rows, d, d_out, ld, device=0):

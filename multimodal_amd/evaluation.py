@@ -127,6 +127,27 @@ def information_matrix(internal, labels, n_labels=None, bins=10, return_counts=F
     return _native.information(internal, labels, n_labels, bins=int(bins), return_counts=return_counts)
 
 
+def sliding_distances(learner, modality, streams, codebooks, windows, example_coefficients, iterations, lags=(5, 2),
+                      metric='cosine_diff', device=None):
+    """The [len(windows), n_examples] matrix the reference's sliding evaluation stores as `sliding_distances`
+    (samples/image_sound_eval_sliding.py:97-126, behind the MFCC front end): every window of the frame `streams` becomes a HAC
+    row, built as CSR on the device (`features.hac.windowed_hac`); the rows are transformed on `learner`'s dictionary of
+    `modality` for `iterations` updates (`MultimodalLearner.reconstruct_internal` on the device arrays); the internal
+    coefficients are compared with `example_coefficients` [n_examples, k] under `metric` (a measure's name or function,
+    `all_distances`'s); `device`: `windowed_hac`'s.  The counts take the example coefficients' type (float32 stays float32,
+    anything else float64)."""
+    from . import _native
+    from .features.hac import windowed_hac
+    code = _measure_code(metric)
+    examples = np.asarray(todense(example_coefficients))
+    if examples.ndim != 2 or examples.shape[1] != learner.k:
+        raise ValueError("example coefficients [n_examples, %d] expected, got shape %s" % (learner.k, examples.shape))
+    dtype = np.float32 if examples.dtype == np.float32 else np.float64
+    rows = windowed_hac(streams, codebooks, windows, lags=lags, dtype=dtype, device=device, output='device')
+    internal = learner.reconstruct_internal(modality, rows, iterations)
+    return _native.all_distances(internal, examples, code)
+
+
 def scores_from_dists(dists, true_labels_0, true_labels_1=None, verbose=False):
     """Deprecated in the reference too (evaluation.py:61-71)."""
     if true_labels_1 is None:

@@ -132,8 +132,40 @@ class MultimodalLearner(object):
                                 self._scales(orig_mods), iterations, weights=weights, beta=self.beta)
 
     def reconstruct_internal(self, orig_mod, test_data, iterations):
+        """Internal coefficients from one modality (reference learner.py:68-69).  `test_data` may be a
+        `features.hac.DeviceCsrRows` (a CSR matrix built on the device): see `_reconstruct_internal_device_rows`."""
+        from .features.hac import DeviceCsrRows
+        if isinstance(test_data, DeviceCsrRows):
+            return self._reconstruct_internal_device_rows(orig_mod, test_data, iterations)
         return self.reconstruct_internal_multi([orig_mod], [test_data],
                                                iterations)
+
+    def _reconstruct_internal_device_rows(self, orig_mod, X, iterations):
+        """`reconstruct_internal(orig_mod, X.to_scipy(), iterations)`, bit for bit, without the download: the CSR problem is
+        gathered from X's device arrays (klnmf_upload_csr_device_rows: X the single source, the identity as row index, the
+        modality's coefficient as scale), as `DeviceDataset._fit_sparse` does.  Where `device_data.csr_rows_plan` says the
+        gather cannot reproduce the reference's dropped zeros -- and for another cost than Kullback-Leibler, or a matrix
+        without stored entries -- the host path runs on `X.to_scipy()`."""
+        import numpy as np
+        from .device_data import csr_rows_plan
+        idx = self.get_index(orig_mod)
+        n, f = X.shape
+        assert(f == self.dim[idx])
+        coef = self.coef[idx]
+        nnz, use_device = csr_rows_plan([X.indptr], np.arange(n, dtype=np.int64), [coef], [X.least])
+        if self.beta != 1.0 or not use_device or nnz == 0:
+            return self.reconstruct_internal_multi([orig_mod], [X.to_scipy()], iterations)
+        import torch
+        rows = torch.arange(n, dtype=torch.int64, device=X.d_indptr.device)
+
+        def upload(ctx):         # (synchronous: `rows` is free to go when it returns)
+            ctx.upload_csr_device_rows([X.pointers()], [0, f], [float(coef)], n, rows.data_ptr(), n)
+        dictionary = self.get_stacked_dicos([orig_mod])
+        model = NMF(n_components=dictionary.shape[0], max_iter=iterations, tol=0)
+        model.components_ = dictionary
+        model._init_dictionary = dictionary       # (`_transform_blocks`)
+        out_dtype_of = lambda H: np.float32 if (not X.f64 and H.dtype == np.float32) else np.float64      # (as `_fit_blocks` on CSR)
+        return model._fit_uploaded(n, f, upload, out_dtype_of, _fit=False, sparse_nnz=nnz)
 
     def reconstruct_modalities(self, dest_mods, internal):
         """internal . stacked dictionaries of dest_mods (reference learner.py:83-84),
