@@ -231,6 +231,18 @@ HAC_SIGNATURES = {
                              _c.c_void_p, _i64, _c.c_void_p, _c.c_void_p, _c.POINTER(_i64)]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/klnmf_kmeans.h (the codebook builders' device half), which the same
+# library exports
+KMEANS_SIGNATURES = {
+    'klnmf_kmeans_work_bytes': (_c.c_int, [_i64, _i64, _i64, _c.POINTER(_c.c_uint64)]),
+    'klnmf_kmeans_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _i64, _i64, _i64, _c.c_void_p, _i64, _i64, _c.c_int,
+                                       _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p]),
+    'klnmf_kmeans_gram_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _i64, _i64, _i64, _c.c_void_p, _i64, _c.c_void_p,
+                                            _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.POINTER(_i64)]),
+    'klnmf_kmeans': (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _i64, _i64, _i64, _c.c_void_p, _i64, _i64, _c.c_int, _c.c_void_p,
+                                _c.c_void_p]),
+}
+
 _lib = None
 
 
@@ -256,7 +268,8 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(BATCH_MASK_SIGNATURES.items()) \
             + list(BATCH_CSR_SIGNATURES.items()) + list(BETA_SIGNATURES.items()) + list(BATCH_BETA_SIGNATURES.items()) \
-            + list(NEAREST_SIGNATURES.items()) + list(INFORMATION_SIGNATURES.items()) + list(HAC_SIGNATURES.items()):
+            + list(NEAREST_SIGNATURES.items()) + list(INFORMATION_SIGNATURES.items()) + list(HAC_SIGNATURES.items()) \
+            + list(KMEANS_SIGNATURES.items()):
         fn = getattr(lib, name)     # AttributeError if a symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -567,6 +580,53 @@ def hac(streams, codebooks, lags, windows, dtype=np.float64, device=0):
                             len(streams), int(T), p(lags), len(lags), p(windows), len(windows), p(indptr), capacity, p(indices),
                             p(values), _c.byref(nnz)))
     return indptr, indices[:nnz.value].copy(), values[:nnz.value].copy()
+
+
+KMEANS_TILE, KMEANS_GROUP = 256, 4096    # KLNMF_KMEANS_TILE, KLNMF_KMEANS_GROUP: the group is the unit of the summation order
+KMEANS_MAX_KD = 13312                    # KLNMF_KMEANS_MAX_KD: K * d of a Lloyd call (fp64 accumulators in LDS)
+KMEANS_GRAM_MAX_D = 64                   # KLNMF_KMEANS_GRAM_MAX_D
+
+
+def kmeans_work_bytes(T, d, K):
+    """Bytes of device workspace a `kmeans_device` or `kmeans_gram_device` call needs: klnmf_kmeans_work_bytes."""
+    out = _c.c_uint64(0)
+    _check(load().klnmf_kmeans_work_bytes(int(T), int(d), int(K), _c.byref(out)))
+    return out.value
+
+
+def kmeans_device(d_frames, ld, T, d, d_codebook, ldc, K, n_iter, d_work, work_bytes, d_labels, d_counts, f64=True, device=0):
+    """`n_iter` Lloyd iterations on DEVICE frames [T, d] and a DEVICE codebook [K, d] (in/out), the int32 labels [T] and int64
+    counts [K] of the last assignment at d_labels / d_counts; no synchronisation: klnmf_kmeans_device."""
+    _check(load().klnmf_kmeans_device(device, DT_F64 if f64 else DT_F32, _c.c_void_p(d_frames or None), int(ld), int(T), int(d),
+                                      _c.c_void_p(d_codebook or None), int(ldc), int(K), int(n_iter), _c.c_void_p(d_work or None),
+                                      int(work_bytes), _c.c_void_p(d_labels or None), _c.c_void_p(d_counts or None)))
+
+
+def kmeans_gram_device(d_frames, ld, T, d, d_labels, cluster, d_work, work_bytes, d_gram, d_colsum, f64=True, device=0):
+    """The fp64 Gram matrix [d, d] at d_gram and column sums [d] at d_colsum of the DEVICE frames with label `cluster` (-1: of all
+    frames); returns their number: klnmf_kmeans_gram_device."""
+    count = _i64(-1)
+    _check(load().klnmf_kmeans_gram_device(device, DT_F64 if f64 else DT_F32, _c.c_void_p(d_frames or None), int(ld), int(T), int(d),
+                                           _c.c_void_p(d_labels or None), int(cluster), _c.c_void_p(d_work or None), int(work_bytes),
+                                           _c.c_void_p(d_gram or None), _c.c_void_p(d_colsum or None), _c.byref(count)))
+    return int(count.value)
+
+
+def kmeans(frames, codebook, n_iter, device=0):
+    """(codebook, labels int32, counts int64) after `n_iter` Lloyd iterations from HOST frames [T, d] and codebook [K, d]
+    (float32 if both are float32, float64 otherwise): klnmf_kmeans."""
+    f32 = np.asarray(frames).dtype == np.float32 and np.asarray(codebook).dtype == np.float32
+    dt = np.float32 if f32 else np.float64
+    frames = np.ascontiguousarray(frames, dtype=dt)
+    codebook = np.array(codebook, dtype=dt, order='C')
+    T, d = frames.shape
+    K = codebook.shape[0]
+    labels = np.zeros(max(1, T), dtype=np.int32)
+    counts = np.zeros(max(1, K), dtype=np.int64)
+    p = lambda a: a.ctypes.data_as(_c.c_void_p)
+    _check(load().klnmf_kmeans(device, DT_F32 if f32 else DT_F64, p(frames) if T else None, d, T, d, p(codebook), codebook.shape[1], K,
+                               int(n_iter), p(labels), p(counts)))
+    return codebook, labels[:T], counts[:K]
 
 
 def csr_rows_to_dense_device(d_indptr, d_indices, d_data, f64, src_rows, d_row_idx, rows, d, d_out, ld, device=0):

@@ -19,7 +19,10 @@
 //                    126-136): checks, workspace layout and the launches of information.hip.h, included by that unit alone
 //   api_hac.hip      the windowed co-occurrence histograms of include/klnmf_hac.h (features/hac.py:152-196 behind its MFCCs, for the
 //                    windows of samples/image_sound_eval_sliding.py:97-113): checks, workspace layout and the launches of
-//                    hac.hip.h, included by that unit alone
+//                    hac.hip.h
+//   api_kmeans.hip   the codebook builders' device half of include/klnmf_kmeans.h (features/hac.py:68-107: Lloyd iterations and
+//                    the Gram matrix of a cluster's members): checks, workspace layout and the launches of kmeans.hip.h, included
+//                    by that unit alone
 // This header: error handling, the type dispatch of the host-facing kernels, the device block cache and the arena over it
 // (DeviceBlocks), the staged host upload, the development switches, the mask state (PresenceState) and the context itself -- its
 // state in four groups, one per lifetime (ContextState, ProblemState, LoopState, LoopRecord) -- and what contexts and batches share

@@ -13,8 +13,8 @@ the MFCCs is integer work with an exact answer, and that part lives here:
 * `frame_windows`, the frame ranges of the reference's `slider` (lib/window.py:345-357) on an integer frame axis.
 
 Not here: the MFCC front end itself -- the reference's `mfcc`, `hac(data, sr, ...)` on audio and `wav2hac` need librosa and the
-recordings -- and the codebook builders (`build_codebook`, `iterative_kmeans`: scipy's kmeans2).  Callers bring the frame streams
-and the codebooks.
+recordings.  Callers bring the frame streams; the codebook builders (`build_codebook`, `iterative_kmeans`) are
+`features.codebook`'s, whose device codebooks `windowed_hac` takes as they are.
 """
 import numpy as np
 import scipy.sparse as sp
