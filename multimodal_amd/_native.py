@@ -243,6 +243,22 @@ KMEANS_SIGNATURES = {
                                 _c.c_void_p]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/klnmf_motion.h (the motion modality's device half), which the same
+# library exports
+MOTION_SIGNATURES = {
+    'klnmf_motion_work_bytes': (_c.c_int, [_i64, _i64, _i64, _i64, _i64, _i64, _i64, _c.POINTER(_c.c_uint64)]),
+    'klnmf_motion_angles_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _i64, _i64, _c.c_void_p, _i64, _c.c_void_p, _i64, _i64,
+                                              _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _i64,
+                                              _c.c_void_p, _i64]),
+    'klnmf_motion_whiten_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _i64, _i64, _i64, _c.c_void_p, _c.c_uint64, _c.c_void_p,
+                                              _i64, _c.c_void_p, _c.c_void_p]),
+    'klnmf_motion_kmeans_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _i64, _i64, _i64, _i64, _i64, _c.c_void_p, _i64,
+                                              _c.c_void_p, _i64, _c.c_double, _c.c_int, _c.c_void_p, _c.c_uint64, _c.c_void_p,
+                                              _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_int)]),
+    'klnmf_motion_hist_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _i64, _i64, _i64, _i64, _i64, _c.c_void_p, _i64,
+                                            _c.c_void_p, _i64, _c.c_int, _c.c_double, _c.c_void_p, _c.c_uint64, _c.c_void_p, _i64]),
+}
+
 _lib = None
 
 
@@ -269,7 +285,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(BATCH_MASK_SIGNATURES.items()) \
             + list(BATCH_CSR_SIGNATURES.items()) + list(BETA_SIGNATURES.items()) + list(BATCH_BETA_SIGNATURES.items()) \
             + list(NEAREST_SIGNATURES.items()) + list(INFORMATION_SIGNATURES.items()) + list(HAC_SIGNATURES.items()) \
-            + list(KMEANS_SIGNATURES.items()):
+            + list(KMEANS_SIGNATURES.items()) + list(MOTION_SIGNATURES.items()):
         fn = getattr(lib, name)     # AttributeError if a symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -627,6 +643,75 @@ def kmeans(frames, codebook, n_iter, device=0):
     _check(load().klnmf_kmeans(device, DT_F32 if f32 else DT_F64, p(frames) if T else None, d, T, d, p(codebook), codebook.shape[1], K,
                                int(n_iter), p(labels), p(counts)))
     return codebook, labels[:T], counts[:K]
+
+
+MOTION_TILE, MOTION_GROUP = 256, 4096    # KLNMF_MOTION_TILE, KLNMF_MOTION_GROUP: the group is the unit of the summation order
+MOTION_MAX_K, MOTION_MAX_D, MOTION_MAX_KD = 256, 16, 1024    # KLNMF_MOTION_MAX_K, _MAX_D, _MAX_KD
+MOTION_MAX_PAIRS, MOTION_MAX_P, MOTION_POLL = 32, 65535, 4   # KLNMF_MOTION_MAX_PAIRS, _MAX_P, _POLL
+MOTION_PADDINGS = {'zeros': 0, 'circular': 1}                # KLNMF_MOTION_PAD_ZEROS, KLNMF_MOTION_PAD_CIRCULAR
+
+
+def _host_array(a, dt):
+    a = np.ascontiguousarray(a, dtype=dt)
+    return a, a.ctypes.data_as(_c.c_void_p)
+
+
+def _host_bounds(b):
+    if b is None:
+        return None, None
+    return _host_array([float(b[0]), float(b[1])], np.float64)
+
+
+def motion_work_bytes(T, C=0, d=1, K=1, P=0, D=1, E=0):
+    """Bytes of device workspace a call of klnmf_motion.h on these sizes needs: klnmf_motion_work_bytes."""
+    out = _c.c_uint64(0)
+    _check(load().klnmf_motion_work_bytes(int(T), int(C), int(d), int(K), int(P), int(D), int(E), _c.byref(out)))
+    return out.value
+
+
+def motion_angles_device(d_records, T, n_markers, pairs, offsets, delay, padding, bounds, vel_bounds, d_work, work_bytes, d_angles,
+                         lda, d_vels, ldv, f64=True, device=0):
+    """Angles and delayed velocities [T, 3 len(pairs)] of DEVICE records [T, n_markers, 7]; `pairs` and `offsets` (E + 1) are host
+    sequences, `padding` a KLNMF_MOTION_PAD_* number, the bounds (min, max) or None: klnmf_motion_angles_device."""
+    pairs, p_pairs = _host_array(pairs, np.int32)
+    offsets, p_off = _host_array(offsets, np.int64)
+    b, p_b = _host_bounds(bounds)
+    vb, p_vb = _host_bounds(vel_bounds)
+    _check(load().klnmf_motion_angles_device(device, DT_F64 if f64 else DT_F32, _c.c_void_p(d_records or None), int(T), int(n_markers),
+                                             p_pairs, pairs.size // 2, p_off, offsets.size - 1, int(delay), int(padding), p_b, p_vb,
+                                             _c.c_void_p(d_work or None), int(work_bytes), _c.c_void_p(d_angles or None), int(lda),
+                                             _c.c_void_p(d_vels or None), int(ldv)))
+
+
+def motion_whiten_device(d_x, ld, T, C, d_work, work_bytes, d_out, ldo, d_mean, d_std, f64=True, device=0):
+    """DEVICE out [T, C] = x / std per column, the fp64 means and deviations at d_mean / d_std: klnmf_motion_whiten_device."""
+    _check(load().klnmf_motion_whiten_device(device, DT_F64 if f64 else DT_F32, _c.c_void_p(d_x or None), int(ld), int(T), int(C),
+                                             _c.c_void_p(d_work or None), int(work_bytes), _c.c_void_p(d_out or None), int(ldo),
+                                             _c.c_void_p(d_mean or None), _c.c_void_p(d_std or None)))
+
+
+def motion_kmeans_device(d_points, set_stride, ld, T, d, D, set_of, d_codebooks, K, thresh, max_iter, d_work, work_bytes, d_alive,
+                         d_distortion, d_iters, d_labels=0, f64=True, device=0):
+    """len(set_of) k-means problems to convergence on DEVICE point sets and codebooks [P, K, d] (in/out); returns -1, or the lowest
+    problem that had not stopped after max_iter iterations: klnmf_motion_kmeans_device."""
+    set_of, p_set = _host_array(set_of, np.int32)
+    unfinished = _c.c_int(-2)
+    _check(load().klnmf_motion_kmeans_device(device, DT_F64 if f64 else DT_F32, _c.c_void_p(d_points or None), int(set_stride), int(ld),
+                                             int(T), int(d), int(D), p_set, set_of.size, _c.c_void_p(d_codebooks or None), int(K),
+                                             float(thresh), int(max_iter), _c.c_void_p(d_work or None), int(work_bytes),
+                                             _c.c_void_p(d_alive or None), _c.c_void_p(d_distortion or None),
+                                             _c.c_void_p(d_iters or None), _c.c_void_p(d_labels or None), _c.byref(unfinished)))
+    return int(unfinished.value)
+
+
+def motion_hist_device(d_points, set_stride, ld, T, d, D, d_codebooks, K, offsets, soft, alpha, d_work, work_bytes, d_out, ldo,
+                       f64=True, device=0):
+    """DEVICE out [E, D * K]: the row-normalised hard (soft = 0) or soft histograms of the examples: klnmf_motion_hist_device."""
+    offsets, p_off = _host_array(offsets, np.int64)
+    _check(load().klnmf_motion_hist_device(device, DT_F64 if f64 else DT_F32, _c.c_void_p(d_points or None), int(set_stride), int(ld),
+                                           int(T), int(d), int(D), _c.c_void_p(d_codebooks or None), int(K), p_off, offsets.size - 1,
+                                           int(soft), float(alpha), _c.c_void_p(d_work or None), int(work_bytes),
+                                           _c.c_void_p(d_out or None), int(ldo)))
 
 
 def csr_rows_to_dense_device(d_indptr, d_indices, d_data, f64, src_rows, d_row_idx, rows, d, d_out, ld, device=0):
