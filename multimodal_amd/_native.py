@@ -27,6 +27,7 @@ PRECISIONS = {'f64': PREC_F64, 'fp64': PREC_F64, 'float64': PREC_F64,
               'bf16x3': PREC_BF16X3,
               'f16x3': PREC_F16X3}
 DT_F32, DT_F64 = 0, 1
+_dt_code = lambda f64: DT_F64 if f64 else DT_F32          # the KLNMF_DT_* of a call that says f64=True / False
 STREAM_DEFAULT = (1 << 64) - 1        # KLNMF_STREAM_DEFAULT: (void *)(intptr_t)-1
 
 ERR_ARG, ERR_ALLOC, ERR_HIP, ERR_UNSUPP, ERR_RCCL, ERR_REPLICA = -1, -2, -3, -4, -5, -6
@@ -35,6 +36,7 @@ COMM_ID_BYTES = 128
 _c = ctypes
 _ctx_p = _c.c_void_p
 _i64 = _c.c_int64
+_ptr = lambda address: _c.c_void_p(address or None)       # a device pointer argument: 0 is NULL
 
 # name -> (restype, argtypes); must list every symbol of include/klnmf.h
 SIGNATURES = {
@@ -142,8 +144,7 @@ SIGNATURES = {
     'klnmf_selftest': (_c.c_int, [_c.c_int, _c.POINTER(_c.c_int)]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/klnmf_batch.h (batches: B problems of one shape in one launch
-# sequence), which the same library exports
+# name -> (restype, argtypes): every symbol of include/klnmf_batch.h (batches: B problems of one shape in one launch sequence)
 BATCH_SIGNATURES = {
     'klnmf_batch_create': (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int, _c.c_int, _c.c_int]),
     'klnmf_batch_destroy': (_c.c_int, [_c.c_void_p]),
@@ -163,8 +164,7 @@ BATCH_SIGNATURES = {
     'klnmf_batch_query': (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_i64)]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/klnmf_batch_mask.h (presence masks on batches), which the same
-# library exports
+# name -> (restype, argtypes): every symbol of include/klnmf_batch_mask.h (presence masks on batches)
 BATCH_MASK_SIGNATURES = {
     'klnmf_batch_upload_presence': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _i64, _i64, _i64, _c.POINTER(_i64),
                                                _c.c_int]),
@@ -173,8 +173,7 @@ BATCH_MASK_SIGNATURES = {
     'klnmf_batch_clear_presence': (_c.c_int, [_c.c_void_p]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/klnmf_batch_csr.h (CSR problems on batches), which the same
-# library exports
+# name -> (restype, argtypes): every symbol of include/klnmf_batch_csr.h (CSR problems on batches)
 BATCH_CSR_SIGNATURES = {
     'klnmf_batch_set_problem_sparse': (_c.c_int, [_c.c_void_p, _i64, _i64, _i64, _i64, _c.POINTER(_i64)]),
     'klnmf_batch_upload_csr_rows': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
@@ -183,8 +182,7 @@ BATCH_CSR_SIGNATURES = {
                                                       _c.POINTER(_c.c_double), _i64, _c.c_void_p, _i64]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/klnmf_beta.h (the beta-divergence cost on a context), which the
-# same library exports
+# name -> (restype, argtypes): every symbol of include/klnmf_beta.h (the beta-divergence cost on a context)
 BETA_SIGNATURES = {
     'klnmf_set_divergence': (_c.c_int, [_ctx_p, _c.c_double]),
     'klnmf_get_divergence': (_c.c_int, [_ctx_p, _c.POINTER(_c.c_double)]),
@@ -192,16 +190,14 @@ BETA_SIGNATURES = {
     'klnmf_beta_step': (_c.c_int, [_ctx_p, _c.c_int]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/klnmf_batch_beta.h (the beta-divergence cost on batches), which the
-# same library exports
+# name -> (restype, argtypes): every symbol of include/klnmf_batch_beta.h (the beta-divergence cost on batches)
 BATCH_BETA_SIGNATURES = {
     'klnmf_batch_set_divergence': (_c.c_int, [_c.c_void_p, _c.c_double]),
     'klnmf_batch_get_divergence': (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_double)]),
     'klnmf_batch_upload_weights': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _i64, _i64, _i64, _i64, _i64]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/klnmf_nearest.h (the fused nearest-example search), which the same
-# library exports
+# name -> (restype, argtypes): every symbol of include/klnmf_nearest.h (the fused nearest-example search)
 NEAREST_SIGNATURES = {
     'klnmf_nearest_work_bytes': (_c.c_int, [_i64, _i64, _c.POINTER(_c.c_uint64)]),
     'klnmf_nearest_many_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _i64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
@@ -209,8 +205,7 @@ NEAREST_SIGNATURES = {
     'klnmf_nearest': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _i64, _i64, _i64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/klnmf_information.h (the atom x label information matrix), which the
-# same library exports
+# name -> (restype, argtypes): every symbol of include/klnmf_information.h (the atom x label information matrix)
 INFORMATION_SIGNATURES = {
     'klnmf_information_work_bytes': (_c.c_int, [_i64, _i64, _c.c_int, _c.c_int, _c.POINTER(_c.c_uint64)]),
     'klnmf_information_many_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _i64, _c.c_void_p, _c.c_void_p,
@@ -219,8 +214,7 @@ INFORMATION_SIGNATURES = {
                                      _c.c_void_p]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/klnmf_hac.h (the windowed co-occurrence histograms), which the same
-# library exports
+# name -> (restype, argtypes): every symbol of include/klnmf_hac.h (the windowed co-occurrence histograms)
 HAC_SIGNATURES = {
     'klnmf_hac_work_bytes': (_c.c_int, [_c.c_int, _i64, _c.c_int, _i64, _c.POINTER(_c.c_uint64)]),
     'klnmf_hac_count_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _i64, _c.c_void_p, _c.c_int, _c.c_void_p, _i64,
@@ -231,8 +225,7 @@ HAC_SIGNATURES = {
                              _c.c_void_p, _i64, _c.c_void_p, _c.c_void_p, _c.POINTER(_i64)]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/klnmf_kmeans.h (the codebook builders' device half), which the same
-# library exports
+# name -> (restype, argtypes): every symbol of include/klnmf_kmeans.h (the codebook builders' device half)
 KMEANS_SIGNATURES = {
     'klnmf_kmeans_work_bytes': (_c.c_int, [_i64, _i64, _i64, _c.POINTER(_c.c_uint64)]),
     'klnmf_kmeans_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _i64, _i64, _i64, _c.c_void_p, _i64, _i64, _c.c_int,
@@ -243,8 +236,7 @@ KMEANS_SIGNATURES = {
                                 _c.c_void_p]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/klnmf_motion.h (the motion modality's device half), which the same
-# library exports
+# name -> (restype, argtypes): every symbol of include/klnmf_motion.h (the motion modality's device half)
 MOTION_SIGNATURES = {
     'klnmf_motion_work_bytes': (_c.c_int, [_i64, _i64, _i64, _i64, _i64, _i64, _i64, _c.POINTER(_c.c_uint64)]),
     'klnmf_motion_angles_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _i64, _i64, _c.c_void_p, _i64, _c.c_void_p, _i64, _i64,
@@ -258,6 +250,14 @@ MOTION_SIGNATURES = {
     'klnmf_motion_hist_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _i64, _i64, _i64, _i64, _i64, _c.c_void_p, _i64,
                                             _c.c_void_p, _i64, _c.c_int, _c.c_double, _c.c_void_p, _c.c_uint64, _c.c_void_p, _i64]),
 }
+
+# (header under include/, its table) in the order the headers came: load() binds every table, and the tests hold each table against
+# its header's declarations and all of them pairwise disjoint.  A new header adds its table above and one line here.
+HEADER_TABLES = (
+    ('klnmf.h', SIGNATURES), ('klnmf_batch.h', BATCH_SIGNATURES), ('klnmf_batch_mask.h', BATCH_MASK_SIGNATURES),
+    ('klnmf_batch_csr.h', BATCH_CSR_SIGNATURES), ('klnmf_beta.h', BETA_SIGNATURES), ('klnmf_batch_beta.h', BATCH_BETA_SIGNATURES),
+    ('klnmf_nearest.h', NEAREST_SIGNATURES), ('klnmf_information.h', INFORMATION_SIGNATURES), ('klnmf_hac.h', HAC_SIGNATURES),
+    ('klnmf_kmeans.h', KMEANS_SIGNATURES), ('klnmf_motion.h', MOTION_SIGNATURES))
 
 _lib = None
 
@@ -282,13 +282,11 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(BATCH_MASK_SIGNATURES.items()) \
-            + list(BATCH_CSR_SIGNATURES.items()) + list(BETA_SIGNATURES.items()) + list(BATCH_BETA_SIGNATURES.items()) \
-            + list(NEAREST_SIGNATURES.items()) + list(INFORMATION_SIGNATURES.items()) + list(HAC_SIGNATURES.items()) \
-            + list(KMEANS_SIGNATURES.items()) + list(MOTION_SIGNATURES.items()):
-        fn = getattr(lib, name)     # AttributeError if a symbol is not exported
-        fn.restype = res
-        fn.argtypes = args
+    for _, table in HEADER_TABLES:
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)     # AttributeError if a symbol is not exported
+            fn.restype = res
+            fn.argtypes = args
     _lib = lib
     return lib
 
@@ -317,6 +315,23 @@ def _np_dtype_code(a):
     if a.dtype == np.float32:
         return DT_F32
     raise TypeError("expected float32/float64, got %s" % a.dtype)
+
+
+def _work_bytes(entry, *sizes):
+    """What a klnmf_*_work_bytes entry point answers for these sizes (host arithmetic: no device is touched)."""
+    out = _c.c_uint64(0)
+    _check(getattr(load(), entry)(*([int(v) for v in sizes] + [_c.byref(out)])))
+    return out.value
+
+
+def _job_table(struct, rows, at_least=1):
+    """A ctypes array of `struct` filled from tuples in the order of its fields -- a pointer that is 0 becomes NULL, everything
+    else an int -- as a void pointer; never an array of no element, so that the pointer is not NULL either."""
+    rows = list(rows)
+    table = (struct * max(1, at_least, len(rows)))()
+    for q, row in enumerate(rows):
+        table[q] = struct(*[(v or None) if t is _c.c_void_p else int(v) for (_, t), v in zip(struct._fields_, row)])
+    return _c.cast(table, _c.c_void_p)
 
 
 def _as_float_array(a):
@@ -348,7 +363,7 @@ def matmul(A, B, device=0):
     B = np.ascontiguousarray(B, dtype=dt)
     C = np.empty((A.shape[0], B.shape[1]), dtype=dt)
     lib = load()
-    _check(lib.klnmf_matmul(device, DT_F32 if dt == np.float32 else DT_F64, A.shape[0], B.shape[1], A.shape[1],
+    _check(lib.klnmf_matmul(device, _dt_code(dt != np.float32), A.shape[0], B.shape[1], A.shape[1],
                             A.ctypes.data_as(_c.c_void_p), B.ctypes.data_as(_c.c_void_p),
                             C.ctypes.data_as(_c.c_void_p)))
     return C
@@ -368,7 +383,7 @@ def all_distances(A, B, metric, device=0):
     B = np.ascontiguousarray(B, dtype=dt)
     out = np.empty((A.shape[0], B.shape[0]), dtype=dt)
     lib = load()
-    _check(lib.klnmf_all_distances(device, DT_F32 if dt == np.float32 else DT_F64, int(metric), A.shape[0],
+    _check(lib.klnmf_all_distances(device, _dt_code(dt != np.float32), int(metric), A.shape[0],
                                    B.shape[0], A.shape[1], A.ctypes.data_as(_c.c_void_p),
                                    B.ctypes.data_as(_c.c_void_p), out.ctypes.data_as(_c.c_void_p)))
     return out
@@ -376,13 +391,13 @@ def all_distances(A, B, metric, device=0):
 
 def matmul_device(dA, lda, dB, ldb, dC, ldc, m, n, kk, f64=True, device=0):
     """C[m, n] = A[m, kk] . B[kk, n] between DEVICE matrices (pointers, row strides in elements): klnmf_matmul_device."""
-    _check(load().klnmf_matmul_device(device, DT_F64 if f64 else DT_F32, int(m), int(n), int(kk), _c.c_void_p(dA), int(lda),
+    _check(load().klnmf_matmul_device(device, _dt_code(f64), int(m), int(n), int(kk), _c.c_void_p(dA), int(lda),
                                       _c.c_void_p(dB), int(ldb), _c.c_void_p(dC), int(ldc)))
 
 
 def all_distances_device(dA, lda, dB, ldb, dout, na, nb, d, metric, f64=True, device=0):
     """out[na, nb] = metric(A[i], B[j]) between DEVICE matrices: klnmf_all_distances_device."""
-    _check(load().klnmf_all_distances_device(device, DT_F64 if f64 else DT_F32, int(metric), int(na), int(nb), int(d),
+    _check(load().klnmf_all_distances_device(device, _dt_code(f64), int(metric), int(na), int(nb), int(d),
                                              _c.c_void_p(dA), int(lda), _c.c_void_p(dB), int(ldb), _c.c_void_p(dout)))
 
 
@@ -410,9 +425,7 @@ def mask_metrics(mask):
 
 def nearest_work_bytes(count, total_rows):
     """Bytes of device workspace `nearest_many_device` needs for `count` jobs of `total_rows` rows: klnmf_nearest_work_bytes."""
-    out = _c.c_uint64(0)
-    _check(load().klnmf_nearest_work_bytes(int(count), int(total_rows), _c.byref(out)))
-    return out.value
+    return _work_bytes('klnmf_nearest_work_bytes', count, total_rows)
 
 
 def nearest_many_device(jobs, mask, d_idx, d_dist, d_work, work_bytes, f64=True, device=0):
@@ -420,10 +433,7 @@ def nearest_many_device(jobs, mask, d_idx, d_dist, d_work, work_bytes, f64=True,
     under each measure of `mask`, int32 [sum na][M] at d_idx (and the distances at d_dist, or None) -- one launch:
     klnmf_nearest_many_device."""
     jobs = list(jobs)
-    table = (NearestJob * max(1, len(jobs)))()
-    for q, (dA, lda, dB, ldb, na, nb, d) in enumerate(jobs):
-        table[q] = NearestJob(dA or None, int(lda), dB or None, int(ldb), int(na), int(nb), int(d))
-    _check(load().klnmf_nearest_many_device(device, DT_F64 if f64 else DT_F32, int(mask), _c.cast(table, _c.c_void_p), len(jobs),
+    _check(load().klnmf_nearest_many_device(device, _dt_code(f64), int(mask), _job_table(NearestJob, jobs), len(jobs),
                                             _c.c_void_p(d_idx), _c.c_void_p(d_dist), _c.c_void_p(d_work), int(work_bytes)))
 
 
@@ -440,7 +450,7 @@ def nearest(A, B, mask, device=0, return_distances=False):
     M = len(mask_metrics(mask)) if 0 < int(mask) <= DIST_MASK_ALL else 1
     idx = np.empty((A.shape[0], M), dtype=np.int32)
     dist = np.empty((A.shape[0], M), dtype=dt) if return_distances else None
-    _check(load().klnmf_nearest(device, DT_F32 if dt == np.float32 else DT_F64, int(mask), A.shape[0], B.shape[0], A.shape[1],
+    _check(load().klnmf_nearest(device, _dt_code(dt != np.float32), int(mask), A.shape[0], B.shape[0], A.shape[1],
                                 A.ctypes.data_as(_c.c_void_p), B.ctypes.data_as(_c.c_void_p), idx.ctypes.data_as(_c.c_void_p),
                                 dist.ctypes.data_as(_c.c_void_p) if return_distances else None))
     return (idx, dist) if return_distances else idx
@@ -465,9 +475,7 @@ def information_route(n_labels, bins):
 def information_work_bytes(count, total_atoms, n_labels, bins):
     """Bytes of device workspace `information_many_device` needs for `count` jobs of `total_atoms` atoms in all:
     klnmf_information_work_bytes."""
-    out = _c.c_uint64(0)
-    _check(load().klnmf_information_work_bytes(int(count), int(total_atoms), int(n_labels), int(bins), _c.byref(out)))
-    return out.value
+    return _work_bytes('klnmf_information_work_bytes', count, total_atoms, n_labels, bins)
 
 
 def information_many_device(jobs, n_labels, bins, d_info, d_counts, d_work, work_bytes, f64=True, device=0):
@@ -475,12 +483,9 @@ def information_many_device(jobs, n_labels, bins, d_info, d_counts, d_work, work
     jobs before it (and the int32 counts [k][n_labels][bins] at d_counts, or None) -- a fixed number of launches for all jobs:
     klnmf_information_many_device."""
     jobs = list(jobs)
-    table = (InformationJob * max(1, len(jobs)))()
-    for q, (dA, lda, d_labels, n, k) in enumerate(jobs):
-        table[q] = InformationJob(dA or None, int(lda), d_labels or None, int(n), int(k))
-    _check(load().klnmf_information_many_device(device, DT_F64 if f64 else DT_F32, int(n_labels), int(bins),
-                                                _c.cast(table, _c.c_void_p), len(jobs), _c.c_void_p(d_info), _c.c_void_p(d_counts),
-                                                _c.c_void_p(d_work), int(work_bytes)))
+    _check(load().klnmf_information_many_device(device, _dt_code(f64), int(n_labels), int(bins), _job_table(InformationJob, jobs),
+                                                len(jobs), _c.c_void_p(d_info), _c.c_void_p(d_counts), _c.c_void_p(d_work),
+                                                int(work_bytes)))
 
 
 def information(A, labels, n_labels, bins=10, device=0, return_counts=False):
@@ -498,7 +503,7 @@ def information(A, labels, n_labels, bins=10, device=0, return_counts=False):
     shape_ok = n >= 1 and k >= 1 and 1 <= int(n_labels) <= 65536 and 1 <= int(bins) <= 256
     info = np.empty((int(n_labels), k) if shape_ok else (1, 1), dtype=np.float64)
     counts = np.empty((k, int(n_labels), int(bins)) if shape_ok else (1, 1, 1), dtype=np.int32) if return_counts else None
-    _check(load().klnmf_information(device, DT_F32 if dt == np.float32 else DT_F64, int(n_labels), int(bins), n, k,
+    _check(load().klnmf_information(device, _dt_code(dt != np.float32), int(n_labels), int(bins), n, k,
                                     A.ctypes.data_as(_c.c_void_p), labels.ctypes.data_as(_c.c_void_p),
                                     info.ctypes.data_as(_c.c_void_p),
                                     counts.ctypes.data_as(_c.c_void_p) if return_counts else None))
@@ -528,9 +533,7 @@ def hac_route(n_codes, K):
 
 def hac_work_bytes(n_streams, T, n_lags, n_windows):
     """Bytes of device workspace a `hac_count_device` / `hac_fill_device` pair needs: klnmf_hac_work_bytes."""
-    out = _c.c_uint64(0)
-    _check(load().klnmf_hac_work_bytes(int(n_streams), int(T), int(n_lags), int(n_windows), _c.byref(out)))
-    return out.value
+    return _work_bytes('klnmf_hac_work_bytes', n_streams, T, n_lags, n_windows)
 
 
 def _hac_host_args(lags, windows):
@@ -544,12 +547,9 @@ def hac_count_device(streams, T, lags, windows, d_work, work_bytes, d_indptr, f6
     int64 row pointers [len(windows) + 1] at d_indptr; returns nnz -- klnmf_hac_count_device.  `lags`, `windows` [(t0, t1) ...]:
     host."""
     streams = list(streams)
-    table = (HacStream * max(1, len(streams)))()
-    for s, (dx, ld, dc, ldc, d, K) in enumerate(streams):
-        table[s] = HacStream(dx or None, int(ld), dc or None, int(ldc), int(d), int(K))
     lags, windows = _hac_host_args(lags, windows)
     nnz = _i64(-1)
-    _check(load().klnmf_hac_count_device(device, DT_F64 if f64 else DT_F32, _c.cast(table, _c.c_void_p), len(streams), int(T),
+    _check(load().klnmf_hac_count_device(device, _dt_code(f64), _job_table(HacStream, streams), len(streams), int(T),
                                          lags.ctypes.data_as(_c.c_void_p), len(lags), windows.ctypes.data_as(_c.c_void_p),
                                          len(windows), _c.c_void_p(d_work), int(work_bytes), _c.c_void_p(d_indptr), _c.byref(nnz)))
     return int(nnz.value)
@@ -560,7 +560,7 @@ def hac_fill_device(Ks, T, lags, windows, d_work, work_bytes, nnz, d_indices, d_
     preceding `hac_count_device` call on the same arguments and workspace measured: klnmf_hac_fill_device."""
     Ks = np.ascontiguousarray(Ks, dtype=np.int64).reshape(-1)
     lags, windows = _hac_host_args(lags, windows)
-    _check(load().klnmf_hac_fill_device(device, DT_F64 if f64 else DT_F32, Ks.ctypes.data_as(_c.c_void_p), len(Ks), int(T),
+    _check(load().klnmf_hac_fill_device(device, _dt_code(f64), Ks.ctypes.data_as(_c.c_void_p), len(Ks), int(T),
                                         lags.ctypes.data_as(_c.c_void_p), len(lags), windows.ctypes.data_as(_c.c_void_p),
                                         len(windows), _c.c_void_p(d_work), int(work_bytes), int(nnz), _c.c_void_p(d_indices),
                                         _c.c_void_p(d_values)))
@@ -578,9 +578,8 @@ def hac(streams, codebooks, lags, windows, dtype=np.float64, device=0):
         raise TypeError("values are float32 or float64, got %s" % vdt)
     lags, windows = _hac_host_args(lags, windows)
     T = streams[0].shape[0] if streams else 0
-    table = (HacStream * max(1, len(streams)))()
-    for s, (x, c) in enumerate(zip(streams, codebooks)):
-        table[s] = HacStream(x.ctypes.data or None, x.shape[1], c.ctypes.data or None, c.shape[1], x.shape[1], c.shape[0])
+    table = _job_table(HacStream, [(x.ctypes.data, x.shape[1], c.ctypes.data, c.shape[1], x.shape[1], c.shape[0])
+                                   for x, c in zip(streams, codebooks)], at_least=len(streams))
     # (an upper bound of nnz from the windows alone: a segment stores at most min(n_codes, K^2) entries)
     length = (windows[:, 1] - windows[:, 0]) if len(windows) else np.zeros(0, dtype=np.int64)
     capacity = 0
@@ -592,9 +591,8 @@ def hac(streams, codebooks, lags, windows, dtype=np.float64, device=0):
     values = np.empty(max(1, capacity), dtype=vdt)
     nnz = _i64(-1)
     p = lambda a: a.ctypes.data_as(_c.c_void_p)
-    _check(load().klnmf_hac(device, DT_F32 if f32 else DT_F64, DT_F32 if vdt == np.float32 else DT_F64, _c.cast(table, _c.c_void_p),
-                            len(streams), int(T), p(lags), len(lags), p(windows), len(windows), p(indptr), capacity, p(indices),
-                            p(values), _c.byref(nnz)))
+    _check(load().klnmf_hac(device, _dt_code(not f32), _dt_code(vdt != np.float32), table, len(streams), int(T), p(lags), len(lags),
+                            p(windows), len(windows), p(indptr), capacity, p(indices), p(values), _c.byref(nnz)))
     return indptr, indices[:nnz.value].copy(), values[:nnz.value].copy()
 
 
@@ -605,26 +603,23 @@ KMEANS_GRAM_MAX_D = 64                   # KLNMF_KMEANS_GRAM_MAX_D
 
 def kmeans_work_bytes(T, d, K):
     """Bytes of device workspace a `kmeans_device` or `kmeans_gram_device` call needs: klnmf_kmeans_work_bytes."""
-    out = _c.c_uint64(0)
-    _check(load().klnmf_kmeans_work_bytes(int(T), int(d), int(K), _c.byref(out)))
-    return out.value
+    return _work_bytes('klnmf_kmeans_work_bytes', T, d, K)
 
 
 def kmeans_device(d_frames, ld, T, d, d_codebook, ldc, K, n_iter, d_work, work_bytes, d_labels, d_counts, f64=True, device=0):
     """`n_iter` Lloyd iterations on DEVICE frames [T, d] and a DEVICE codebook [K, d] (in/out), the int32 labels [T] and int64
     counts [K] of the last assignment at d_labels / d_counts; no synchronisation: klnmf_kmeans_device."""
-    _check(load().klnmf_kmeans_device(device, DT_F64 if f64 else DT_F32, _c.c_void_p(d_frames or None), int(ld), int(T), int(d),
-                                      _c.c_void_p(d_codebook or None), int(ldc), int(K), int(n_iter), _c.c_void_p(d_work or None),
-                                      int(work_bytes), _c.c_void_p(d_labels or None), _c.c_void_p(d_counts or None)))
+    _check(load().klnmf_kmeans_device(device, _dt_code(f64), _ptr(d_frames), int(ld), int(T), int(d), _ptr(d_codebook), int(ldc),
+                                      int(K), int(n_iter), _ptr(d_work), int(work_bytes), _ptr(d_labels), _ptr(d_counts)))
 
 
 def kmeans_gram_device(d_frames, ld, T, d, d_labels, cluster, d_work, work_bytes, d_gram, d_colsum, f64=True, device=0):
     """The fp64 Gram matrix [d, d] at d_gram and column sums [d] at d_colsum of the DEVICE frames with label `cluster` (-1: of all
     frames); returns their number: klnmf_kmeans_gram_device."""
     count = _i64(-1)
-    _check(load().klnmf_kmeans_gram_device(device, DT_F64 if f64 else DT_F32, _c.c_void_p(d_frames or None), int(ld), int(T), int(d),
-                                           _c.c_void_p(d_labels or None), int(cluster), _c.c_void_p(d_work or None), int(work_bytes),
-                                           _c.c_void_p(d_gram or None), _c.c_void_p(d_colsum or None), _c.byref(count)))
+    _check(load().klnmf_kmeans_gram_device(device, _dt_code(f64), _ptr(d_frames), int(ld), int(T), int(d), _ptr(d_labels),
+                                           int(cluster), _ptr(d_work), int(work_bytes), _ptr(d_gram), _ptr(d_colsum),
+                                           _c.byref(count)))
     return int(count.value)
 
 
@@ -640,7 +635,7 @@ def kmeans(frames, codebook, n_iter, device=0):
     labels = np.zeros(max(1, T), dtype=np.int32)
     counts = np.zeros(max(1, K), dtype=np.int64)
     p = lambda a: a.ctypes.data_as(_c.c_void_p)
-    _check(load().klnmf_kmeans(device, DT_F32 if f32 else DT_F64, p(frames) if T else None, d, T, d, p(codebook), codebook.shape[1], K,
+    _check(load().klnmf_kmeans(device, _dt_code(not f32), p(frames) if T else None, d, T, d, p(codebook), codebook.shape[1], K,
                                int(n_iter), p(labels), p(counts)))
     return codebook, labels[:T], counts[:K]
 
@@ -664,9 +659,7 @@ def _host_bounds(b):
 
 def motion_work_bytes(T, C=0, d=1, K=1, P=0, D=1, E=0):
     """Bytes of device workspace a call of klnmf_motion.h on these sizes needs: klnmf_motion_work_bytes."""
-    out = _c.c_uint64(0)
-    _check(load().klnmf_motion_work_bytes(int(T), int(C), int(d), int(K), int(P), int(D), int(E), _c.byref(out)))
-    return out.value
+    return _work_bytes('klnmf_motion_work_bytes', T, C, d, K, P, D, E)
 
 
 def motion_angles_device(d_records, T, n_markers, pairs, offsets, delay, padding, bounds, vel_bounds, d_work, work_bytes, d_angles,
@@ -677,17 +670,15 @@ def motion_angles_device(d_records, T, n_markers, pairs, offsets, delay, padding
     offsets, p_off = _host_array(offsets, np.int64)
     b, p_b = _host_bounds(bounds)
     vb, p_vb = _host_bounds(vel_bounds)
-    _check(load().klnmf_motion_angles_device(device, DT_F64 if f64 else DT_F32, _c.c_void_p(d_records or None), int(T), int(n_markers),
-                                             p_pairs, pairs.size // 2, p_off, offsets.size - 1, int(delay), int(padding), p_b, p_vb,
-                                             _c.c_void_p(d_work or None), int(work_bytes), _c.c_void_p(d_angles or None), int(lda),
-                                             _c.c_void_p(d_vels or None), int(ldv)))
+    _check(load().klnmf_motion_angles_device(device, _dt_code(f64), _ptr(d_records), int(T), int(n_markers), p_pairs, pairs.size //
+                                             2, p_off, offsets.size - 1, int(delay), int(padding), p_b, p_vb, _ptr(d_work),
+                                             int(work_bytes), _ptr(d_angles), int(lda), _ptr(d_vels), int(ldv)))
 
 
 def motion_whiten_device(d_x, ld, T, C, d_work, work_bytes, d_out, ldo, d_mean, d_std, f64=True, device=0):
     """DEVICE out [T, C] = x / std per column, the fp64 means and deviations at d_mean / d_std: klnmf_motion_whiten_device."""
-    _check(load().klnmf_motion_whiten_device(device, DT_F64 if f64 else DT_F32, _c.c_void_p(d_x or None), int(ld), int(T), int(C),
-                                             _c.c_void_p(d_work or None), int(work_bytes), _c.c_void_p(d_out or None), int(ldo),
-                                             _c.c_void_p(d_mean or None), _c.c_void_p(d_std or None)))
+    _check(load().klnmf_motion_whiten_device(device, _dt_code(f64), _ptr(d_x), int(ld), int(T), int(C), _ptr(d_work),
+                                             int(work_bytes), _ptr(d_out), int(ldo), _ptr(d_mean), _ptr(d_std)))
 
 
 def motion_kmeans_device(d_points, set_stride, ld, T, d, D, set_of, d_codebooks, K, thresh, max_iter, d_work, work_bytes, d_alive,
@@ -696,11 +687,10 @@ def motion_kmeans_device(d_points, set_stride, ld, T, d, D, set_of, d_codebooks,
     problem that had not stopped after max_iter iterations: klnmf_motion_kmeans_device."""
     set_of, p_set = _host_array(set_of, np.int32)
     unfinished = _c.c_int(-2)
-    _check(load().klnmf_motion_kmeans_device(device, DT_F64 if f64 else DT_F32, _c.c_void_p(d_points or None), int(set_stride), int(ld),
-                                             int(T), int(d), int(D), p_set, set_of.size, _c.c_void_p(d_codebooks or None), int(K),
-                                             float(thresh), int(max_iter), _c.c_void_p(d_work or None), int(work_bytes),
-                                             _c.c_void_p(d_alive or None), _c.c_void_p(d_distortion or None),
-                                             _c.c_void_p(d_iters or None), _c.c_void_p(d_labels or None), _c.byref(unfinished)))
+    _check(load().klnmf_motion_kmeans_device(device, _dt_code(f64), _ptr(d_points), int(set_stride), int(ld), int(T), int(d),
+                                             int(D), p_set, set_of.size, _ptr(d_codebooks), int(K), float(thresh), int(max_iter),
+                                             _ptr(d_work), int(work_bytes), _ptr(d_alive), _ptr(d_distortion), _ptr(d_iters),
+                                             _ptr(d_labels), _c.byref(unfinished)))
     return int(unfinished.value)
 
 
@@ -708,16 +698,15 @@ def motion_hist_device(d_points, set_stride, ld, T, d, D, d_codebooks, K, offset
                        f64=True, device=0):
     """DEVICE out [E, D * K]: the row-normalised hard (soft = 0) or soft histograms of the examples: klnmf_motion_hist_device."""
     offsets, p_off = _host_array(offsets, np.int64)
-    _check(load().klnmf_motion_hist_device(device, DT_F64 if f64 else DT_F32, _c.c_void_p(d_points or None), int(set_stride), int(ld),
-                                           int(T), int(d), int(D), _c.c_void_p(d_codebooks or None), int(K), p_off, offsets.size - 1,
-                                           int(soft), float(alpha), _c.c_void_p(d_work or None), int(work_bytes),
-                                           _c.c_void_p(d_out or None), int(ldo)))
+    _check(load().klnmf_motion_hist_device(device, _dt_code(f64), _ptr(d_points), int(set_stride), int(ld), int(T), int(d), int(D),
+                                           _ptr(d_codebooks), int(K), p_off, offsets.size - 1, int(soft), float(alpha),
+                                           _ptr(d_work), int(work_bytes), _ptr(d_out), int(ldo)))
 
 
 def csr_rows_to_dense_device(d_indptr, d_indices, d_data, f64, src_rows, d_row_idx, rows, d, d_out, ld, device=0):
     """Rows row_idx[0 .. rows) of one DEVICE-resident CSR matrix (int64 row pointers, int32 column indices, float32 / float64
     values; pointers) as a dense float64 device matrix [rows, d], rows `ld` apart: klnmf_csr_rows_to_dense_device."""
-    _check(load().klnmf_csr_rows_to_dense_device(device, DT_F64 if f64 else DT_F32, _c.c_void_p(d_indptr), _c.c_void_p(d_indices),
+    _check(load().klnmf_csr_rows_to_dense_device(device, _dt_code(f64), _c.c_void_p(d_indptr), _c.c_void_p(d_indices),
                                                  _c.c_void_p(d_data), int(src_rows), _c.c_void_p(d_row_idx), int(rows), int(d),
                                                  _c.c_void_p(d_out), int(ld)))
 
@@ -898,7 +887,7 @@ class Context(object):
             raise ValueError("%d source columns for %d modalities" % (len(cols), len(bounds) - 1))
         cb = (_i64 * len(bounds))(*bounds)
         sc = (_c.c_int * max(1, len(cols)))(*cols)
-        _check(self._lib.klnmf_upload_presence_device_rows(self._h, _c.c_void_p(dev_ptr), DT_F64 if f64 else DT_F32, int(src_rows), int(ld),
+        _check(self._lib.klnmf_upload_presence_device_rows(self._h, _c.c_void_p(dev_ptr), _dt_code(f64), int(src_rows), int(ld),
                                                            _c.c_void_p(row_idx_ptr) if row_idx_ptr else None, int(rows), int(row0),
                                                            sc, cb, len(cols)))
 
@@ -950,7 +939,7 @@ class Context(object):
         indices = np.ascontiguousarray(X.indices, dtype=np.int64)
         data = np.ascontiguousarray(X.data, dtype=dt)
         p = lambda a: a.ctypes.data_as(_c.c_void_p)
-        _check(self._lib.klnmf_upload_csr_rows(self._h, DT_F32 if dt == np.float32 else DT_F64, p(indptr), p(indices), p(data)))
+        _check(self._lib.klnmf_upload_csr_rows(self._h, _dt_code(dt != np.float32), p(indptr), p(indices), p(data)))
         self._csr = (indptr, indices)
         return X
 
@@ -970,7 +959,7 @@ class Context(object):
         if len(col_bounds) != M + 1 or len(scales) != M:
             raise ValueError("%d sources need %d column bounds and %d scales" % (M, M + 1, M))
         ptrs = lambda j: (_c.c_void_p * M)(*[int(s[j]) or None for s in sources])
-        dts = (_c.c_int * M)(*[DT_F64 if s[3] else DT_F32 for s in sources])
+        dts = (_c.c_int * M)(*[_dt_code(s[3]) for s in sources])
         cb = (_i64 * (M + 1))(*[int(b) for b in col_bounds])
         sc = (_c.c_double * M)(*[float(v) for v in scales])
         _check(self._lib.klnmf_upload_csr_device_rows(self._h, M, ptrs(0), ptrs(1), ptrs(2), dts, cb, sc, int(src_rows),
@@ -988,18 +977,18 @@ class Context(object):
 
     def upload_V_device_rows_dt(self, dev_ptr, f64, row_idx_ptr, rows, cols, ld, row0=0, col0=0, scale=1.0):
         """The same for a float32 or float64 device-resident matrix; row_idx_ptr 0: rows 0 .. rows - 1."""
-        _check(self._lib.klnmf_upload_V_device_rows_dt(self._h, _c.c_void_p(dev_ptr), DT_F64 if f64 else DT_F32,
+        _check(self._lib.klnmf_upload_V_device_rows_dt(self._h, _c.c_void_p(dev_ptr), _dt_code(f64),
                                                        _c.c_void_p(row_idx_ptr) if row_idx_ptr else None, rows, cols, ld,
                                                        row0, col0, float(scale)))
 
     def set_H_device(self, dev_ptr, f64, ld, col0, ncols, last=True):
         """H[:, col0 : col0 + ncols] from a device-resident dictionary (klnmf_set_H_device)."""
-        _check(self._lib.klnmf_set_H_device(self._h, _c.c_void_p(dev_ptr), DT_F64 if f64 else DT_F32, int(ld), int(col0),
+        _check(self._lib.klnmf_set_H_device(self._h, _c.c_void_p(dev_ptr), _dt_code(f64), int(ld), int(col0),
                                             int(ncols), 1 if last else 0))
 
     def get_W_device(self, dev_ptr, f64, ld):
         """The coefficients into device memory ([n, k], rows ld apart): klnmf_get_W_device."""
-        _check(self._lib.klnmf_get_W_device(self._h, _c.c_void_p(dev_ptr), DT_F64 if f64 else DT_F32, int(ld)))
+        _check(self._lib.klnmf_get_W_device(self._h, _c.c_void_p(dev_ptr), _dt_code(f64), int(ld)))
 
     def set_H(self, H):
         H = _as_float_array(H)
@@ -1299,7 +1288,7 @@ def group_selftest(devices, count, f64=False):
     lib = load()
     devs = (_c.c_int * len(devices))(*[int(d) for d in devices])
     failed = _c.c_int(-1)
-    _check(lib.klnmf_group_selftest(devs, len(devices), int(count), DT_F64 if f64 else DT_F32, ctypes.byref(failed)))
+    _check(lib.klnmf_group_selftest(devs, len(devices), int(count), _dt_code(f64), ctypes.byref(failed)))
     return failed.value
 
 
@@ -1413,7 +1402,7 @@ class Batch(object):
         dt = np.float32 if X.dtype == np.float32 else np.float64
         data = np.ascontiguousarray(X.data, dtype=dt)
         ptr = lambda a: a.ctypes.data_as(_c.c_void_p)
-        _check(self._lib.klnmf_batch_upload_csr_rows(self._h, int(p), DT_F32 if dt == np.float32 else DT_F64, ptr(indptr), ptr(indices),
+        _check(self._lib.klnmf_batch_upload_csr_rows(self._h, int(p), _dt_code(dt != np.float32), ptr(indptr), ptr(indices),
                                                      ptr(data)))
 
     def upload_csr_device_rows(self, p, sources, col_bounds, scales, src_rows, row_idx_ptr, rows):
@@ -1422,7 +1411,7 @@ class Batch(object):
         if len(col_bounds) != M + 1 or len(scales) != M:
             raise ValueError("%d sources need %d column bounds and %d scales" % (M, M + 1, M))
         ptrs = lambda j: (_c.c_void_p * M)(*[int(s[j]) or None for s in sources])
-        dts = (_c.c_int * M)(*[DT_F64 if s[3] else DT_F32 for s in sources])
+        dts = (_c.c_int * M)(*[_dt_code(s[3]) for s in sources])
         cb = (_i64 * (M + 1))(*[int(b) for b in col_bounds])
         sc = (_c.c_double * M)(*[float(v) for v in scales])
         _check(self._lib.klnmf_batch_upload_csr_device_rows(self._h, int(p), M, ptrs(0), ptrs(1), ptrs(2), dts, cb, sc, int(src_rows),
@@ -1447,7 +1436,7 @@ class Batch(object):
                                               int(row0), int(col0), float(scale)))
 
     def upload_V_device_rows_dt(self, p, dev_ptr, f64, row_idx_ptr, rows, cols, ld, row0=0, col0=0, scale=1.0):
-        _check(self._lib.klnmf_batch_upload_V_device_rows_dt(self._h, int(p), _c.c_void_p(dev_ptr), DT_F64 if f64 else DT_F32,
+        _check(self._lib.klnmf_batch_upload_V_device_rows_dt(self._h, int(p), _c.c_void_p(dev_ptr), _dt_code(f64),
                                                              _c.c_void_p(row_idx_ptr) if row_idx_ptr else None, int(rows), int(cols),
                                                              int(ld), int(row0), int(col0), float(scale)))
 
@@ -1478,7 +1467,7 @@ class Batch(object):
         cb = (_i64 * len(bounds))(*bounds)
         sc = (_c.c_int * max(1, len(cols)))(*cols)
         _check(self._lib.klnmf_batch_upload_presence_device_rows(self._h, int(p), _c.c_void_p(dev_ptr) if dev_ptr else None,
-                                                                 DT_F64 if f64 else DT_F32, int(src_rows), int(ld),
+                                                                 _dt_code(f64), int(src_rows), int(ld),
                                                                  _c.c_void_p(row_idx_ptr) if row_idx_ptr else None, int(rows), int(row0),
                                                                  sc, cb, len(cols)))
 
@@ -1523,7 +1512,7 @@ class Batch(object):
         _check(self._lib.klnmf_batch_set_H(self._h, int(p), H.ctypes.data, _np_dtype_code(H)))
 
     def set_H_device(self, p, dev_ptr, f64, ld, col0, ncols, last=True):
-        _check(self._lib.klnmf_batch_set_H_device(self._h, int(p), _c.c_void_p(dev_ptr), DT_F64 if f64 else DT_F32, int(ld), int(col0),
+        _check(self._lib.klnmf_batch_set_H_device(self._h, int(p), _c.c_void_p(dev_ptr), _dt_code(f64), int(ld), int(col0),
                                                   int(ncols), 1 if last else 0))
 
     def set_W(self, p, W):
@@ -1562,7 +1551,7 @@ class Batch(object):
         return self._get(self._lib.klnmf_batch_get_H, p, (self.k, self.f), dtype)
 
     def get_W_device(self, p, dev_ptr, f64, ld):
-        _check(self._lib.klnmf_batch_get_W_device(self._h, int(p), _c.c_void_p(dev_ptr), DT_F64 if f64 else DT_F32, int(ld)))
+        _check(self._lib.klnmf_batch_get_W_device(self._h, int(p), _c.c_void_p(dev_ptr), _dt_code(f64), int(ld)))
 
     def query(self, what):
         v = _i64(0)

@@ -5,6 +5,7 @@
 #include "probe.hip.h"
 #include "../../include/klnmf_nearest.h"
 #include "nearest.hip.h"
+#include "feature_host.hip.h"
 
 thread_local std::string klnmf_host::g_err;
 
@@ -61,25 +62,25 @@ void matmul_on_device(int64_t m, int64_t n, int64_t kk, const void *A, const voi
 // ---- the fused nearest-example search (include/klnmf_nearest.h; nearest.hip.h) ----
 constexpr int64_t kNearestMaxRows = (int64_t)1 << 24;
 
-inline size_t nearest_table_bytes(int64_t count) { return ((size_t)count * sizeof(NearestJob) + 15) & ~(size_t)15; }
+// The caller's workspace: the job table at 0, the row -> job map behind it (its end is not rounded, so no WorkLayout).
+inline size_t nearest_table_bytes(int64_t count) { return up16((size_t)count * sizeof(NearestJob)); }
 inline size_t nearest_bytes(int64_t count, int64_t rows) { return nearest_table_bytes(count) + (size_t)rows * sizeof(int32_t); }
 
 // Checks a call's arguments (fail() on the first bad one: nothing has been touched then) and returns the sum of na.
-int64_t nearest_check(const char *who, int dtype, int metrics, const klnmf_nearest_job *jobs, int64_t count) {
-    auto bad = [&](const char *what) { fail(KLNMF_ERR_ARG, std::string(who) + ": " + what); };
-    if (dtype != KLNMF_DT_F32 && dtype != KLNMF_DT_F64) bad("dtype must be KLNMF_DT_F32 or KLNMF_DT_F64");
-    if (metrics <= 0 || metrics > KLNMF_DIST_MASK_ALL) bad("empty or unknown measure mask");
-    if (count < 0 || count > KLNMF_NEAREST_MAX_JOBS) bad("job count negative or above KLNMF_NEAREST_MAX_JOBS");
-    if (count > 0 && !jobs) bad("null job table");
+int64_t nearest_check(const Who &w, int dtype, int metrics, const klnmf_nearest_job *jobs, int64_t count) {
+    w.dtype(dtype);
+    if (metrics <= 0 || metrics > KLNMF_DIST_MASK_ALL) w.bad("empty or unknown measure mask");
+    if (count < 0 || count > KLNMF_NEAREST_MAX_JOBS) w.bad("job count negative or above KLNMF_NEAREST_MAX_JOBS");
+    if (count > 0 && !jobs) w.bad("null job table");
     int64_t rows = 0;
     for (int64_t q = 0; q < count; ++q) {
         const klnmf_nearest_job &j = jobs[q];
-        if (j.na < 0 || j.nb < 0 || j.d < 0 || j.na > kNearestMaxRows || j.nb > kNearestMaxRows || j.d > (1LL << 30)) bad("bad shape");
-        if (j.lda < j.d || j.ldb < j.d) bad("a stride below d");
-        if (j.na > 0 && j.nb == 0) bad("rows to classify and no example (nb = 0 with na > 0)");
-        if (j.na > 0 && j.d > 0 && (!j.A || !j.B)) bad("null operand");
+        if (j.na < 0 || j.nb < 0 || j.d < 0 || j.na > kNearestMaxRows || j.nb > kNearestMaxRows || j.d > (1LL << 30)) w.bad("bad shape");
+        if (j.lda < j.d || j.ldb < j.d) w.bad("a stride below d");
+        if (j.na > 0 && j.nb == 0) w.bad("rows to classify and no example (nb = 0 with na > 0)");
+        if (j.na > 0 && j.d > 0 && (!j.A || !j.B)) w.bad("null operand");
         rows += j.na;
-        if (rows > kNearestMaxRows) bad("more than 2^24 rows in one call");
+        if (rows > kNearestMaxRows) w.bad("more than 2^24 rows in one call");
     }
     return rows;
 }
@@ -105,12 +106,11 @@ void nearest_launch(int dtype, int metrics, const klnmf_nearest_job *jobs, int64
     HIPCHK(hipMemcpy(d_work, host.data(), host.size(), hipMemcpyHostToDevice));
     const NearestJob *table = (const NearestJob *)d_work;
     const int32_t *row_job = (const int32_t *)((const unsigned char *)d_work + nearest_table_bytes(count));
-    if (dtype == KLNMF_DT_F64)
-        hipLaunchKernelGGL((k_nearest<double>), dim3((unsigned)rows), dim3(64 * kNearestWaves), 0, 0, table, row_job, metrics, kEpsRatio,
-                           d_idx, (double *)d_dist);
-    else
-        hipLaunchKernelGGL((k_nearest<float>), dim3((unsigned)rows), dim3(64 * kNearestWaves), 0, 0, table, row_job, metrics, kEpsRatio,
-                           d_idx, (float *)d_dist);
+    by_dtype(dtype, [&](auto tag) {
+        using T = tag_t<decltype(tag)>;
+        hipLaunchKernelGGL((k_nearest<T>), dim3((unsigned)rows), dim3(64 * kNearestWaves), 0, 0, table, row_job, metrics, kEpsRatio, d_idx,
+                           (T *)d_dist);
+    });
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(0));
 }
@@ -121,9 +121,10 @@ extern "C" {
 
 int klnmf_nearest_work_bytes(int64_t count, int64_t total_rows, uint64_t *bytes) {
     return guarded([&] {
-        if (!bytes) fail(KLNMF_ERR_ARG, "klnmf_nearest_work_bytes: null bytes");
+        const Who w{"klnmf_nearest_work_bytes"};
+        if (!bytes) w.bad("null bytes");
         if (count < 0 || total_rows < 0 || count > KLNMF_NEAREST_MAX_JOBS || total_rows > kNearestMaxRows)
-            fail(KLNMF_ERR_ARG, "klnmf_nearest_work_bytes: a count negative or beyond the limits");
+            w.bad("a count negative or beyond the limits");
         *bytes = (uint64_t)nearest_bytes(count, total_rows);
     });
 }
@@ -131,10 +132,11 @@ int klnmf_nearest_work_bytes(int64_t count, int64_t total_rows, uint64_t *bytes)
 int klnmf_nearest_many_device(int device, int dtype, int metrics, const klnmf_nearest_job *jobs, int64_t count, int32_t *d_idx,
                               void *d_dist, void *d_work, uint64_t work_bytes) {
     return guarded([&] {
-        const int64_t rows = nearest_check("klnmf_nearest_many_device", dtype, metrics, jobs, count);
+        const Who w{"klnmf_nearest_many_device"};
+        const int64_t rows = nearest_check(w, dtype, metrics, jobs, count);
         if (rows == 0) return;
-        if (!d_idx || !d_work) fail(KLNMF_ERR_ARG, "klnmf_nearest_many_device: null output or workspace");
-        if (work_bytes < (uint64_t)nearest_bytes(count, rows)) fail(KLNMF_ERR_ARG, "klnmf_nearest_many_device: workspace below klnmf_nearest_work_bytes");
+        if (!d_idx || !d_work) w.bad("null output or workspace");
+        w.workspace(work_bytes, nearest_bytes(count, rows), "klnmf_nearest_work_bytes");
         HIPCHK(hipSetDevice(device));
         nearest_launch(dtype, metrics, jobs, count, rows, d_idx, d_dist, d_work);
     });
@@ -143,35 +145,27 @@ int klnmf_nearest_many_device(int device, int dtype, int metrics, const klnmf_ne
 int klnmf_nearest(int device, int dtype, int metrics, int64_t na, int64_t nb, int64_t d, const void *A, const void *B, int32_t *idx,
                   void *dist) {
     return guarded([&] {
+        const Who w{"klnmf_nearest"};
         klnmf_nearest_job job{A, d, B, d, na, nb, d};
-        const int64_t rows = nearest_check("klnmf_nearest", dtype, metrics, &job, 1);
+        const int64_t rows = nearest_check(w, dtype, metrics, &job, 1);
         if (rows == 0) return;
-        if (!idx) fail(KLNMF_ERR_ARG, "klnmf_nearest: null idx");
+        if (!idx) w.bad("null idx");
         HIPCHK(hipSetDevice(device));
-        const size_t el = dtype == KLNMF_DT_F64 ? 8 : 4, M = (size_t)__builtin_popcount((unsigned)metrics);
-        unsigned char *dA = nullptr, *dB = nullptr, *dV = nullptr, *dW = nullptr;
-        int32_t *dI = nullptr;
-        auto release = [&] { (void)hipFree(dA); (void)hipFree(dB); (void)hipFree(dV); (void)hipFree(dW); (void)hipFree(dI); };
-        try {
-            HIPCHK(hipMalloc((void **)&dA, el * (size_t)std::max<int64_t>(1, na * d)));
-            HIPCHK(hipMalloc((void **)&dB, el * (size_t)std::max<int64_t>(1, nb * d)));
-            HIPCHK(hipMalloc((void **)&dI, sizeof(int32_t) * (size_t)na * M));
-            if (dist) HIPCHK(hipMalloc((void **)&dV, el * (size_t)na * M));
-            HIPCHK(hipMalloc((void **)&dW, nearest_bytes(1, rows)));
-            if (d > 0) {
-                HIPCHK(hipMemcpy(dA, A, el * (size_t)(na * d), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(dB, B, el * (size_t)(nb * d), hipMemcpyHostToDevice));
-            }
-            job.A = dA;
-            job.B = dB;
-            nearest_launch(dtype, metrics, &job, 1, rows, dI, dV, dW);
-            HIPCHK(hipMemcpy(idx, dI, sizeof(int32_t) * (size_t)na * M, hipMemcpyDeviceToHost));
-            if (dist) HIPCHK(hipMemcpy(dist, dV, el * (size_t)na * M, hipMemcpyDeviceToHost));
-        } catch (...) {
-            release();
-            throw;
+        const size_t el = dtype_bytes(dtype), M = (size_t)__builtin_popcount((unsigned)metrics);
+        DeviceScratch mem;
+        void *dA = mem.take(el * (size_t)(na * d)), *dB = mem.take(el * (size_t)(nb * d));
+        int32_t *dI = (int32_t *)mem.take(sizeof(int32_t) * (size_t)na * M);
+        void *dV = dist ? mem.take(el * (size_t)na * M) : nullptr;
+        void *dW = mem.take(nearest_bytes(1, rows));
+        if (d > 0) {
+            HIPCHK(hipMemcpy(dA, A, el * (size_t)(na * d), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(dB, B, el * (size_t)(nb * d), hipMemcpyHostToDevice));
         }
-        release();
+        job.A = dA;
+        job.B = dB;
+        nearest_launch(dtype, metrics, &job, 1, rows, dI, dV, dW);
+        HIPCHK(hipMemcpy(idx, dI, sizeof(int32_t) * (size_t)na * M, hipMemcpyDeviceToHost));
+        if (dist) HIPCHK(hipMemcpy(dist, dV, el * (size_t)na * M, hipMemcpyDeviceToHost));
     });
 }
 

@@ -2,6 +2,7 @@
 // checks, the workspace layout, the launches of motion.hip.h (included by this unit alone) and the stop-flag polls of the
 // k-means loop.
 #include "ctx.hip.h"
+#include "feature_host.hip.h"
 #include "../../include/klnmf_motion.h"
 #include "motion.hip.h"
 
@@ -17,10 +18,7 @@ static_assert((size_t)kMoMaxKd * 16 + (size_t)kMoMaxD * kMoXStride * 8 + kMoTile
 namespace klnmf_host {
 namespace {
 
-constexpr int64_t kMoMaxInt = 0x7fffffffLL;
 constexpr size_t kMoPairBytes = 256;                // kMoMaxPairs * 2 int32
-
-inline size_t mo_up16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 // The caller's workspace (byte offsets).  The main part serves one call at a time: whitening (the partials at 0), k-means (the
 // partial sums at 0, then distances, counts, and the problems' previous distortion, stop flag and set), histograms (the raw
@@ -29,30 +27,27 @@ struct MoLayout {
     size_t groups, pdist, pcnt, prev, done, set_of, km, main, offsets, pairs, total;
     MoLayout(int64_t T, int64_t C, int64_t d, int64_t K, int64_t P, int64_t D, int64_t E) {
         groups = (size_t)mo_groups(T);
-        const size_t whiten = mo_up16(groups * (size_t)C * sizeof(double));
-        pdist = mo_up16(groups * (size_t)P * (size_t)K * (size_t)d * sizeof(double));
-        pcnt = pdist + mo_up16(groups * (size_t)P * sizeof(double));
-        prev = pcnt + mo_up16(groups * (size_t)P * (size_t)K * sizeof(int32_t));
-        done = prev + mo_up16((size_t)P * sizeof(double));
-        set_of = done + mo_up16((size_t)P * sizeof(int32_t));
-        km = set_of + mo_up16((size_t)P * sizeof(int32_t));
-        const size_t hist = mo_up16((size_t)E * (size_t)D * (size_t)K * sizeof(double));
-        main = std::max(whiten, std::max(km, hist));
-        offsets = main;
-        pairs = offsets + mo_up16((size_t)(E + 1) * sizeof(int64_t));
-        total = pairs + kMoPairBytes;
+        WorkLayout w, whiten, kmeans, hist;
+        whiten.take(groups * (size_t)C * sizeof(double));
+        kmeans.take(groups * (size_t)P * (size_t)K * (size_t)d * sizeof(double));
+        pdist = kmeans.take(groups * (size_t)P * sizeof(double));
+        pcnt = kmeans.take(groups * (size_t)P * (size_t)K * sizeof(int32_t));
+        prev = kmeans.take((size_t)P * sizeof(double));
+        done = kmeans.take((size_t)P * sizeof(int32_t));
+        set_of = kmeans.take((size_t)P * sizeof(int32_t));
+        km = kmeans.end;
+        hist.take((size_t)E * (size_t)D * (size_t)K * sizeof(double));
+        w.overlay({whiten, kmeans, hist});
+        main = w.end;
+        offsets = w.take((size_t)(E + 1) * sizeof(int64_t));
+        pairs = w.take(kMoPairBytes);
+        total = w.end;
     }
 };
 
-struct MoWho {
-    const char *who;
-    [[noreturn]] void bad(const std::string &what) const { fail(KLNMF_ERR_ARG, std::string(who) + ": " + what); }
-    [[noreturn]] void unsupp(const std::string &what) const { fail(KLNMF_ERR_UNSUPP, std::string(who) + ": " + what); }
-    void dtype(int dt) const {
-        if (dt != KLNMF_DT_F32 && dt != KLNMF_DT_F64) bad("dtype must be KLNMF_DT_F32 or KLNMF_DT_F64");
-    }
+struct MoWho : Who {                                // the refusals several of this unit's entry points share
     void frames(int64_t T, int64_t least) const {
-        if (T < least || T >= kMoMaxInt) bad("T below " + std::to_string(least) + " or not below 2^31 - 1");
+        if (T < least || T >= kMaxInt) bad("T below " + std::to_string(least) + " or not below 2^31 - 1");
     }
     void limits(int64_t d, int64_t K, int64_t P, int64_t D) const {
         if (K > kMoMaxK || d > kMoMaxD || K * d > kMoMaxKd)
@@ -62,7 +57,7 @@ struct MoWho {
     }
     void offsets(const int64_t *off, int64_t E, int64_t T) const {
         if (!off) bad("null offsets");
-        if (E < 1 || E >= kMoMaxInt) bad("E < 1");
+        if (E < 1 || E >= kMaxInt) bad("E < 1");
         if (off[0] != 0 || off[E] != T) bad("offsets that do not start at 0 or do not end at T");
         for (int64_t e = 0; e < E; ++e)
             if (off[e + 1] < off[e]) bad("offsets that decrease at example " + std::to_string(e));
@@ -148,10 +143,10 @@ extern "C" {
 
 int klnmf_motion_work_bytes(int64_t T, int64_t C, int64_t d, int64_t K, int64_t P, int64_t D, int64_t E, uint64_t *bytes) {
     return guarded([&] {
-        const MoWho w{"klnmf_motion_work_bytes"};
+        const MoWho w{{"klnmf_motion_work_bytes"}};
         if (!bytes) w.bad("null bytes");
         w.frames(T, 0);
-        if (C < 0 || P < 0 || E < 0 || C >= kMoMaxInt || E >= kMoMaxInt) w.bad("C, P or E negative or not below 2^31 - 1");
+        if (C < 0 || P < 0 || E < 0 || C >= kMaxInt || E >= kMaxInt) w.bad("C, P or E negative or not below 2^31 - 1");
         if (d < 1 || K < 1 || D < 1) w.bad("d, K or D < 1");
         w.limits(d, K, P, D);
         *bytes = (uint64_t)MoLayout(T, C, d, K, P, D, E).total;
@@ -163,11 +158,11 @@ int klnmf_motion_angles_device(int device, int dtype, const void *records, int64
                                const double *bounds, const double *vel_bounds, void *d_work, uint64_t work_bytes, void *angles,
                                int64_t lda, void *vels, int64_t ldv) {
     return guarded([&] {
-        const MoWho w{"klnmf_motion_angles_device"};
+        const MoWho w{{"klnmf_motion_angles_device"}};
         w.dtype(dtype);
         w.frames(T, 1);
         if (!records || !pairs || !angles || !vels || !d_work) w.bad("null records, pairs, angles, velocities or workspace");
-        if (n_markers < 1 || n_markers >= kMoMaxInt / 8) w.bad("n_markers < 1 or too large");
+        if (n_markers < 1 || n_markers >= kMaxInt / 8) w.bad("n_markers < 1 or too large");
         if (n_pairs < 1) w.bad("n_pairs < 1");
         if (n_pairs > kMoMaxPairs) w.unsupp("n_pairs = " + std::to_string(n_pairs) + " is above " + std::to_string(kMoMaxPairs));
         for (int64_t i = 0; i < 2 * n_pairs; ++i)
@@ -179,15 +174,15 @@ int klnmf_motion_angles_device(int device, int dtype, const void *records, int64
         for (const double *b : {bounds, vel_bounds})
             if (b && !(b[0] <= b[1])) w.bad("bounds with min > max or a NaN");
         const MoLayout at(T, 0, 1, 1, 0, 1, E);
-        if (work_bytes < (uint64_t)at.total) w.bad("workspace below klnmf_motion_work_bytes");
+        w.workspace(work_bytes, at.total, "klnmf_motion_work_bytes");
         HIPCHK(hipSetDevice(device));
         unsigned char *work = (unsigned char *)d_work;
         mo_upload_offsets(work, at, offsets, E);
         HIPCHK(hipMemcpy(work + at.pairs, pairs, sizeof(int32_t) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice));
-        if (dtype == KLNMF_DT_F64)
-            mo_angles<double>(records, T, n_markers, n_pairs, E, delay, padding, bounds, vel_bounds, work, at, angles, lda, vels, ldv);
-        else
-            mo_angles<float>(records, T, n_markers, n_pairs, E, delay, padding, bounds, vel_bounds, work, at, angles, lda, vels, ldv);
+        by_dtype(dtype, [&](auto tag) {
+            mo_angles<tag_t<decltype(tag)>>(records, T, n_markers, n_pairs, E, delay, padding, bounds, vel_bounds, work, at, angles, lda,
+                                            vels, ldv);
+        });
         HIPCHK(hipGetLastError());
     });
 }
@@ -195,18 +190,19 @@ int klnmf_motion_angles_device(int device, int dtype, const void *records, int64
 int klnmf_motion_whiten_device(int device, int dtype, const void *x, int64_t ld, int64_t T, int64_t C, void *d_work,
                                uint64_t work_bytes, void *out, int64_t ldo, double *d_mean, double *d_std) {
     return guarded([&] {
-        const MoWho w{"klnmf_motion_whiten_device"};
+        const MoWho w{{"klnmf_motion_whiten_device"}};
         w.dtype(dtype);
         w.frames(T, 1);
         if (!x || !out || !d_mean || !d_std || !d_work) w.bad("null x, out, mean, std or workspace");
-        if (C < 1 || C >= kMoMaxInt) w.bad("C < 1");
+        if (C < 1 || C >= kMaxInt) w.bad("C < 1");
         if (ld < C || ldo < C) w.bad("a stride below C");
         if ((C + kMoMomCols - 1) / kMoMomCols > kMoMaxGridY) w.unsupp("more than 32 * 65535 columns");
         const MoLayout at(T, C, 1, 1, 0, 1, 0);
-        if (work_bytes < (uint64_t)at.total) w.bad("workspace below klnmf_motion_work_bytes");
+        w.workspace(work_bytes, at.total, "klnmf_motion_work_bytes");
         HIPCHK(hipSetDevice(device));
-        if (dtype == KLNMF_DT_F64) mo_whiten<double>(x, ld, T, C, (unsigned char *)d_work, at, out, ldo, d_mean, d_std);
-        else mo_whiten<float>(x, ld, T, C, (unsigned char *)d_work, at, out, ldo, d_mean, d_std);
+        by_dtype(dtype, [&](auto tag) {
+            mo_whiten<tag_t<decltype(tag)>>(x, ld, T, C, (unsigned char *)d_work, at, out, ldo, d_mean, d_std);
+        });
         HIPCHK(hipGetLastError());
     });
 }
@@ -216,7 +212,7 @@ int klnmf_motion_kmeans_device(int device, int dtype, const void *points, int64_
                                int max_iter, void *d_work, uint64_t work_bytes, int32_t *d_alive, double *d_distortion,
                                int32_t *d_iters, int32_t *d_labels, int *unfinished) {
     return guarded([&] {
-        const MoWho w{"klnmf_motion_kmeans_device"};
+        const MoWho w{{"klnmf_motion_kmeans_device"}};
         w.dtype(dtype);
         w.frames(T, 1);
         if (!points || !set_of || !codebooks || !d_alive || !d_distortion || !d_iters || !d_work || !unfinished)
@@ -229,14 +225,15 @@ int klnmf_motion_kmeans_device(int device, int dtype, const void *points, int64_
         for (int64_t p = 0; p < P; ++p)
             if (set_of[p] < 0 || set_of[p] >= D) w.bad("a set_of entry outside [0, D)");
         const MoLayout at(T, 0, d, K, P, D, 0);
-        if (work_bytes < (uint64_t)at.total) w.bad("workspace below klnmf_motion_work_bytes");
+        w.workspace(work_bytes, at.total, "klnmf_motion_work_bytes");
         HIPCHK(hipSetDevice(device));
         unsigned char *work = (unsigned char *)d_work;
         HIPCHK(hipMemcpy(work + at.set_of, set_of, sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice));
         const MoKm call{points, codebooks, set_stride, ld, (int32_t)T, (int32_t)d, (int32_t)K, (int32_t)P,
                         (const int32_t *)(work + at.set_of), d_alive, (int32_t *)(work + at.done), (double *)(work + at.prev)};
-        *unfinished = dtype == KLNMF_DT_F64 ? mo_kmeans<double>(call, thresh, max_iter, work, at, d_distortion, d_iters, d_labels)
-                                            : mo_kmeans<float>(call, thresh, max_iter, work, at, d_distortion, d_iters, d_labels);
+        by_dtype(dtype, [&](auto tag) {
+            *unfinished = mo_kmeans<tag_t<decltype(tag)>>(call, thresh, max_iter, work, at, d_distortion, d_iters, d_labels);
+        });
     });
 }
 
@@ -244,7 +241,7 @@ int klnmf_motion_hist_device(int device, int dtype, const void *points, int64_t 
                              int64_t D, const void *codebooks, int64_t K, const int64_t *offsets, int64_t E, int soft,
                              double alpha, void *d_work, uint64_t work_bytes, void *out, int64_t ldo) {
     return guarded([&] {
-        const MoWho w{"klnmf_motion_hist_device"};
+        const MoWho w{{"klnmf_motion_hist_device"}};
         w.dtype(dtype);
         w.frames(T, 1);
         if (!points || !codebooks || !out || !d_work) w.bad("null points, codebooks, out or workspace");
@@ -256,14 +253,13 @@ int klnmf_motion_hist_device(int device, int dtype, const void *points, int64_t 
         w.limits(d, K, 0, D);
         if (ldo < D * K) w.bad("an output stride below D * K");
         const MoLayout at(T, 0, d, K, 0, D, E);
-        if (work_bytes < (uint64_t)at.total) w.bad("workspace below klnmf_motion_work_bytes");
+        w.workspace(work_bytes, at.total, "klnmf_motion_work_bytes");
         HIPCHK(hipSetDevice(device));
         unsigned char *work = (unsigned char *)d_work;
         mo_upload_offsets(work, at, offsets, E);
         const MoHist call{points, codebooks, set_stride, ld, (int32_t)d, (int32_t)K, (int32_t)D, soft, alpha,
                           (const int64_t *)(work + at.offsets)};
-        if (dtype == KLNMF_DT_F64) mo_hist<double>(call, E, work, out, ldo);
-        else mo_hist<float>(call, E, work, out, ldo);
+        by_dtype(dtype, [&](auto tag) { mo_hist<tag_t<decltype(tag)>>(call, E, work, out, ldo); });
         HIPCHK(hipGetLastError());
     });
 }

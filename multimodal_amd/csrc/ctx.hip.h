@@ -19,10 +19,15 @@
 //                    126-136): checks, workspace layout and the launches of information.hip.h, included by that unit alone
 //   api_hac.hip      the windowed co-occurrence histograms of include/klnmf_hac.h (features/hac.py:152-196 behind its MFCCs, for the
 //                    windows of samples/image_sound_eval_sliding.py:97-113): checks, workspace layout and the launches of
-//                    hac.hip.h
+//                    hac.hip.h behind the quantiser of vq.hip.h
 //   api_kmeans.hip   the codebook builders' device half of include/klnmf_kmeans.h (features/hac.py:68-107: Lloyd iterations and
 //                    the Gram matrix of a cluster's members): checks, workspace layout and the launches of kmeans.hip.h, included
-//                    by that unit alone
+//                    by that unit alone behind vq.hip.h
+//   api_motion.hip   the motion modality's device half of include/klnmf_motion.h: checks, workspace layout and the launches of
+//                    motion.hip.h, included by that unit alone
+// The feature units (the nearest part of api_eval.hip, api_info.hip, api_hac.hip, api_kmeans.hip, api_motion.hip) word their
+// refusals, cut up their workspaces, own their scratch and pick their element type through feature_host.hip.h; the quantiser of
+// api_hac.hip and api_kmeans.hip is vq.hip.h's.
 // This header: error handling, the type dispatch of the host-facing kernels, the device block cache and the arena over it
 // (DeviceBlocks), the staged host upload, the development switches, the mask state (PresenceState) and the context itself -- its
 // state in four groups, one per lifetime (ContextState, ProblemState, LoopState, LoopRecord) -- and what contexts and batches share

@@ -2,11 +2,10 @@
 // window with `compute_coocurrences` (features/hac.py:152-175: scipy's vq, the lagged pair codes, np.bincount) and sp.vstack
 // (samples/image_sound_eval_sliding.py:97-113), for all windows in a fixed number of launches.
 //
-//   k_hac_vq<T>      every frame of every stream quantised ONCE: q[t] = the index of the nearest codebook row, the squared
-//                    distance formed in fp64, j ascending, every difference, product and sum rounded on its own (no fused
-//                    multiply-add), the lowest index among equal minima; a NaN distance never wins.  A thread per frame; the
-//                    stream's codebook and the block's frames (transposed, so that lanes read neighbouring words) are staged in
-//                    LDS where the host found room for them (HacStream::stage) and read from global memory / L2 otherwise.
+//   k_hac_vq<T>      every frame of every stream quantised ONCE: q[t] = the code of vq.hip.h (its rule, its staging: a thread per
+//                    frame; the stream's codebook and the block's frames are staged in LDS where the host found room for them,
+//                    HacStream::stage, and read from global memory / L2 otherwise).  The unit that includes this header includes
+//                    vq.hip.h before it.
 //   k_hac_pass<T, 0> one workgroup per segment = (window, stream, lag): the number of DISTINCT pair codes q[t + lag] * K + q[t].
 //   k_hac_scan       exclusive scan of the segment counts: the segment offsets, every (S * L)-th of them a row pointer, nnz.
 //   k_hac_pass<T, 1> the same text again: the distinct codes in ascending order and their counts, at the segment's offset.
@@ -27,12 +26,11 @@ constexpr int kHacThreads = 256;
 constexpr int kHacSortMax = 4096;              // pair codes of a segment the sort route takes
 constexpr int kHacDenseBins = 36864;           // K^2 of the dense route: 144 KiB of int32 counters (K <= 192)
 constexpr int kHacVqLds = 64 * 1024;           // bytes of LDS k_hac_vq may stage a codebook and a frame tile in
-constexpr int kHacFrameStride = kHacThreads + 1;   // words between the elements j, j + 1 of a staged frame (bank spread)
 constexpr int kHacScanItems = 8;
 constexpr int32_t kHacSentinel = 0x7fffffff;
 
 enum { HAC_ROUTE_NONE = 0, HAC_ROUTE_SORT = 1, HAC_ROUTE_DENSE = 2, HAC_ROUTE_UNFIT = -1 };
-enum { HAC_STAGE_CODEBOOK = 1, HAC_STAGE_FRAMES = 2 };
+static_assert(kHacThreads == kVqTile, "k_hac_vq: vq.hip.h's tile, a thread per frame");
 
 // The route of a segment of n_codes pair codes over a codebook of K units.
 __host__ __device__ inline int hac_route(int64_t n_codes, int64_t K) {
@@ -46,7 +44,7 @@ struct HacStream {                              // one stream: frames [T, d], co
     int64_t ldx, ldc;
     int32_t d, K;
     int32_t block0;                             // the first workgroup of the stream in k_hac_vq's grid
-    int32_t stage;                              // HAC_STAGE_*: what the host found room for in LDS
+    int32_t stage;                              // VQ_STAGE_*: what the host found room for in LDS
 };
 struct HacStreams {                             // k_hac_vq's table, passed by value
     HacStream s[kHacMaxStreams];
@@ -59,25 +57,6 @@ struct HacPlan {                                // the passes' table, passed by 
     int32_t S, L, T, pad;
 };
 
-// The code of one frame `xp[j * sx]` (j < d) against the codebook rows cb + k * ldc.
-template <typename T>
-__device__ __forceinline__ int hac_nearest_code(const T *xp, int64_t sx, const T *cb, int64_t ldc, int K, int d) {
-    double best = __longlong_as_double(0x7ff0000000000000LL);
-    int q = 0;
-    for (int k = 0; k < K; ++k) {
-        const T *c = cb + (int64_t)k * ldc;
-        double acc = 0.0;
-        for (int j = 0; j < d; ++j) {
-            const double df = __dsub_rn((double)xp[(int64_t)j * sx], (double)c[j]);
-            acc = __dadd_rn(acc, __dmul_rn(df, df));
-        }
-        const bool ahead = acc < best;          // strict: the lowest index keeps a tie, a NaN never wins
-        best = ahead ? acc : best;
-        q = ahead ? k : q;
-    }
-    return q;
-}
-
 template <typename T>
 __global__ __launch_bounds__(kHacThreads) void k_hac_vq(HacStreams tab, int32_t *codes) {
     extern __shared__ double hac_vq_lds[];
@@ -89,25 +68,13 @@ __global__ __launch_bounds__(kHacThreads) void k_hac_vq(HacStreams tab, int32_t 
     const int64_t frame0 = (int64_t)((int)blockIdx.x - st.block0) * kHacThreads;
     const int64_t t = frame0 + threadIdx.x;
     T *cbs = (T *)hac_vq_lds;
-    T *xs = cbs + ((st.stage & HAC_STAGE_CODEBOOK) ? (int64_t)K * d : 0);
-    if (st.stage & HAC_STAGE_CODEBOOK)
-        for (int e = threadIdx.x; e < K * d; e += kHacThreads) cbs[e] = cb[(int64_t)(e / d) * st.ldc + e % d];
-    if (st.stage & HAC_STAGE_FRAMES)
-        for (int e = threadIdx.x; e < kHacThreads * d; e += kHacThreads) {
-            const int f = e / d, j = e % d;
-            xs[j * kHacFrameStride + f] = frame0 + f < tab.T ? x[(frame0 + f) * st.ldx + j] : (T)0;
-        }
+    T *xs = cbs + ((st.stage & VQ_STAGE_CODEBOOK) ? (int64_t)K * d : 0);
+    if (st.stage & VQ_STAGE_CODEBOOK) vq_stage_codebook<T>(cbs, cb, st.ldc, K * d, d);
+    if (st.stage & VQ_STAGE_FRAMES)
+        vq_stage_frames<T>(xs, x, st.ldx, frame0, (int)min((int64_t)kHacThreads, (int64_t)tab.T - frame0), d);
     __syncthreads();
     if (t >= tab.T) return;
-    int q;
-    if (st.stage & HAC_STAGE_FRAMES) {
-        if (st.stage & HAC_STAGE_CODEBOOK) q = hac_nearest_code<T>(xs + threadIdx.x, kHacFrameStride, cbs, d, K, d);
-        else q = hac_nearest_code<T>(xs + threadIdx.x, kHacFrameStride, cb, st.ldc, K, d);
-    } else {
-        if (st.stage & HAC_STAGE_CODEBOOK) q = hac_nearest_code<T>(x + t * st.ldx, 1, cbs, d, K, d);
-        else q = hac_nearest_code<T>(x + t * st.ldx, 1, cb, st.ldc, K, d);
-    }
-    codes[(int64_t)s * tab.T + t] = q;
+    codes[(int64_t)s * tab.T + t] = vq_code<T>(st.stage, x, st.ldx, t, xs, cb, st.ldc, cbs, K, d);
 }
 
 // Ordered compaction over the positions [0, M): emit(rank, i) for every i with flag(i), rank = the flagged positions before i.

@@ -14,7 +14,9 @@
 //                     the wave puts several rows into one wave (lane -> (row, atom)).  The label check rides here.
 //   k_info_mi         a workgroup per atom: the column totals of its table in LDS, then one thread per label.
 // Every count is an exact integer and every floating-point order is fixed: the outputs do not depend on scheduling.
+// The bin edges and k_info_mi's sums round every product and sum on its own: plain operators, contraction off (vq.hip.h: why).
 #pragma once
+#pragma clang fp contract(off)
 #include "common.hip.h"
 
 namespace klnmf {
@@ -67,8 +69,8 @@ __device__ __forceinline__ int info_job_of_atom(const InfoJob *jobs, int count, 
 // last element set to stop; step == 0: y = arange / div * delta + start)
 __device__ __forceinline__ double info_edge(int b, int B, double lo, double hi, double step, double delta) {
     if (b >= B) return hi;
-    const double y = step != 0.0 ? __dmul_rn((double)b, step) : __dmul_rn((double)b / (double)B, delta);
-    return __dadd_rn(y, lo);
+    const double y = step != 0.0 ? (double)b * step : (double)b / (double)B * delta;
+    return y + lo;
 }
 
 // The bin of v: the b with e_b <= v < e_(b+1), v == hi in B - 1.  `inv` = B / (hi - lo) only seeds the guess; the edges decide.
@@ -235,14 +237,14 @@ KL_GLOBAL __launch_bounds__(kInfoThreads) void k_info_mi(const InfoJob *jobs, in
             const int t = t0[b];
             if (t > 0) {
                 const double p = (double)t / N, pc = (double)tot[b] / N;
-                I = __dadd_rn(I, __dmul_rn(p, log(p / __dmul_rn(pr0, pc))));
+                I = I + p * log(p / (pr0 * pc));
             }
         }
         for (int b = 0; b < B; ++b) {
             const int t = tot[b] - t0[b];
             if (t > 0) {
                 const double p = (double)t / N, pc = (double)tot[b] / N;
-                I = __dadd_rn(I, __dmul_rn(p, log(p / __dmul_rn(pr1, pc))));
+                I = I + p * log(p / (pr1 * pc));
             }
         }
         info[atom0 * L + (int64_t)l * k + a] = I;

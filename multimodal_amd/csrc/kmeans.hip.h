@@ -2,11 +2,10 @@
 // vq, kmeans2 and an SVD of the largest cluster's members (features/hac.py:68-107), as a fixed number of launches per iteration.
 //
 //   k_km_assign<T>   one workgroup per GROUP of kKmGroup = 4096 consecutive frames, walked as 16 tiles of kKmTile = 256 frames.
-//                    Per tile: a thread per frame forms its label with km_nearest_code (features.hac.quantize's rule: fp64
-//                    squared distance, j ascending, every difference, product and sum rounded on its own, the lowest index among
-//                    equal minima, a NaN distance never wins), stores it, and leaves it in LDS; then the tile's frames are added,
-//                    frame by frame in ascending order, to the group's K * d fp64 accumulators and K int32 counts, which stay in
-//                    LDS across the group's tiles.  At the end the group's partial sums and counts go to the workspace.
+//                    Per tile: a thread per frame forms its label with vq.hip.h's code (features.hac.quantize's rule), stores
+//                    it, and leaves it in LDS; then the tile's frames are added, frame by frame in ascending order, to the
+//                    group's K * d fp64 accumulators and K int32 counts, which stay in LDS across the group's tiles.  At the
+//                    end the group's partial sums and counts go to the workspace.
 //   k_km_update<T>   a thread per codebook element: the groups' partials added in ascending group order, the count likewise
 //                    (integers), the new element = sum / count.
 //   k_km_gram<T>     one workgroup per group: sum over the group's member frames (label == cluster, or all with cluster = -1),
@@ -30,13 +29,11 @@
 //
 // LDS of k_km_assign: K * d doubles + K + 256 ints, at most kKmMaxKd * 8 + kKmMaxKd * 4 + 1024 = 160768 of the CU's 163840
 // bytes at the bound K * d <= kKmMaxKd = 13312 (150 x 39 = 5850 and 1000 x 13 = 13000 fit).  Where more room is left the host
-// stages the codebook and then the tile's frames (transposed: lanes read neighbouring words) as k_hac_vq does.
+// stages the codebook and then the tile's frames (vq_staging; k_hac_vq does the same).
 // Every store to global memory is a plain vector store by exactly one thread.
 //
-// Contraction.  "Rounded on its own" needs the compiler's contraction of a product and a sum into a fused multiply-add off,
-// and device code has it on by default; __dmul_rn / __dadd_rn do not help, they are the plain operators inside a header that
-// was parsed with the default (hac_nearest_code, written with them, compiles to fused multiply-adds; so the assignment here is
-// km_nearest_code, the same text in plain operators).  Everything below this line is compiled with contraction off.
+// Contraction.  "Rounded on its own" needs the compiler's contraction of a product and a sum into a fused multiply-add off:
+// vq.hip.h, included before this header, says why the _rn intrinsics do not give that; the pragma below restates vq.hip.h's.
 #pragma once
 #pragma clang fp contract(off)
 
@@ -48,49 +45,11 @@ constexpr int kKmGroupTiles = 16;
 constexpr int kKmGroup = kKmTile * kKmGroupTiles;   // frames per group = per workgroup: the unit of the order rule
 constexpr int kKmMaxKd = 13312;                     // K * d of a Lloyd call: 104 KiB of fp64 accumulators
 constexpr int kKmLds = 160 * 1024;                  // the CU's LDS
-constexpr int kKmFrameStride = kKmTile + 1;         // words between the elements j, j + 1 of a staged frame (bank spread)
 constexpr int kKmGramMaxD = 64;
 constexpr int kKmGramTile = 64;                     // frames staged per step of k_km_gram: 64 x 64 doubles = 32 KiB
 constexpr int kKmGramPairs = (kKmGramMaxD * (kKmGramMaxD + 1) / 2 + kKmThreads - 1) / kKmThreads;   // 9 pairs per thread
 
-enum { KM_STAGE_CODEBOOK = 1, KM_STAGE_FRAMES = 2 };
-
-// hac_nearest_code's rule: the code of one frame `xp[j * sx]` (j < d) against the codebook rows cb + k * ldc.
-template <typename T>
-__device__ __forceinline__ int km_nearest_code(const T *xp, int64_t sx, const T *cb, int64_t ldc, int K, int d) {
-    double best = __longlong_as_double(0x7ff0000000000000LL);
-    int q = 0, k = 0;
-    // four rows at a time: the frame's element is read once for the four, and four independent sums are in flight (a workgroup
-    // with its accumulators in LDS is often alone on its CU, one wave per SIMD).  Each row's sum is formed exactly as below.
-    for (; k + 4 <= K; k += 4) {
-        const T *c0 = cb + (int64_t)k * ldc, *c1 = c0 + ldc, *c2 = c1 + ldc, *c3 = c2 + ldc;
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-        for (int j = 0; j < d; ++j) {
-            const double xv = (double)xp[(int64_t)j * sx];
-            const double d0 = xv - (double)c0[j], d1 = xv - (double)c1[j], d2 = xv - (double)c2[j], d3 = xv - (double)c3[j];
-            a0 = a0 + d0 * d0;
-            a1 = a1 + d1 * d1;
-            a2 = a2 + d2 * d2;
-            a3 = a3 + d3 * d3;
-        }
-        if (a0 < best) { best = a0; q = k; }    // in ascending order, strict: as below
-        if (a1 < best) { best = a1; q = k + 1; }
-        if (a2 < best) { best = a2; q = k + 2; }
-        if (a3 < best) { best = a3; q = k + 3; }
-    }
-    for (; k < K; ++k) {
-        const T *c = cb + (int64_t)k * ldc;
-        double acc = 0.0;
-        for (int j = 0; j < d; ++j) {
-            const double df = (double)xp[(int64_t)j * sx] - (double)c[j];
-            acc = acc + df * df;
-        }
-        const bool ahead = acc < best;          // strict: the lowest index keeps a tie, a NaN never wins
-        best = ahead ? acc : best;
-        q = ahead ? k : q;
-    }
-    return q;
-}
+static_assert(kKmThreads == kVqTile && kKmTile == kVqTile, "k_km_assign: vq.hip.h's tile, a thread per frame");
 
 __host__ __device__ inline int64_t km_groups(int64_t T) { return T > 0 ? (T + kKmGroup - 1) / kKmGroup : 1; }
 
@@ -99,7 +58,7 @@ struct KmCall {                                     // one Lloyd call; device po
     void *cb;
     int64_t ldx, ldc;
     int32_t T, d, K;
-    int32_t stage;                                  // KM_STAGE_*: what the host found room for in LDS
+    int32_t stage;                                  // VQ_STAGE_*: what the host found room for in LDS
     int32_t sums;                                   // 0: labels and counts alone (n_iter = 0)
 };
 
@@ -112,13 +71,12 @@ __global__ __launch_bounds__(kKmThreads) void k_km_assign(KmCall c, int32_t *lab
     const T *x = (const T *)c.x, *cb = (const T *)c.cb;
     double *acc = km_lds;
     T *cbs = (T *)(acc + Kd);
-    T *xs = cbs + ((c.stage & KM_STAGE_CODEBOOK) ? Kd : 0);
-    int32_t *cnt = (int32_t *)(xs + ((c.stage & KM_STAGE_FRAMES) ? kKmFrameStride * d : 0));
+    T *xs = cbs + ((c.stage & VQ_STAGE_CODEBOOK) ? Kd : 0);
+    int32_t *cnt = (int32_t *)(xs + ((c.stage & VQ_STAGE_FRAMES) ? kVqFrameStride * d : 0));
     int32_t *lab = cnt + K;
     for (int e = tid; e < Kd; e += kKmThreads) acc[e] = 0.0;
     for (int k = tid; k < K; k += kKmThreads) cnt[k] = 0;
-    if (c.stage & KM_STAGE_CODEBOOK)
-        for (int e = tid; e < Kd; e += kKmThreads) cbs[e] = cb[(int64_t)(e / d) * c.ldc + e % d];
+    if (c.stage & VQ_STAGE_CODEBOOK) vq_stage_codebook<T>(cbs, cb, c.ldc, Kd, d);
     // the accumulators of this thread: column j0 (+ 256, ...) of the clusters [k_lo, k_hi)
     const bool wide = d >= kKmThreads;
     const int nr = wide ? 1 : kKmThreads / d;
@@ -132,22 +90,11 @@ __global__ __launch_bounds__(kKmThreads) void k_km_assign(KmCall c, int32_t *lab
         const int64_t frame0 = group0 + (int64_t)tile * kKmTile;
         if (frame0 >= c.T) break;                   // (block-uniform)
         const int n = (int)min((int64_t)kKmTile, (int64_t)c.T - frame0);
-        if (c.stage & KM_STAGE_FRAMES)
-            for (int e = tid; e < kKmTile * d; e += kKmThreads) {
-                const int f = e / d, j = e % d;
-                xs[j * kKmFrameStride + f] = f < n ? x[(frame0 + f) * c.ldx + j] : (T)0;
-            }
+        if (c.stage & VQ_STAGE_FRAMES) vq_stage_frames<T>(xs, x, c.ldx, frame0, n, d);
         __syncthreads();                            // (the staged tile; the first time also the zeros and the codebook)
         if (tid < n) {
             const int64_t t = frame0 + tid;
-            int q;
-            if (c.stage & KM_STAGE_FRAMES) {
-                if (c.stage & KM_STAGE_CODEBOOK) q = km_nearest_code<T>(xs + tid, kKmFrameStride, cbs, d, K, d);
-                else q = km_nearest_code<T>(xs + tid, kKmFrameStride, cb, c.ldc, K, d);
-            } else {
-                if (c.stage & KM_STAGE_CODEBOOK) q = km_nearest_code<T>(x + t * c.ldx, 1, cbs, d, K, d);
-                else q = km_nearest_code<T>(x + t * c.ldx, 1, cb, c.ldc, K, d);
-            }
+            const int q = vq_code<T>(c.stage, x, c.ldx, t, xs, cb, c.ldc, cbs, K, d);
             labels[t] = q;
             lab[tid] = q;
         }
@@ -157,7 +104,7 @@ __global__ __launch_bounds__(kKmThreads) void k_km_assign(KmCall c, int32_t *lab
             if (l >= k_lo && l < k_hi) {
                 if (c.sums)
                     for (int j = j0; j < d; j += kKmThreads) {
-                        const double v = (c.stage & KM_STAGE_FRAMES) ? (double)xs[j * kKmFrameStride + f]
+                        const double v = (c.stage & VQ_STAGE_FRAMES) ? (double)xs[j * kVqFrameStride + f]
                                                                      : (double)x[(frame0 + f) * c.ldx + j];
                         acc[l * d + j] = acc[l * d + j] + v;
                     }

@@ -29,7 +29,7 @@
 // +0, the groups ascending from +0.  The numpy twin (multimodal_amd/features/angle_histograms.py) restates it.
 // No two threads ever touch one accumulator (the ownership of k_km_assign); no floating-point atomic exists in this file; every
 // store to global memory is a plain vector store by exactly one thread; no array is indexed dynamically outside LDS and global
-// memory, so nothing goes to scratch.  Everything below is compiled with contraction off (kmeans.hip.h says why).
+// memory, so nothing goes to scratch.  Everything below is compiled with contraction off (vq.hip.h says why).
 #pragma once
 #pragma clang fp contract(off)
 
@@ -239,8 +239,8 @@ __device__ __forceinline__ void mo_stage_points(const T *x, int64_t ld, int64_t 
     }
 }
 
-// km_nearest_code's rule over the live rows of the staged codebook cbs [K, d]: the squared distance of staged point f to row k,
-// j ascending, every operation rounded on its own.
+// vq.hip.h's rule (vq_nearest_code) over the live rows of the staged codebook cbs [K, d]: the squared distance of staged point f
+// to row k, j ascending, every operation rounded on its own.
 __device__ __forceinline__ double mo_dist2(const double *xs, int f, const double *row, int d) {
     double acc = 0.0;
     for (int j = 0; j < d; ++j) {

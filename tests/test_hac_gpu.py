@@ -90,6 +90,41 @@ def test_ties_go_to_the_lowest_index_and_f32_inputs_are_compared_in_f64():
     assert list(hac.quantize(x, c)) == [1, 1, 1] and list(labels_on_device(x, c)) == [1, 1, 1]
 
 
+def fused_distance(row):
+    """The squared distance of the origin to `row` as a loop of fused multiply-adds forms it: acc = fl(v * v + acc), exact
+    arithmetic rounded once per step."""
+    from fractions import Fraction
+    acc = 0.0
+    for v in row:
+        acc = float(Fraction(float(v)) * Fraction(float(v)) + Fraction(acc))
+    return acc
+
+
+def test_labels_where_fused_and_unfused_distances_disagree():
+    """Frames at the origin against the codebook [[a, b], [b, a]], fp64.  Rounded on their own, the two distances are the same two
+    products added in either order: an exact tie, label 0.  A fused loop forms fl(fl(a^2) + b^2) against fl(fl(b^2) + a^2), which
+    differ for many (a, b); the pairs kept here are those for which it would pick label 1 (asserted, so that the inputs cannot
+    stop being adversarial).  The histogram builder, the codebook builder and the host twin must all say 0.  float32 inputs cannot
+    show the difference with frames at the origin -- products of 24-bit values are exact in fp64 -- so the f32 instantiation
+    rests on its device code holding no fused fp64 multiply-add (profiles/feature_units_refactor_ab.txt)."""
+    rng = np.random.default_rng(0)
+    pairs = []
+    for _ in range(2000):
+        a, b = rng.uniform(1, 2, 2)
+        if fused_distance((b, a)) < fused_distance((a, b)):
+            pairs.append((a, b))
+        if len(pairs) == 8:
+            break
+    assert len(pairs) == 8
+    x = np.zeros((3, 2))
+    for a, b in pairs:
+        c = np.array([[a, b], [b, a]])
+        assert a * a + b * b == b * b + a * a and fused_distance(c[1]) < fused_distance(c[0])
+        assert list(hac.quantize(x, c)) == [0, 0, 0]
+        assert list(labels_on_device(x, c)) == [0, 0, 0], (a, b)
+        assert list(_native.kmeans(x, c, n_iter=0)[1]) == [0, 0, 0], (a, b)
+
+
 def test_a_single_frame_and_no_frame():
     x, c = hc.coded([2], 4)
     got = check([x], [c], [(0, 1), (0, 0), (1, 1)], [1])

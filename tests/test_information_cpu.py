@@ -11,11 +11,11 @@ import pytest
 from multimodal_amd import _native, device_data, device_experiment as dx, evaluation
 from multimodal_amd.lib import metrics
 from tests import information_cases as ic
-from tests.test_batch_csr_cpu import declared_in
+from tests.test_batch_csr_cpu import check_header_tables, declared_in, other_headers
 from tests.test_nearest_cpu import CpuEvaluation, host_matrix, learner_of
 
 NEW = {'klnmf_information_work_bytes', 'klnmf_information_many_device', 'klnmf_information'}
-OTHERS = ('klnmf.h', 'klnmf_batch.h', 'klnmf_batch_mask.h', 'klnmf_batch_csr.h', 'klnmf_beta.h', 'klnmf_batch_beta.h', 'klnmf_nearest.h')
+OTHERS = other_headers('klnmf_information.h')
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'g20_information.npz')
 
 
@@ -34,12 +34,7 @@ def test_every_declared_information_symbol_is_bound_and_exported():
 
 
 def test_the_other_headers_declare_what_they_declared():
-    tables = (_native.SIGNATURES, _native.BATCH_SIGNATURES, _native.BATCH_MASK_SIGNATURES, _native.BATCH_CSR_SIGNATURES,
-              _native.BETA_SIGNATURES, _native.BATCH_BETA_SIGNATURES, _native.NEAREST_SIGNATURES)
-    assert [len(t) for t in tables] == [79, 15, 3, 3, 4, 3, 3]
-    for header, table in zip(OTHERS, tables):
-        assert declared_in(header) == set(table), header
-        assert not (NEW & set(table)), header
+    check_header_tables()                # (and NEW is this header's own table: the test above)
 
 
 def test_the_workspace_size_and_the_route_are_host_arithmetic():

@@ -15,14 +15,13 @@ import pytest
 from multimodal_amd import _native
 from multimodal_amd.features import angle_histograms as ah
 from tests import motion_cases as mc
-from tests.test_batch_csr_cpu import declared_in
+from tests.test_batch_csr_cpu import check_header_tables, declared_in, other_headers
 from tests.test_hac_cpu import host_matrix
 from tests.test_kmeans_cpu import write_matrix
 
 NEW = {'klnmf_motion_work_bytes', 'klnmf_motion_angles_device', 'klnmf_motion_whiten_device', 'klnmf_motion_kmeans_device',
        'klnmf_motion_hist_device'}
-OTHERS = ('klnmf.h', 'klnmf_batch.h', 'klnmf_batch_mask.h', 'klnmf_batch_csr.h', 'klnmf_beta.h', 'klnmf_batch_beta.h',
-          'klnmf_nearest.h', 'klnmf_information.h', 'klnmf_hac.h', 'klnmf_kmeans.h')
+OTHERS = other_headers('klnmf_motion.h')
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'klnmf_motion.h')
 
 
@@ -51,13 +50,7 @@ def test_every_declared_motion_symbol_is_bound_and_exported():
 
 
 def test_the_other_headers_keep_their_sets():
-    tables = (_native.SIGNATURES, _native.BATCH_SIGNATURES, _native.BATCH_MASK_SIGNATURES, _native.BATCH_CSR_SIGNATURES,
-              _native.BETA_SIGNATURES, _native.BATCH_BETA_SIGNATURES, _native.NEAREST_SIGNATURES, _native.INFORMATION_SIGNATURES,
-              _native.HAC_SIGNATURES, _native.KMEANS_SIGNATURES)
-    assert [len(t) for t in tables] == [79, 15, 3, 3, 4, 3, 3, 3, 4, 4]
-    for header, table in zip(OTHERS, tables):
-        assert declared_in(header) == set(table), header
-        assert not (NEW & set(table)), header
+    check_header_tables()                # (and NEW is this header's own table: the test above)
 
 
 def test_every_entry_point_names_the_reference_lines_it_replaces():

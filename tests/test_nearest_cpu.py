@@ -11,10 +11,10 @@ import pytest
 from multimodal_amd import _native, device_data, device_experiment as dx
 from multimodal_amd.learner import MultimodalLearner
 from tests import eval_cases as evc
-from tests.test_batch_csr_cpu import declared_in
+from tests.test_batch_csr_cpu import check_header_tables, declared_in, other_headers
 
 NEW = {'klnmf_nearest_work_bytes', 'klnmf_nearest_many_device', 'klnmf_nearest'}
-OTHERS = ('klnmf.h', 'klnmf_batch.h', 'klnmf_batch_mask.h', 'klnmf_batch_csr.h', 'klnmf_beta.h', 'klnmf_batch_beta.h')
+OTHERS = other_headers('klnmf_nearest.h')
 FOUR = [metric for metric, _suffix in dx.DEVICE_MEASURES]
 
 
@@ -33,12 +33,7 @@ def test_every_declared_nearest_symbol_is_bound_and_exported():
 
 
 def test_the_other_headers_declare_what_they_declared():
-    tables = (_native.SIGNATURES, _native.BATCH_SIGNATURES, _native.BATCH_MASK_SIGNATURES, _native.BATCH_CSR_SIGNATURES,
-              _native.BETA_SIGNATURES, _native.BATCH_BETA_SIGNATURES)
-    assert [len(t) for t in tables] == [79, 15, 3, 3, 4, 3]
-    for header, table in zip(OTHERS, tables):
-        assert declared_in(header) == set(table), header
-        assert not (NEW & set(table)), header
+    check_header_tables()                # (and NEW is this header's own table: the test above)
 
 
 def test_the_workspace_size_and_the_masks_are_host_arithmetic():
