@@ -251,6 +251,18 @@ MOTION_SIGNATURES = {
                                             _c.c_void_p, _i64, _c.c_int, _c.c_double, _c.c_void_p, _c.c_uint64, _c.c_void_p, _i64]),
 }
 
+# name -> (restype, argtypes): every symbol of include/features/klnmf_mfcc.h (the MFCC front end of the sound modality)
+MFCC_SIGNATURES = {
+    'klnmf_mfcc_work_bytes': (_c.c_int, [_i64, _i64, _i64, _i64, _i64, _i64, _c.POINTER(_c.c_uint64)]),
+    'klnmf_mfcc_mel_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _i64, _i64, _i64, _c.c_int, _c.c_void_p,
+                                         _c.c_void_p, _i64, _i64, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p]),
+    'klnmf_mfcc_cepstra_device': (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _i64, _i64,
+                                             _c.c_void_p, _i64,
+                                             _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _i64]),
+    'klnmf_mfcc': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _i64, _i64, _i64, _c.c_int, _c.c_void_p,
+                              _c.c_void_p, _i64, _c.c_void_p, _c.c_void_p, _i64, _i64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _i64]),
+}
+
 # (header under include/, its table) in the order the headers came: load() binds every table, and the tests hold each table against
 # its header's declarations and all of them pairwise disjoint.  A new header adds its table above and one line here.
 HEADER_TABLES = (
@@ -258,6 +270,13 @@ HEADER_TABLES = (
     ('klnmf_batch_csr.h', BATCH_CSR_SIGNATURES), ('klnmf_beta.h', BETA_SIGNATURES), ('klnmf_batch_beta.h', BATCH_BETA_SIGNATURES),
     ('klnmf_nearest.h', NEAREST_SIGNATURES), ('klnmf_information.h', INFORMATION_SIGNATURES), ('klnmf_hac.h', HAC_SIGNATURES),
     ('klnmf_kmeans.h', KMEANS_SIGNATURES), ('klnmf_motion.h', MOTION_SIGNATURES))
+
+# The headers of the feature front ends, under include/features/, with their tables: a registry of its own, bound by load() after
+# HEADER_TABLES.  HEADER_TABLES stays the closed list of the headers directly under include/ -- tests/test_batch_csr_cpu.py holds it
+# against that directory's listing and against the number of exports each of them had, so a header added there would change what
+# an existing test asserts.  A new feature header adds its table above and one line here.
+FEATURE_HEADER_TABLES = (
+    ('features/klnmf_mfcc.h', MFCC_SIGNATURES),)
 
 _lib = None
 
@@ -282,7 +301,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for _, table in HEADER_TABLES:
+    for _, table in HEADER_TABLES + FEATURE_HEADER_TABLES:
         for name, (res, args) in table.items():
             fn = getattr(lib, name)     # AttributeError if a symbol is not exported
             fn.restype = res
@@ -594,6 +613,82 @@ def hac(streams, codebooks, lags, windows, dtype=np.float64, device=0):
     _check(load().klnmf_hac(device, _dt_code(not f32), _dt_code(vdt != np.float32), table, len(streams), int(T), p(lags), len(lags),
                             p(windows), len(windows), p(indptr), capacity, p(indices), p(values), _c.byref(nnz)))
     return indptr, indices[:nnz.value].copy(), values[:nnz.value].copy()
+
+
+MFCC_I16, MFCC_F32, MFCC_F64 = 0, 1, 2                         # KLNMF_MFCC_I16 / _F32 / _F64: the kinds of samples
+MFCC_ROUTES = {'auto': 0, 'fft': 1, 'direct': 2}               # KLNMF_MFCC_ROUTE_*
+MFCC_MAX_MELS = 4096                                           # KLNMF_MFCC_MAX_MELS
+MFCC_SAMPLE_KINDS = {np.dtype(np.int16): MFCC_I16, np.dtype(np.float32): MFCC_F32, np.dtype(np.float64): MFCC_F64}
+
+
+def mfcc_route(n_fft, route='auto'):
+    """The route the transform of `n_fft` points takes -- include/features/klnmf_mfcc.h's rule: 'fft' for the powers of two in
+    [64, 4096], 'direct' for the even sizes in [16, 1024], 'refused' (KLNMF_ERR_UNSUPP) for a size that fits neither or not the
+    route asked for."""
+    n = int(n_fft)
+    fft = 64 <= n <= 4096 and n & (n - 1) == 0
+    direct = 16 <= n <= 1024 and n % 2 == 0
+    if route == 'fft':
+        return 'fft' if fft else 'refused'
+    if route == 'direct':
+        return 'direct' if direct else 'refused'
+    return 'fft' if fft else 'direct' if direct else 'refused'
+
+
+def mfcc_work_bytes(n_utterances, total_samples, total_frames, n_fft, n_mels, n_mfcc):
+    """Bytes of device workspace a `mfcc_mel_device` / `mfcc_cepstra_device` pair needs: klnmf_mfcc_work_bytes."""
+    return _work_bytes('klnmf_mfcc_work_bytes', n_utterances, total_samples, total_frames, n_fft, n_mels, n_mfcc)
+
+
+def _i64_array(a):
+    a = np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+    return a, a.ctypes.data_as(_c.c_void_p)
+
+
+def mfcc_mel_device(d_samples, sample_kind, sample_offsets, n_fft, hop, d_window, d_mel, n_mels, total_frames, d_work, work_bytes,
+                    d_S, d_Smax, route='auto', device=0):
+    """Frames, window, transform, power and filter bank of the utterances [offsets[u], offsets[u + 1]) of the DEVICE samples: the
+    fp64 energies [total_frames, n_mels] at d_S and the utterances' maxima at d_Smax -- klnmf_mfcc_mel_device."""
+    off, off_p = _i64_array(sample_offsets)
+    _check(load().klnmf_mfcc_mel_device(device, int(sample_kind), _ptr(d_samples), off_p, len(off) - 1, int(n_fft), int(hop),
+                                        MFCC_ROUTES[route] if route in MFCC_ROUTES else int(route), _ptr(d_window), _ptr(d_mel),
+                                        int(n_mels), int(total_frames), _ptr(d_work), int(work_bytes), _ptr(d_S), _ptr(d_Smax)))
+
+
+def mfcc_cepstra_device(d_S, d_Smax, d_dct, d_dct_sums, n_mels, n_mfcc, frame_offsets, d_work, work_bytes, d_mfcc, d_delta1, d_delta2, ld,
+                        f64=True, device=0):
+    """Log, floor, DCT (d_dct_sums: the basis' exact row sums, fp64 [n_mfcc]) and the two deltas: the three streams [total_frames, n_mfcc] (float64, or float32 with f64=False), rows
+    `ld` apart -- klnmf_mfcc_cepstra_device."""
+    off, off_p = _i64_array(frame_offsets)
+    _check(load().klnmf_mfcc_cepstra_device(device, _dt_code(f64), _ptr(d_S), _ptr(d_Smax), _ptr(d_dct), _ptr(d_dct_sums), int(n_mels), int(n_mfcc),
+                                            off_p, len(off) - 1, _ptr(d_work), int(work_bytes), _ptr(d_mfcc), _ptr(d_delta1),
+                                            _ptr(d_delta2), int(ld)))
+
+
+def mfcc(samples, sample_offsets, n_fft, hop, window, mel, dct, dct_sums, dtype=np.float64, route='auto', device=0):
+    """The three streams [total_frames, n_mfcc] of `dtype` from HOST arrays: samples (int16 / float32 / float64, the utterances one
+    after the other), window [n_fft], mel [n_mels, n_fft // 2 + 1], dct [n_mfcc, n_mels], dct_sums [n_mfcc] -- klnmf_mfcc."""
+    samples = np.ascontiguousarray(samples)
+    if samples.dtype not in MFCC_SAMPLE_KINDS:
+        raise TypeError("samples are int16, float32 or float64, got %s" % samples.dtype)
+    odt = np.dtype(dtype)
+    if odt not in (np.float32, np.float64):
+        raise TypeError("streams are float32 or float64, got %s" % odt)
+    off, off_p = _i64_array(sample_offsets)
+    window = np.ascontiguousarray(window, dtype=np.float64)
+    mel = np.ascontiguousarray(mel, dtype=np.float64)
+    dct = np.ascontiguousarray(dct, dtype=np.float64)
+    dct_sums = np.ascontiguousarray(dct_sums, dtype=np.float64).reshape(-1)
+    if dct_sums.shape != (dct.shape[0],):
+        raise ValueError('one row sum per row of the basis: %s for %d rows' % (dct_sums.shape, dct.shape[0]))
+    T = int(sum(1 + int(L) // max(1, int(hop)) for L in np.diff(off)))
+    n_mels, n_mfcc = mel.shape[0], dct.shape[0]
+    outs = [np.empty((T, n_mfcc), dtype=odt) for _ in range(3)]
+    p = lambda a: a.ctypes.data_as(_c.c_void_p)
+    _check(load().klnmf_mfcc(device, MFCC_SAMPLE_KINDS[samples.dtype], _dt_code(odt != np.float32), p(samples), off_p, len(off) - 1,
+                             int(n_fft), int(hop), MFCC_ROUTES[route], p(window), p(mel), n_mels, p(dct), p(dct_sums), n_mfcc, T, p(outs[0]),
+                             p(outs[1]), p(outs[2]), n_mfcc))
+    return outs
 
 
 KMEANS_TILE, KMEANS_GROUP = 256, 4096    # KLNMF_KMEANS_TILE, KLNMF_KMEANS_GROUP: the group is the unit of the summation order

@@ -25,7 +25,9 @@
 //                    by that unit alone behind vq.hip.h
 //   api_motion.hip   the motion modality's device half of include/klnmf_motion.h: checks, workspace layout and the launches of
 //                    motion.hip.h, included by that unit alone
-// The feature units (the nearest part of api_eval.hip, api_info.hip, api_hac.hip, api_kmeans.hip, api_motion.hip) word their
+//   api_mfcc.hip     the MFCC front end of include/features/klnmf_mfcc.h (features/hac.py:44-65 and the deltas of :190-192):
+//                    checks, workspace layout, the table of twiddles and the launches of mfcc.hip.h, included by that unit alone
+// The feature units (the nearest part of api_eval.hip, api_info.hip, api_hac.hip, api_kmeans.hip, api_motion.hip, api_mfcc.hip) word their
 // refusals, cut up their workspaces, own their scratch and pick their element type through feature_host.hip.h; the quantiser of
 // api_hac.hip and api_kmeans.hip is vq.hip.h's.
 // This header: error handling, the type dispatch of the host-facing kernels, the device block cache and the arena over it

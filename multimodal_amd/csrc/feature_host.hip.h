@@ -1,5 +1,5 @@
 // What the host halves of the feature units share (api_eval.hip's nearest part, api_info.hip, api_hac.hip, api_kmeans.hip,
-// api_motion.hip; included behind ctx.hip.h): how a refusal is worded, how a caller's workspace is cut up, who owns the device
+// api_motion.hip, api_mfcc.hip; included behind ctx.hip.h): how a refusal is worded, how a caller's workspace is cut up, who owns the device
 // memory of a host-array wrapper, and the pick of a kernel's element type.  No policy lives here: which checks an entry point
 // makes, in which order, and what its workspace holds stay with its unit.
 #pragma once

@@ -1,2 +1,2 @@
-"""Feature extraction behind the reference's front ends (reference multimodal/features/): `hac`, the histograms of acoustic
-co-occurrences from frame streams on."""
+"""Feature extraction behind the reference's front ends (reference multimodal/features/): `mfcc`, audio to cepstra and deltas;
+`hac`, the histograms of acoustic co-occurrences from frame streams (or audio) on; `codebook`; `angle_histograms`."""

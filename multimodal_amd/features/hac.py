@@ -12,9 +12,10 @@ the MFCCs is integer work with an exact answer, and that part lives here:
   evaluation does with a `multiprocessing.Pool` over `process_win` and `sp.vstack` (samples/image_sound_eval_sliding.py:97-113);
 * `frame_windows`, the frame ranges of the reference's `slider` (lib/window.py:345-357) on an integer frame axis.
 
-Not here: the MFCC front end itself -- the reference's `mfcc`, `hac(data, sr, ...)` on audio and `wav2hac` need librosa and the
-recordings.  Callers bring the frame streams; the codebook builders (`build_codebook`, `iterative_kmeans`) are
-`features.codebook`'s, whose device codebooks `windowed_hac` takes as they are.
+The MFCC front end is `features.mfcc`'s (csrc/mfcc.hip.h), under rules stated there; the reference's names on audio -- `mfcc`,
+`hac(data, sr, ...)`, `wav2hac`, `build_codebooks_from_list_of_wav` -- stand at the end of this module on top of it, with
+`hac_many` and `build_codebooks_from_audio` for a whole corpus at once.  The codebook builders (`build_codebook`,
+`iterative_kmeans`) are `features.codebook`'s, whose device codebooks `windowed_hac` takes as they are.
 """
 import numpy as np
 import scipy.sparse as sp
@@ -247,3 +248,63 @@ def windowed_hac(streams, codebooks, windows, lags=DEFAULT_LAGS, dtype=np.float6
                             f64=vf64, device=ordinal)
     rows = DeviceCsrRows((N, F), d_indptr, d_indices, d_data, d_indptr.cpu().numpy(), nnz, vf64)
     return rows if output == 'device' else rows.to_scipy()
+
+
+# ---- from audio: the reference's entry points behind the device front end ------------------------------------------------------------
+def _mfcc_params(values):
+    """The reference's `complete_mfcc_params` (features/hac.py:30-41): n_mfcc = 13 unless given."""
+    params = {'n_mfcc': 13}
+    params.update(values)
+    return params
+
+
+def mfcc(data, sr=22050, n_mfcc=20, device=None, **kwargs):
+    """The reference's `mfcc(data, sr, n_mfcc, **kwargs)` (features/hac.py:44-65): a host array [n_mfcc, T], computed on the GPU
+    under `features.mfcc`'s rules."""
+    from . import mfcc as front
+    streams, _ = front.mfcc_streams(np.asarray(data), sr, n_mfcc=n_mfcc, device=device, output='numpy', **kwargs)
+    return np.ascontiguousarray(streams[0].T)
+
+
+def hac_many(audio_list, sr, codebooks, lags=DEFAULT_LAGS, dtype=np.float64, device=None, output='scipy', **mfcc_params):
+    """The [len(audio_list), F] CSR matrix whose row u is the reference's `hac(audio_list[u], sr, codebooks, lags, **mfcc_params)`
+    (features/hac.py:178-196): ONE `features.mfcc.mfcc_streams` call for the corpus and ONE `windowed_hac` call over the
+    utterances' frame spans; the streams never leave the device.  output: 'scipy' or 'device' (a `DeviceCsrRows`, what
+    `MultimodalLearner.reconstruct_internal` takes)."""
+    from . import mfcc as front
+    streams, spans = front.mfcc_streams(audio_list, sr, device=device, output='device', **_mfcc_params(mfcc_params))
+    return windowed_hac(streams, codebooks, spans, lags=lags, dtype=dtype, device=device, output=output)
+
+
+def hac(data, sr, codebooks, lags=DEFAULT_LAGS, device=None, **mfcc_params):
+    """The reference's `hac(data, sr, codebooks, lags, **mfcc_params)` (features/hac.py:178-196): the dense vector of counts of
+    one utterance."""
+    row = hac_many([np.asarray(data)], sr, codebooks, lags=lags, device=device, output='scipy', **mfcc_params)
+    return np.asarray(row.toarray()).ravel().astype(np.int64)
+
+
+def wav2hac(wav_path, codebooks, lags=DEFAULT_LAGS, device=None, **mfcc_params):
+    """The reference's `wav2hac` (features/hac.py:199-201)."""
+    from scipy.io import wavfile
+    sr, data = wavfile.read(wav_path)
+    return hac(data, sr, codebooks, lags=lags, device=device, **mfcc_params)
+
+
+def build_codebooks_from_audio(audio_list, sr, ks, mode='raw', rng=None, device=None, output='numpy', **mfcc_params):
+    """The three codebooks of the reference's `build_codebooks_from_list_of_wav` (features/hac.py:110-149) from the utterances'
+    samples: `mfcc_streams(output='device')` into `features.codebook.build_codebooks`."""
+    from . import codebook, mfcc as front
+    streams, _ = front.mfcc_streams(audio_list, sr, device=device, output='device', **_mfcc_params(mfcc_params))
+    return codebook.build_codebooks(streams, ks, mode=mode, rng=rng, device=device, output=output)
+
+
+def build_codebooks_from_list_of_wav(wavs, ks, mode='raw', rng=None, device=None, output='numpy', **mfcc_params):
+    """The reference's `build_codebooks_from_list_of_wav(wavs, ks, mode, **mfcc_params)` (features/hac.py:110-149); the files
+    share one sample rate (a call has one filter bank)."""
+    from scipy.io import wavfile
+    read = [wavfile.read(w) for w in wavs]
+    rates = set(int(sr) for sr, _ in read)
+    if len(rates) != 1:
+        raise ValueError("files of one sample rate expected, got %s" % sorted(rates))
+    return build_codebooks_from_audio([data for _, data in read], rates.pop(), ks, mode=mode, rng=rng, device=device, output=output,
+                                      **mfcc_params)
